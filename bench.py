@@ -2,7 +2,7 @@
 """Headline benchmark: fp64 5-point Jacobi over a dl_esm_inf r2d_field (+ RCCL halo exchange
 when N > 1), BASELINE.json metric "stencil Mcells/s + achieved HBM GB/s, 16384^2 fp64 grid".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tile 16384] [--alignment 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tile 16384] [--alignment 64] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch: (halo exchange +) one Jacobi sweep of the
@@ -31,7 +31,7 @@ SEED = 20261004
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="number of timed steps (one Jacobi sweep of the tile each)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--tile", type=int, default=16384, help="per-GPU interior is tile x tile")
     ap.add_argument("--alignment", type=int, default=64, help="DL_ESM_ALIGNMENT for the run")
@@ -63,7 +63,43 @@ def parse():
                     help="experiments: dlesm_set_tuning(KEY, INT) before the run (repeatable)")
     ap.add_argument("--rows", type=int, default=None, help="tuning: rows per strip")
     ap.add_argument("--variant", type=int, default=None, help="tuning: kernel variant bits")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the field the last timed step computed to DIR/*.npy (float64; "
+                         "a fixed, seeded sample of it when the tile is large) so that two builds can be compared")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_CELLS = 1 << 22            # --dump-outputs: at most this many sampled cells per run (32 MiB of fp64)
+
+
+def dump_outputs(dirpath, torch, field, rank, world):
+    """--dump-outputs: what the timed path handed its caller after the last timed step -- the internal region of the
+    output field, the cells the Jacobi sweep writes.  If it has at most DUMP_CELLS cells per rank it is written whole
+    (jacobi5_out.npy, ny x nx); otherwise its four edge lines in full (jacobi5_out_edges.npy: first row, last row, first
+    column, last column) and DUMP_CELLS / world cells drawn with numpy's default_rng(SEED) (jacobi5_out_sample.npy, in
+    the order drawn).  The sample depends only on the tile's shape, so two builds run with the same arguments write the
+    same cells.  N > 1: every rank writes its own tile under a .rank<r> suffix.  Total <= 32.5 MiB for any tile."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    it = field.internal
+    out = field.data[it.ystart - 1:it.ystop, it.xstart - 1:it.xstop]       # 1-based inclusive bounds -> view
+    ny, nx = out.shape
+    sfx = f".rank{rank}" if world > 1 else ""
+    arrays = {}
+    budget = DUMP_CELLS // world
+    if nx * ny <= budget:
+        arrays["jacobi5_out"] = out
+    else:
+        arrays["jacobi5_out_edges"] = torch.cat([out[0], out[-1], out[:, 0], out[:, -1]])
+        flat = np.random.default_rng(SEED).integers(0, nx * ny, size=budget, dtype=np.int64)
+        idx = torch.from_numpy(flat).to(out.device)
+        arrays["jacobi5_out_sample"] = out[idx // nx, idx % nx]
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), t.to(dtype=torch.float64).cpu().numpy())
 
 
 def cpu_baseline(host_in, ld, box, budget_s):
@@ -1468,6 +1504,9 @@ def main():
         tt = torch.tensor([wall, ev_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall, ev_ms = float(tt[0]), float(tt[1])
+    if args.dump_outputs:
+        stage(rank, world, "dump of the last timed step's output")
+        dump_outputs(args.dump_outputs, torch, a, rank, world)      # `a`: what the last timed step wrote
     stage(rank, world, "global checksum (ncclAllReduce)")
     checksum = D.field_checksum(a)
     # N > 1: the SAME warm-up + timed steps once more from the same initial state in the conservative form (DLESM_DM_SAFE:

@@ -171,6 +171,13 @@ def golden_device_io():
         ops = [l.split() for l in lines if "operation" in l]
         res["runs"].append({"alignment": al, "rc": rc, "rows": rows,
                             "ops": ops, "passed": "Test passed" in so})
+    # pass / fail of the same program for every alignment tests/test_reference_programs_dropin.py runs it with: it
+    # passes up to 12 and overruns its fixed-size virtual device from 16 on (64: glibc aborts on the corrupted heap)
+    res["outcomes"] = []
+    for al in [None, 1, 2, 4, 8, 12, 16, 64]:
+        env = {"DL_ESM_ALIGNMENT": str(al)} if al else None
+        rc, so, se = run("ref_device_io.exe", env_extra=env)
+        res["outcomes"].append({"alignment": al, "rc": rc, "passed": rc == 0 and "Test passed" in so})
     return res
 
 

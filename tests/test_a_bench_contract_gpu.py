@@ -89,6 +89,45 @@ def test_reference_default_alignment():
     assert "error" not in sw["with_time_smooth"] and sw["with_time_smooth"]["copy_ceiling"]["best_gbs"] > 0, sw["with_time_smooth"]
 
 
+@pytest.mark.parametrize("tile", [256, 4096])
+def test_dump_outputs_is_the_last_timed_step(tmp_path, tile):
+    """--dump-outputs DIR: the field the last timed step wrote (whole at 256^2, edges + a seeded sample at 4096^2), the same
+    in two runs with the same arguments, equal bit for bit to warmup + steps oracle sweeps of the bench's hash-initialised
+    field; --steps is the number of timed steps and ms_per_step agrees with the headline rate"""
+    import numpy as np
+    import oracle_lib as O
+    steps, warmup = 5, 2
+    quick = ("--tile", str(tile), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-temporal-blocking",
+             "--no-shallow", "--no-configs", "--no-weak-tile", "--no-peer")
+    runs = []
+    for k in range(2):
+        d = _bench(*quick, "--dump-outputs", str(tmp_path / f"run{k}"))
+        assert d["steps"] == steps and d["ms_per_step"] > 0, d
+        assert abs(d["value"] * d["ms_per_step"] / (tile * tile / 1e3) - 1) < 0.02, (d["value"], d["ms_per_step"])
+        files = sorted(os.listdir(tmp_path / f"run{k}"))
+        runs.append({f: np.load(tmp_path / f"run{k}" / f) for f in files})
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0]), "dumps differ"
+    assert all(a.dtype in (np.float32, np.float64) for a in runs[0].values())
+    assert sum(a.nbytes for a in runs[0].values()) <= 64 << 20
+    # the bench's field: T points, NE offset, external BCs, DL_ESM_ALIGNMENT=64 -- internal 2..tile+1, whole 1..tile+2
+    ld, ny = O.grid_extents(tile + 2, tile + 2, 64)
+    assert ld == d["config"]["ld"]
+    x = O.hash_field(20261004, ny, ld, 0, 0, 1, tile + 2, 1, tile + 2)           # bench.py's SEED
+    y = x.copy()
+    for _ in range(warmup + steps):
+        O.jacobi5(x, y, ld, 2, tile + 1, 2, tile + 1)
+        x, y = y, x
+    want = x[1:tile + 1, 1:tile + 1]
+    got = runs[0]
+    if tile * tile <= 1 << 22:
+        assert set(got) == {"jacobi5_out.npy"} and np.array_equal(got["jacobi5_out.npy"], want)
+    else:
+        assert set(got) == {"jacobi5_out_edges.npy", "jacobi5_out_sample.npy"}, set(got)
+        assert np.array_equal(got["jacobi5_out_edges.npy"], np.concatenate([want[0], want[-1], want[:, 0], want[:, -1]]))
+        flat = np.random.default_rng(20261004).integers(0, tile * tile, size=1 << 22, dtype=np.int64)
+        assert np.array_equal(got["jacobi5_out_sample.npy"], want.reshape(-1)[flat])
+
+
 def test_rehearsal_of_the_multi_gpu_secondary_leg():
     d = _bench("--force-dm-leg", "--no-cpu-baseline")
     assert d["dm_form"] == "timeloop" and d["dm_selfcheck_steps"] == 50 and d["dm_step_equals_stencil_plus_exchange"] is True, d

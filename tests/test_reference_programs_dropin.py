@@ -1,53 +1,31 @@
 """Drop-in check of the Fortran API layer: the reference's OWN programs -- its example and its four test programs --
-are compiled UNMODIFIED, from where they lie under /root/reference, against this library's modules
-(dl_esm_inf_amd/fortran/build/*.mod + lib_fd_hip.a + libdlesm_hip.so) and run on one rank.  Nothing of them is copied
-into the repository and the executables go to a temporary directory.  What this pins is the API surface a GOcean
-application sees: module names, type components, generic interfaces, argument lists, the device-sync callback seam
-(tests/device_computation/test_device_io.f90 installs its own callbacks) and the one-rank behaviour of decomposition,
-halo exchange, global sum, scatter and gather.
+compiled UNMODIFIED against this library's modules (dl_esm_inf_amd/fortran/build/*.mod + lib_fd_hip.a +
+libdlesm_hip.so) by build() (oracle/Makefile target `dropin`, into oracle/_ref/dropin; nothing of them is copied into the
+repository) and run on one rank.  What this pins is the API surface a GOcean application sees: module names, type
+components, generic interfaces, argument lists, the device-sync callback seam (tests/device_computation/test_device_io.f90
+installs its own callbacks) and the one-rank behaviour of decomposition, halo exchange, global sum, scatter and gather.
 
 CPU only (-m "not gpu"): on one rank these programs keep their fields on the host -- no kernel of the hot path is
-invoked, so no GPU is needed; the multi-rank runs of the same programs are the reference's MPI job, which this
-container cannot launch against RCCL (no GPU here, one GPU on the box).  Skipped where /root/reference does not exist
-(the GPU box)."""
+invoked, so no GPU is needed; tests/test_a_reference_programs_multirank_gpu.py runs the same executables on 2-6 ranks.
+Skipped where build() found no reference sources to compile them from."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
 
-REF = "/root/reference/finite_difference"
-FDIR = os.path.join(ROOT, "dl_esm_inf_amd", "fortran")
-BUILD = os.path.join(FDIR, "build")
-LIBDIR = os.path.join(ROOT, "dl_esm_inf_amd", "lib")
+DROP = os.path.join(ROOT, "oracle", "_ref", "dropin")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("amdflang") is None,
-                                reason="needs /root/reference and amdflang (this container, not the GPU box)")
-
-PROGRAMS = {
-    "model": "example/model.f90",
-    "test_device_io": "tests/device_computation/test_device_io.f90",
-    "test_halos": "tests/dist_mem/test_halos.f90",
-    "test_gsum": "tests/dist_mem/test_gsum.f90",
-    "test_reduction": "tests/dist_mem/test_reduction.f90",
-}
+PROGRAMS = ("model", "test_device_io", "test_halos", "test_gsum", "test_reduction")
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    subprocess.check_call(["make", "-C", FDIR], stdout=subprocess.DEVNULL)
-    out = tmp_path_factory.mktemp("dropin")
-    exes = {}
-    for name, rel in PROGRAMS.items():
-        exe = str(out / f"{name}.exe")
-        cmd = ["amdflang", "-O1", f"-I{BUILD}", f"-J{out}", os.path.join(REF, rel), os.path.join(BUILD, "lib_fd_hip.a"),
-               f"-L{LIBDIR}", "-ldlesm_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", f"-Wl,-rpath,{LIBDIR}",
-               "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, f"{rel} does not build against this library's Fortran layer:\n{p.stderr[-3000:]}"
-        exes[name] = exe
+def built():
+    exes = {name: os.path.join(DROP, f"{name}.exe") for name in PROGRAMS}
+    missing = [e for e in exes.values() if not os.path.exists(e)]
+    if missing:
+        pytest.skip(f"{missing[0]} not built (build() makes it where the reference's sources are present)")
     return exes
 
 
@@ -72,20 +50,18 @@ def test_reference_example_model(built):
 @pytest.mark.parametrize("alignment", [None, 1, 2, 4, 8, 12, 16, 64])
 def test_reference_device_io_test(built, alignment):
     """tests/device_computation/test_device_io.f90: its own 'virtual device' behind the read/write callbacks of the
-    field type.  The program says it must pass for any DL_ESM_ALIGNMENT; with the REAL reference library
-    (oracle/_ref/ref_device_io.exe, the same source) it passes up to 12 and overruns its fixed-size virtual device from
-    16 on ('free(): corrupted ...').  Required here: pass up to 12, and the same outcome as the real reference beyond."""
+    field type.  The program says it must pass for any DL_ESM_ALIGNMENT; with the REAL reference library (the same
+    source, outcomes recorded in tests/golden/ref_device_io.json by oracle/make_golden.py) it passes up to 12 and overruns
+    its fixed-size virtual device from 16 on ('free(): corrupted ...').  Required here: pass up to 12, and the same
+    outcome as the real reference beyond."""
     env = {} if alignment is None else {"DL_ESM_ALIGNMENT": alignment}
     rc, out = _run(built["test_device_io"], **env)
     ok = rc == 0 and "Test passed" in out
     if alignment is None or alignment <= 12:
         assert ok, out[-2000:]
         return
-    real = os.path.join(ROOT, "oracle", "_ref", "ref_device_io.exe")
-    if not os.path.exists(real):
-        pytest.skip("oracle/_ref/ref_device_io.exe not built (make -C oracle ref)")
-    rrc, rout = _run(real, **env)
-    assert ok == (rrc == 0 and "Test passed" in rout), (out[-800:], rout[-800:])
+    real = next(o for o in load_golden("ref_device_io")["outcomes"] if o["alignment"] == alignment)
+    assert ok == real["passed"], (out[-800:], real)
 
 
 @pytest.mark.parametrize("nx,ny", [(10, 4), (4, 10), (10, 10)])
