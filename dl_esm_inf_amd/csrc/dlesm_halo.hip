@@ -1692,6 +1692,149 @@ extern "C" int dlesm_shallow_step_smooth_dm_pipelined(dlesm_halo_plan *p, const 
                                 (hipStream_t)stream, true, &alpha);
 }
 
+// Two shallow-water steps per launch on a decomposed grid (dlesm_shallow_step_x2_dm / _smooth_x2_dm).  The plan exchanges
+// depth-2 halos.  Stage 1 (level n+1) is evaluated on the box grown by one cell towards every neighbour -- the cells there are
+// the neighbour's interior cells, computed from the same operands with the same expression tree, so they are its bits -- and
+// stage 2 (level n+2) on the box; ONE depth-2 exchange of the newest level per two steps.  The plain form stores level n+1 on
+// the grown box too, which is all the next call's old level needs: no message for it.  The filtered form stores the FILTERED
+// level n+1, which needs level n+2 at the cell and so exists on the box only: it travels with level n+2 (six fields, one
+// aggregated exchange; in mailbox mode, whose mailboxes hold three fields, in two turns).
+// Default order: the whole box, then the exchange, on the caller's stream.  The overlapped form (sw_x2_dm_overlap = 1) is ordered
+// by events only (no device flag): the 2-deep frame strips along the sides that have a neighbour, event, the exchange on the side
+// stream, the interior on the caller's stream, the caller's stream waits for the exchange.
+static int shallow_x2_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_sw_params *q, const double *alpha, int ld, int ny,
+                              int xstart, int xstop, int ystart, int ystop, const double *const (&all)[12], hipStream_t s)
+{
+    DLESM_REQUIRE(p != nullptr && q != nullptr, "null pointer");
+    for (const double *f : all) DLESM_REQUIRE(f != nullptr, "null pointer");
+    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
+    if (int rc = ensure_device()) return rc;
+    if (int rc = x2_disjoint(who, all, ld, ny)) return rc;
+    const bool comms = !p->sends.empty() || !p->recvs.empty();
+    double *const *w = (double *const *)all;
+    if (!comms) {        // no neighbour: the single-domain entry, bit for bit
+        if (alpha)
+            return dlesm_shallow_step_smooth_x2_f64(q, *alpha, ld, ny, xstart, xstop, ystart, ystop, all[0], all[1], all[2], all[3], all[4],
+                                                    all[5], w[9], w[10], w[11], w[6], w[7], w[8], s);
+        return dlesm_shallow_step_x2_f64(q, ld, ny, xstart, xstop, ystart, ystop, all[0], all[1], all[2], all[3], all[4], all[5], w[6],
+                                         w[7], w[8], w[9], w[10], w[11], s);
+    }
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
+    const bool mailbox = p->peer_on && p->peer_fcap >= 3 && (g_mailbox || tuning("dm_peer", 1));
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
+    if (int rc = join_pending(p, s)) return rc;
+    int gw = 0, ge = 0, gs = 0, gn = 0;
+    for (const Msg &m : p->recvs) {      // as dlesm_jacobi5_multi_step_dm: a receive filed under Iminus comes from the west, ...
+        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
+        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
+        if (!xdir && !ydir) continue;
+        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 2, "%s: the plan exchanges depth-%d halos, two steps per launch need depth 2 "
+                      "(dlesm_map_comms_depth, depth = 2)", who, xdir ? m.nx : m.ny);
+        if (m.dir == DLESM_IMINUS) gw = 1;
+        if (m.dir == DLESM_IPLUS) ge = 1;
+        if (m.dir == DLESM_JMINUS) gs = 1;
+        if (m.dir == DLESM_JPLUS) gn = 1;
+    }
+    DLESM_REQUIRE(!g_mailbox || mailbox, "mailbox mode: %s exchanges three fields at a time, this plan's mailboxes have room for %d",
+                  who, p->peer_fcap);
+    if (xstop < xstart || ystop < ystart) return DLESM_OK;
+    if (int rc = check_box(who, ld, ny, xstart, xstop, ystart, ystop, 2)) return rc;
+    double *fields[6] = {w[9], w[10], w[11], w[6], w[7], w[8]};     // level n+2 [, the filtered level n+1]
+    const int nf = alpha ? 6 : 3;
+    auto exchange = [&](hipStream_t on) {
+        for (int k = 0; k < nf; k += mailbox ? 3 : nf)
+            if (int rc = exchange_on(p, fields + k, mailbox ? 3 : nf, DLESM_DIRS_ALL, on)) return rc;
+        return DLESM_OK;
+    };
+    if (!x2_grown_fits(ld, xstop, ge, all)) {
+        // arrays the wave tiles do not take: the definition, one single step over the grown box, one over the box
+        const int ex0 = xstart - gw, ex1 = xstop + ge, ey0 = ystart - gs, ey1 = ystop + gn;
+        if (!alpha) {
+            if (int rc = dlesm_shallow_step_f64(q, ld, ny, ex0, ex1, ey0, ey1, all[0], all[1], all[2], all[3], all[4], all[5], w[6], w[7],
+                                                w[8], s)) return rc;
+            if (int rc = dlesm_shallow_step_f64(q, ld, ny, xstart, xstop, ystart, ystop, w[6], w[7], w[8], all[0], all[1], all[2], w[9],
+                                                w[10], w[11], s)) return rc;
+            return exchange(s);
+        }
+        // filtered: old2 <- old, T <- u (the fixed ring of the unfiltered level n+1), step_smooth over the grown box (T = n+1,
+        // old2 = filtered n), step_smooth over the box (new2 = n+2, old2 = filtered n+1 on the box; its grown ring is exchanged)
+        const size_t bytes = (size_t)ld * ny * sizeof(double);
+        double *t[3] = {nullptr, nullptr, nullptr};
+        for (int k = 0; k < 3; k++)
+            if (hipMallocAsync((void **)&t[k], bytes, s) != hipSuccess) {
+                for (int k2 = 0; k2 < k; k2++) (void)hipFreeAsync(t[k2], s);
+                return fail(DLESM_EHIP, "%s: no scratch memory for the intermediate time level", who);
+            }
+        int rc = DLESM_OK;
+        for (int k = 0; k < 3 && !rc; k++)
+            if (hipMemcpyAsync(w[6 + k], all[3 + k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(t[k], all[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                rc = fail(DLESM_EHIP, "%s: copy failed", who);
+        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, ex0, ex1, ey0, ey1, all[0], all[1], all[2], w[6], w[7], w[8], t[0],
+                                                    t[1], t[2], s);
+        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], w[6], w[7], w[8],
+                                                    w[9], w[10], w[11], s);
+        for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
+        return rc ? rc : exchange(s);
+    }
+    auto box = [&](int xs, int xe, int ys, int ye) {
+        launch_x2_grown(*q, ld, ny, xs, xe, ys, ye, xstart, xstop, ystart, ystop, gw, ge, gs, gn, all, alpha, s);
+        DLESM_HIP_TRY(hipGetLastError());
+        return DLESM_OK;
+    };
+    const int ix0 = xstart + 2 * gw, ix1 = xstop - 2 * ge, iy0 = ystart + 2 * gs, iy1 = ystop - 2 * gn;
+    // Whole box, then the exchange, by default: the four thin 2-row frame launches cost more than the exchange they hide.
+    // Measured in loop-back (scripts/sw_x2_dm_timing.py, profiles/r05_sw_x2_dm_loopback.json), ms per time step, medians of 7
+    // interleaved windows, serial / frame-overlapped: plain 8192^2 0.637 / 0.669 (RCCL), 0.620 / 0.659 (mailboxes); 4096^2
+    // 0.175 / 0.182, 0.162 / 0.191; filtered 8192^2 0.654 / 0.683, 0.669 / 0.691.  sw_x2_dm_overlap = 1 (HOOK): the overlapped form.
+    const bool serial = !tuning("sw_x2_dm_overlap", 0);
+    if (serial || ix1 < ix0 || iy1 < iy0) {      // ... or the tile is all frame: no interior to hide the exchange behind
+        if (int rc = box(xstart, xstop, ystart, ystop)) return rc;
+        return exchange(s);
+    }
+    hipStream_t side = side_stream();
+    // 1. frame: the 2-deep strips of the new level(s) along the sides that have a neighbour
+    if (gs)
+        if (int rc = box(xstart, xstop, ystart, iy0 - 1)) return rc;
+    if (gn)
+        if (int rc = box(xstart, xstop, iy1 + 1, ystop)) return rc;
+    if (gw)
+        if (int rc = box(xstart, ix0 - 1, iy0, iy1)) return rc;
+    if (ge)
+        if (int rc = box(ix1 + 1, xstop, iy0, iy1)) return rc;
+    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
+    // 2. exchange of the frame on the side stream ...
+    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
+    if (int rc = exchange(side)) return rc;
+    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
+    // 3. ... behind the interior
+    if (int rc = box(ix0, ix1, iy0, iy1)) return rc;
+    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
+    return DLESM_OK;
+}
+
+extern "C" int dlesm_shallow_step_x2_dm(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
+                                        int ystop, const double *u, const double *v, const double *pf, const double *uold,
+                                        const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
+                                        double *unew2, double *vnew2, double *pnew2, void *stream)
+{
+    clear_error();
+    const double *all[12] = {u, v, pf, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2};
+    return shallow_x2_dm_impl("dlesm_shallow_step_x2_dm", p, q, nullptr, ld, ny, xstart, xstop, ystart, ystop, all, (hipStream_t)stream);
+}
+
+extern "C" int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *p, const dlesm_sw_params *q, double alpha, int ld, int ny, int xstart,
+                                               int xstop, int ystart, int ystop, const double *u, const double *v, const double *pf,
+                                               const double *uold, const double *vold, const double *pold, double *unew2,
+                                               double *vnew2, double *pnew2, double *uold2, double *vold2, double *pold2, void *stream)
+{
+    clear_error();
+    const double *all[12] = {u, v, pf, uold, vold, pold, uold2, vold2, pold2, unew2, vnew2, pnew2};
+    return shallow_x2_dm_impl("dlesm_shallow_step_smooth_x2_dm", p, q, &alpha, ld, ny, xstart, xstop, ystart, ystop, all,
+                              (hipStream_t)stream);
+}
+
 extern "C" int dlesm_global_sum_f64(double *value)
 {
     DLESM_REQUIRE(value != nullptr, "null pointer");

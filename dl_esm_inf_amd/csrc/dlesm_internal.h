@@ -273,6 +273,12 @@ void choose_block_shape(int *nxw_io, int *tpb_out, int prefer = 0);
 // the same for a sweep with the Jacobi tile geometry over the 0-based box: the planned Jacobi shape of that (ld, box) if there is one
 void shape_for_tile_sweep(int ld, int x0, int x1, int y0, int y1, int *nxw_io, int *tpb_out);
 int check_box(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, int ring);
+// two shallow-water steps per launch (dlesm_shallow_x2.hip): the overlap check of the twelve arrays, and the distributed form's
+// wave-tile conditions and launch (stage 1 computed on the box grown by gw..gn; see shallow_tile_x2_grown)
+int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny);
+bool x2_grown_fits(int ld, int xstop, int ge, const double *const (&all)[12]);
+void launch_x2_grown(const dlesm_sw_params &q, int ld, int ny, int xs, int xe, int ys, int ye, int bx0, int bx1, int by0, int by1, int gw,
+                     int ge, int gs, int gn, const double *const (&all)[12], const double *alpha, hipStream_t s);
 // the shallow-water frame as the first workgroups of the interior launch (shallow_tile_framed)
 struct SwFrameJob {
     FramePack3 pk;

@@ -169,9 +169,20 @@ struct X2Arrays {
 // HL: lanes per side that only feed their neighbours.  One is all two steps need; with four the 112 output columns of a tile are
 // seven whole 128-byte lines of the six arrays written (dlesm_shallow.hip) -- that pays for the four-row plain form (1.253 ->
 // 1.208 ms at 8192^2) and costs the two-row forms 3-4 % (twice the tiles, twice the extra lanes loaded), which keep one.
-template <int R, int NTM, bool SM = false, int WPE = 1, int HL = 1>
+// GROW (the distributed entries dlesm_shallow_step_x2_dm / _smooth_x2_dm; launch_x2_grown): the box (x0..x1, y0..y1) is a
+// piece of a sub-domain whose level n carries depth-2 halos; level n+1 is COMPUTED (not loaded) wherever it lies in g.e* -- the
+// sub-domain's box grown by one cell towards every neighbour, where level n+1 is a neighbour's interior cell -- with the operands
+// and expression tree that neighbour uses, so the bits are its bits.  The plain form also STORES it on g.w* (the launch box grown
+// into that ring where it touches it): the next call's old level needs no message.  Tiles whose stage-1 rows and columns lie
+// wholly inside g.e* merge nothing, as interior tiles of a single-domain launch.
+struct X2Grow {
+    int ex0, ex1, ey0, ey1;       // where level n+1 is computed (0-based, inclusive); the ring outside it is loaded as without GROW
+    int wx0, wx1, wy0, wy1;       // where the plain form stores level n+1
+};
+
+template <int R, int NTM, bool SM = false, int WPE = 1, int HL = 1, bool GROW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void shallow_tile_x2(dlesm_sw_params q, int ld, int ny, int x0, int x1, int y0, int y1, int cb, int nxw,
-                                                       int stack, X2Arrays a, double alpha)
+                                                       int stack, X2Arrays a, double alpha, X2Grow g)
 {
     constexpr int X2_HALO_LANES = HL, X2_OUT_LANES = 64 - 2 * HL;
     const int lane = threadIdx.x & 63;
@@ -219,7 +230,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     // cells of level n+1 outside the box are the fixed ring the level-n+1 arrays hold: only tiles on the edge of the box
     // (wave-uniform test) load them
     const int c0 = c - lane;                            // lane 0's chunk
-    const bool rim = jb - 1 < y0 || jb + R > y1 || 2 * c0 < x0 || 2 * c0 + 127 > x1;
+    // (GROW: the region where level n+1 is computed is g.e*, not the launch box)
+    const int kx0 = GROW ? g.ex0 : x0, kx1 = GROW ? g.ex1 : x1, ky0 = GROW ? g.ey0 : y0, ky1 = GROW ? g.ey1 : y1;
+    const bool rim = jb - 1 < ky0 || jb + R > ky1 || 2 * c0 < kx0 || 2 * c0 + 127 > kx1;
     if (rim) {
 #pragma unroll
         for (int k = 0; k < R + 2; k++) {
@@ -228,8 +241,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             W2 ru, rv, rp;
             if constexpr (SM) { ru = U[k + 1]; rv = V[k + 1]; rp = P[k + 1]; (void)o; }      // (level n's ring, already in registers)
             else { ru = xld<false>(a.u1 + o); rv = xld<false>(a.v1 + o); rp = xld<false>(a.p1 + o); }
-            const bool rin = jj >= y0 && jj <= y1;
-            const bool i0 = rin && 2 * c >= x0 && 2 * c <= x1, i1 = rin && 2 * c + 1 >= x0 && 2 * c + 1 <= x1;
+            const bool rin = jj >= ky0 && jj <= ky1;
+            const bool i0 = rin && 2 * c >= kx0 && 2 * c <= kx1, i1 = rin && 2 * c + 1 >= kx0 && 2 * c + 1 <= kx1;
             U1[k] = XW(i0 ? U1[k].x : ru.x, i1 ? U1[k].y : ru.y);
             V1[k] = XW(i0 ? V1[k].x : rv.x, i1 ? V1[k].y : rv.y);
             P1[k] = XW(i0 ? P1[k].x : rp.x, i1 ? P1[k].y : rp.y);
@@ -256,6 +269,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             U1[k + 1] = fu; V1[k + 1] = fv; P1[k + 1] = fp;
         }
     }
+    if constexpr (GROW && !SM) {
+        // level n+2 on the launch box; level n+1 on g.w*, which reaches one cell beyond the launch box where that is the grown ring:
+        // row jb-1 of the first strip, row je+1 of the last, and the column left of the first tile / right of the last one,
+        // which lies in a halo lane (stage 1 is valid there: columns 1 .. 126 of the wave) when no tile has it as an output lane
+        const bool own = c >= 0 && c <= c_ld &&
+                         (out_lane || (lane < X2_HALO_LANES && c < cb) || (lane >= 64 - X2_HALO_LANES && c > x1 / 2));
+        const bool w0 = own && 2 * c >= g.wx0 && 2 * c <= g.wx1, w1 = own && 2 * c + 1 >= g.wx0 && 2 * c + 1 <= g.wx1;
+#pragma unroll
+        for (int k = 0; k < R + 2; k++) {
+            const int jj = jb - 1 + k;
+            if (jj < g.wy0 || jj > g.wy1 || (jj < jb && jj >= y0) || (jj > je && jj <= y1)) continue;    // (wave-uniform)
+            const size_t o = (size_t)jj * ld + (size_t)c * 2;
+            if (w0 && w1) {
+                xst<(NTM & 2) != 0>(a.u1 + o, U1[k]);
+                xst<(NTM & 2) != 0>(a.v1 + o, V1[k]);
+                xst<(NTM & 2) != 0>(a.p1 + o, P1[k]);
+            } else {
+                if (w0) { a.u1[o] = U1[k].x; a.v1[o] = V1[k].x; a.p1[o] = P1[k].x; }
+                if (w1) { a.u1[o + 1] = U1[k].y; a.v1[o + 1] = V1[k].y; a.p1[o + 1] = P1[k].y; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const int jj = jb + k;
+            if (jj > je) break;
+            const size_t o = (size_t)jj * ld + (size_t)c * 2;
+            if (m0 && m1) {
+                xst<(NTM & 2) != 0>(a.u2 + o, U2[k]);
+                xst<(NTM & 2) != 0>(a.v2 + o, V2[k]);
+                xst<(NTM & 2) != 0>(a.p2 + o, P2[k]);
+            } else {
+                if (m0) { a.u2[o] = U2[k].x; a.v2[o] = V2[k].x; a.p2[o] = P2[k].x; }
+                if (m1) { a.u2[o + 1] = U2[k].y; a.v2[o + 1] = V2[k].y; a.p2[o + 1] = P2[k].y; }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < R; k++) {
         const int jj = jb + k;
@@ -275,6 +325,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         }
     }
 }
+
 
 // The SW-offset, DOUBLY PERIODIC model (the GOcean `shallow` benchmark's configuration), two steps per launch.  Nothing is a
 // fixed ring here: level n+1 one cell outside the box is the periodic image of level n+1 inside, i.e. the first stage's
@@ -385,9 +436,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 
 namespace dlesm {
 namespace {
-// the wave-tile launch of both entries below; alpha != nullptr: the filtered form
+// the wave-tile launch of both entries below; alpha != nullptr: the filtered form; grow != nullptr: the GROW kernels (the
+// distributed entries, product shapes only)
 static void launch_x2(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop, X2Arrays a, const double *alpha,
-                      hipStream_t s)
+                      hipStream_t s, const X2Grow *grow = nullptr)
 {
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
     const int cb = (x0 / 2) & ~7;                        // tiles anchored on a 128-byte line of the row, as shallow_tile
@@ -403,7 +455,7 @@ static void launch_x2(const dlesm_sw_params &q, int ld, int ny, int xstart, int 
     // written ((R+4)/R: 2.33 against 3).  Four-row tiles do not fit: capped 164-336 B of scratch, uncapped one wave per SIMD,
     // also with the rows of level n-1 the filter needs loaded a second time instead of kept live.
     int R = alpha ? 3 : 4, nt = 2, stack = 4, pad = 0;
-    if (kLab) {
+    if (kLab && !grow) {
         const int rows = tuning("sw_x2_rows", 0);        // (0: the product's height for the form)
         if (rows == 2 || rows == 4 || rows == 6 || (rows == 3 && alpha)) R = rows;
         nt = tuning("sw_x2_nt", R == 2 && alpha ? 6 : nt) & 7;
@@ -427,11 +479,18 @@ static void launch_x2(const dlesm_sw_params &q, int ld, int ny, int xstart, int 
     const int strips = (y1 - y0 + R) / R;
     const unsigned grid = stack ? (unsigned)((long)nxw * ((strips + tpb - 1) / tpb)) : (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
     const double al = alpha ? *alpha : 0.0;
+    if (grow) {
+        const dim3 gd(grid), bd(64 * tpb);
+        if (alpha) hipLaunchKernelGGL((shallow_tile_x2<3, 2, true, 2, 1, true>), gd, bd, 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, *grow);
+        else if (out_lanes == 56) hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 4, true>), gd, bd, 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, *grow);
+        else hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 1, true>), gd, bd, 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, *grow);
+        return;
+    }
 #define DLESM_X2(RR, NN)                                                                                                                                  \
     do {                                                                                                                                                  \
-        if (alpha) hipLaunchKernelGGL((shallow_tile_x2<RR, NN, true>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al); \
-        else if (RR == 4 && lines) hipLaunchKernelGGL((shallow_tile_x2<RR, NN, false, 1, (RR == 4 ? 4 : 1)>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al); \
-        else hipLaunchKernelGGL((shallow_tile_x2<RR, NN, false, 1, 1>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al); \
+        if (alpha) hipLaunchKernelGGL((shallow_tile_x2<RR, NN, true>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{}); \
+        else if (RR == 4 && lines) hipLaunchKernelGGL((shallow_tile_x2<RR, NN, false, 1, (RR == 4 ? 4 : 1)>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{}); \
+        else hipLaunchKernelGGL((shallow_tile_x2<RR, NN, false, 1, 1>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{}); \
     } while (0)
 #ifdef DLESM_LAB
 #define DLESM_X2R(RR)                                                                                                  \
@@ -439,14 +498,14 @@ static void launch_x2(const dlesm_sw_params &q, int ld, int ny, int xstart, int 
     case 0: DLESM_X2(RR, 0); break; case 3: DLESM_X2(RR, 3); break; case 4: DLESM_X2(RR, 4); break;                   \
     case 6: DLESM_X2(RR, 6); break; case 7: DLESM_X2(RR, 7); break; default: DLESM_X2(RR, 2); break;                  \
     }
-    if (R == 3) hipLaunchKernelGGL((shallow_tile_x2<3, 2, true, 2>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al);
+    if (R == 3) hipLaunchKernelGGL((shallow_tile_x2<3, 2, true, 2>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{});
     else if (R == 2) { DLESM_X2R(2) } else if (R == 6) { DLESM_X2R(6) } else { DLESM_X2R(4) }
 #undef DLESM_X2R
 #else
     (void)nt;
-    if (alpha) hipLaunchKernelGGL((shallow_tile_x2<3, 2, true, 2>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al);
-    else if (lines) hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 4>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al);
-    else hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 1>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al);
+    if (alpha) hipLaunchKernelGGL((shallow_tile_x2<3, 2, true, 2>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{});
+    else if (lines) hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 4>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{});
+    else hipLaunchKernelGGL((shallow_tile_x2<4, 2, false, 1, 1>), dim3(grid), dim3(64 * tpb), 0, s, q, ld, ny, x0, x1, y0, y1, cb, nxw, stack, a, al, X2Grow{});
 #endif
 #undef DLESM_X2
 }
@@ -481,11 +540,11 @@ static void launch_sw_x2(const dlesm_sw_params &q, int ld, int ny, int xstart, i
 } // namespace
 } // namespace dlesm
 
-using namespace dlesm;
+namespace dlesm {
 
 // the twelve arrays of a two-step call are ld x ny doubles each and must not overlap (a shifted alias would be read and written
 // by different tiles of one launch)
-static int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny)
+int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny)
 {
     const uintptr_t bytes = (uintptr_t)ld * (uintptr_t)ny * sizeof(double);
     for (int i = 0; i < 12; i++)
@@ -495,6 +554,37 @@ static int x2_disjoint(const char *who, const double *const (&all)[12], int ld, 
         }
     return DLESM_OK;
 }
+
+// The wave-tile conditions of the GROW kernels: 16-byte aligned bases, and an even leading dimension or a grown box
+// whose last computed column (xstop + ge) and its east operand lie in whole 2-column chunks.
+bool x2_grown_fits(int ld, int xstop, int ge, const double *const (&all)[12])
+{
+    bool ok = ld % 2 == 0 || (xstop - 1 + ge) + 1 <= 2 * (ld / 2) - 1;
+    for (const double *f : all) ok = ok && ((uintptr_t)f % 16 == 0);
+    return ok && tuning("sw_kernel", 0) == 0 && tuning("sw_x2_fused", 1) != 0;
+}
+
+// One launch of shallow_tile_x2<..., GROW> over the piece (xs..xe, ys..ye) of the sub-domain box (bx0..bx1, by0..by1), all 1-based;
+// gw..gn: the box's sides that have a neighbour.  all[]: u, v, p, uold, vold, pold, level n+1 (plain) or the filtered level n+1
+// (alpha != nullptr), level n+2.
+void launch_x2_grown(const dlesm_sw_params &q, int ld, int ny, int xs, int xe, int ys, int ye, int bx0, int bx1, int by0, int by1, int gw,
+                     int ge, int gs, int gn, const double *const (&all)[12], const double *alpha, hipStream_t s)
+{
+    X2Grow g{bx0 - 1 - gw, bx1 - 1 + ge, by0 - 1 - gs, by1 - 1 + gn, xs - 1, xe - 1, ys - 1, ye - 1};
+    if (!alpha) {         // level n+1 goes into the grown ring where the piece touches it
+        if (xs == bx0) g.wx0 -= gw;
+        if (xe == bx1) g.wx1 += ge;
+        if (ys == by0) g.wy0 -= gs;
+        if (ye == by1) g.wy1 += gn;
+    }
+    double *const *w = (double *const *)all;
+    launch_x2(q, ld, ny, xs, xe, ys, ye, X2Arrays{all[0], all[1], all[2], all[3], all[4], all[5], w[6], w[7], w[8], w[9], w[10], w[11]},
+              alpha, s, &g);
+}
+
+} // namespace dlesm
+
+using namespace dlesm;
 
 // Two leapfrog steps, one launch (NE offset, fixed boundary ring): level n+1 into (unew, vnew, pnew), level n+2 into
 // (unew2, vnew2, pnew2) -- bit for bit what

@@ -571,6 +571,25 @@ module dlesm_hip_mod
        type(c_ptr), value :: u, v, p, uold, vold, pold, unew, vnew, pnew, stream
        integer(c_int) :: rc
      end function
+     function dlesm_shallow_step_x2_dm(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, &
+          unew, vnew, pnew, unew2, vnew2, pnew2, stream) bind(C, name="dlesm_shallow_step_x2_dm") result(rc)
+       import :: c_int, c_ptr, c_sw_params
+       type(c_ptr), value :: plan
+       type(c_sw_params), intent(in) :: params
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_shallow_step_smooth_x2_dm(plan, params, alpha, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, &
+          pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream) bind(C, name="dlesm_shallow_step_smooth_x2_dm") result(rc)
+       import :: c_int, c_ptr, c_sw_params, c_double
+       type(c_ptr), value :: plan
+       type(c_sw_params), intent(in) :: params
+       real(c_double), value :: alpha
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream
+       integer(c_int) :: rc
+     end function
      function dlesm_shallow_step_dm_pipelined(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, &
           uold, vold, pold, unew, vnew, pnew, stream) bind(C, name="dlesm_shallow_step_dm_pipelined") result(rc)
        import :: c_int, c_ptr, c_sw_params

@@ -343,6 +343,9 @@ module parallel_comms_mod
   type(c_comm_tables), save :: ctables
   logical, save :: have_tables = .false.
   type(c_ptr), save :: plan = c_null_ptr, scratch = c_null_ptr
+  ! a run without distributed memory: a plan from tables without messages (serial_plan_for)
+  type(c_ptr), save :: serial_plan = c_null_ptr
+  integer, save :: serial_ld = 0, serial_ny = 0
   integer, save :: plan_ld = 0, plan_ny = 0
 
   public :: map_comms, iprocmap, exchmod_alloc, exchange_generic, global_sum
@@ -354,7 +357,7 @@ module parallel_comms_mod
             IminusJplus, MaxCommDir
   public :: opp_dirn
   ! additions of this implementation
-  public :: halo_plan_for, exchange_device, to_c_decomp
+  public :: halo_plan_for, serial_plan_for, exchange_device, to_c_decomp
 
 contains
 
@@ -460,6 +463,9 @@ contains
     if (c_associated(scratch)) rc = dlesm_field_destroy(scratch)
     plan = c_null_ptr;  scratch = c_null_ptr
     plan_ld = 0;  plan_ny = 0
+    if (c_associated(serial_plan)) rc = dlesm_halo_plan_destroy(serial_plan)
+    serial_plan = c_null_ptr
+    serial_ld = 0;  serial_ny = 0
   end subroutine drop_plans
 
   !> Device message plan for fields of extent (ld, ny): built once, shared by every field of
@@ -477,6 +483,30 @@ contains
     end if
     p = plan
   end function halo_plan_for
+
+  !> The plan of a run without distributed memory: tables without messages (the reference's serial tables,
+  !! parallel_comms_mod.f90:216), so that a distributed entry taking it runs its single-domain form in the library.
+  function serial_plan_for(ld, ny) result(p)
+    integer, intent(in) :: ld, ny
+    type(c_ptr) :: p
+    type(c_comm_tables) :: empty
+    integer(c_int) :: rc
+    if (c_associated(serial_plan) .and. (ld /= serial_ld .or. ny /= serial_ny)) then
+       rc = dlesm_halo_plan_destroy(serial_plan)
+       serial_plan = c_null_ptr
+    end if
+    if (.not. c_associated(serial_plan)) then
+       empty%nsend = 0;  empty%nrecv = 0
+       empty%dirsend = 0;  empty%destination = 0;  empty%isrcsend = 0;  empty%jsrcsend = 0
+       empty%idessend = 0;  empty%jdessend = 0;  empty%nxsend = 0;  empty%nysend = 0
+       empty%dirrecv = 0;  empty%source = 0;  empty%isrcrecv = 0;  empty%jsrcrecv = 0
+       empty%idesrecv = 0;  empty%jdesrecv = 0;  empty%nxrecv = 0;  empty%nyrecv = 0
+       rc = dlesm_halo_plan_create(empty, int(ld, c_int), int(ny, c_int), serial_plan)
+       if (rc /= 0) call parallel_abort('halo plan: ' // dlesm_error_text())
+       serial_ld = ld;  serial_ny = ny
+    end if
+    p = serial_plan
+  end function serial_plan_for
 
   integer(c_int) function dir_mask(comm1, comm2, comm3, comm4) result(mask)
     integer, intent(in) :: comm1, comm2, comm3, comm4

@@ -58,6 +58,7 @@ module dlesm_psy_mod
   public :: invoke_shallow_step_sw_periodic, plan_shallow_step_sw, invoke_periodic_halos_multi
   public :: invoke_shallow_step_smooth, invoke_shallow_step_sw_smooth_periodic, invoke_shallow_step_smooth_dm
   public :: invoke_shallow_step_x2, invoke_shallow_step_smooth_x2
+  public :: invoke_shallow_step_x2_dm, invoke_shallow_step_smooth_x2_dm
   public :: invoke_shallow_step_sw_x2_periodic, invoke_shallow_step_sw_smooth_x2_periodic
 
 contains
@@ -507,10 +508,11 @@ contains
   !> The distributed form of invoke_shallow_step_smooth (one launch + the exchange of the new level hidden behind the interior):
   !! `pipelined` = the time-loop form (halo_join(grid) after the loop); serial builds fall back to invoke_shallow_step_smooth.
   subroutine invoke_shallow_step_smooth_dm(prm, alpha, u, v, p, uold, vold, pold, unew, vnew, pnew, pipelined)
-    use parallel_comms_mod, only: halo_plan_for
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
     use parallel_utils_mod, only: DIST_MEM_ENABLED
     type(c_sw_params), intent(in) :: prm
     real(go_wp), intent(in) :: alpha
+    type(c_ptr) :: plan
     type(r2d_field), intent(inout), target :: u, v, p, uold, vold, pold, unew, vnew, pnew
     logical, intent(in), optional :: pipelined
     logical :: pipe
@@ -776,6 +778,72 @@ contains
                                c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_shallow_step_dm: ' // dlesm_error_text())
   end subroutine invoke_shallow_step_dm
+
+  !> TWO leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_x2_dm): the grid must have been
+  !! decomposed with halo_width = 2 (without distributed memory the plan has no messages: the library runs the single-domain entry).  u, v, p need valid depth-2 halos, uold, vold, pold depth-1 halos; unew2, vnew2, pnew2 leave
+  !! with valid depth-2 halos, unew, vnew, pnew valid on the internal region grown by one cell towards every neighbour.
+  !! Time loop: (cur, old, new1, new2) <- (new2, new1, old, cur) after every call.
+  subroutine invoke_shallow_step_x2_dm(prm, u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    type(c_sw_params), intent(in) :: prm
+    type(r2d_field), intent(inout), target :: u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2
+    type(c_ptr) :: plan
+    integer(c_int) :: rc
+    if (p%grid%subdomain%internal%xstart - 1 /= 2 .or. p%grid%subdomain%internal%ystart - 1 /= 2) &
+         call gocean_stop('invoke_shallow_step_x2_dm: the grid must be decomposed with halo_width = 2')
+    call need_device(u);  call need_device(v);  call need_device(p)
+    call need_device(uold);  call need_device(vold);  call need_device(pold)
+    call need_device(unew);  call need_device(vnew);  call need_device(pnew)
+    call need_device(unew2);  call need_device(vnew2);  call need_device(pnew2)
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(p%grid%nx, p%grid%ny)
+    else
+       plan = serial_plan_for(p%grid%nx, p%grid%ny)
+    end if
+    rc = dlesm_shallow_step_x2_dm(plan, prm, int(p%grid%nx, c_int), int(p%grid%ny, c_int), &
+                                  int(p%internal%xstart, c_int), int(p%internal%xstop, c_int), &
+                                  int(p%internal%ystart, c_int), int(p%internal%ystop, c_int), &
+                                  field_device_data(u), field_device_data(v), field_device_data(p), &
+                                  field_device_data(uold), field_device_data(vold), field_device_data(pold), &
+                                  field_device_data(unew), field_device_data(vnew), field_device_data(pnew), &
+                                  field_device_data(unew2), field_device_data(vnew2), field_device_data(pnew2), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_shallow_step_x2_dm: ' // dlesm_error_text())
+  end subroutine invoke_shallow_step_x2_dm
+
+  !> TWO filtered leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_smooth_x2_dm; halo_width = 2):
+  !! level n+2 into unew2, vnew2, pnew2 and the filtered level n+1 into uold2, vold2, pold2, both with valid depth-2 halos;
+  !! u .. pold are not modified (the filtered old level needs valid depth-1 halos).
+  !! Time loop: ping-pong (u, v, p, uold, vold, pold) <-> (unew2, vnew2, pnew2, uold2, vold2, pold2).
+  subroutine invoke_shallow_step_smooth_x2_dm(prm, alpha, u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    type(c_sw_params), intent(in) :: prm
+    real(go_wp), intent(in) :: alpha
+    type(r2d_field), intent(inout), target :: u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2
+    type(c_ptr) :: plan
+    integer(c_int) :: rc
+    if (p%grid%subdomain%internal%xstart - 1 /= 2 .or. p%grid%subdomain%internal%ystart - 1 /= 2) &
+         call gocean_stop('invoke_shallow_step_smooth_x2_dm: the grid must be decomposed with halo_width = 2')
+    call need_device(u);  call need_device(v);  call need_device(p)
+    call need_device(uold);  call need_device(vold);  call need_device(pold)
+    call need_device(unew2);  call need_device(vnew2);  call need_device(pnew2)
+    call need_device(uold2);  call need_device(vold2);  call need_device(pold2)
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(p%grid%nx, p%grid%ny)
+    else
+       plan = serial_plan_for(p%grid%nx, p%grid%ny)
+    end if
+    rc = dlesm_shallow_step_smooth_x2_dm(plan, prm, alpha, &
+                                         int(p%grid%nx, c_int), int(p%grid%ny, c_int), &
+                                         int(p%internal%xstart, c_int), int(p%internal%xstop, c_int), &
+                                         int(p%internal%ystart, c_int), int(p%internal%ystop, c_int), &
+                                         field_device_data(u), field_device_data(v), field_device_data(p), &
+                                         field_device_data(uold), field_device_data(vold), field_device_data(pold), &
+                                         field_device_data(unew2), field_device_data(vnew2), field_device_data(pnew2), &
+                                         field_device_data(uold2), field_device_data(vold2), field_device_data(pold2), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_shallow_step_smooth_x2_dm: ' // dlesm_error_text())
+  end subroutine invoke_shallow_step_smooth_x2_dm
 
   !> The same step for a time loop: returns with the exchange of the new fields in flight; the next
   !! invoke_shallow_step_dm_pipelined on this grid waits for it on the device; halo_join(grid) after the loop.

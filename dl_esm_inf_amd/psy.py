@@ -392,6 +392,38 @@ def invoke_shallow_step_smooth_dm(params, alpha, u, v, p, uold, vold, pold, unew
              vnew.device_ptr, pnew.device_ptr, _stream_ptr(stream)))
 
 
+def _x2_dm_plan(g, who):
+    """the plan of a grid decomposed with halo_width = 2 (the two-step distributed entries need depth-2 halos)"""
+    if getattr(g, "halo_width", 1) != 2:
+        raise _cabi.DlesmError(_cabi.EINVAL, f"{who}: the grid has halo_width {getattr(g, 'halo_width', 1)}; two steps per "
+                                             "call need a grid decomposed with halo_width = 2")
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, f"{who}: the grid has no message tables (grid_init after decompose)")
+    return grid_mod.halo_plan(g)
+
+
+def invoke_shallow_step_x2_dm(params, u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2, stream=None):
+    """TWO leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_x2_dm; halo_width = 2): level n+2
+    into unew2.. with valid depth-2 halos, level n+1 into unew.. on the box grown by one cell towards every neighbour, which is
+    all the next call reads of it.  Time loop: (cur, old, new1, new2) <- (new2, new1, old, cur) after every call."""
+    g, it = p.grid, p.internal
+    plan = _x2_dm_plan(g, "invoke_shallow_step_x2_dm")
+    check(_cabi.lib().dlesm_shallow_step_x2_dm(plan, C.byref(params), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
+                                               *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2)],
+                                               _stream_ptr(stream)))
+
+
+def invoke_shallow_step_smooth_x2_dm(params, alpha, u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream=None):
+    """TWO filtered leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_smooth_x2_dm; halo_width = 2):
+    level n+2 into unew2.., the filtered level n+1 into uold2.., both with valid depth-2 halos; inputs untouched.  The filtered
+    old level must carry valid depth-1 halos.  Time loop: ping-pong (cur, old) <-> (unew2.., uold2..)."""
+    g, it = p.grid, p.internal
+    plan = _x2_dm_plan(g, "invoke_shallow_step_smooth_x2_dm")
+    check(_cabi.lib().dlesm_shallow_step_smooth_x2_dm(
+        plan, C.byref(params), float(alpha), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
+        *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2)], _stream_ptr(stream)))
+
+
 def halo_exchange_multi(fields, stream=None, dirs=_cabi.DIRS_ALL):
     """halo_exchange(1) of several fields of one grid in a single grouped RCCL launch"""
     g = fields[0].grid

@@ -337,7 +337,8 @@ int dlesm_shallow_step_sw_periodic_f64(const dlesm_sw_params *params, int ld, in
  * leave behind -- six arrays read and six written per TWO steps, 48 B/cell/step instead of 72.  As for those two calls the ring of
  * unew, vnew, pnew outside the box (which no step writes) must hold the boundary values before the call.  Twelve distinct
  * arrays (level n+2 cannot overwrite level n-1 in place: the first stage reads it one cell around each tile).  The PSy-layer
- * loop nests it replaces: two passes of the un-fused GOcean kernel sequence (infrastructure_mod.f90:13-41 for the form). */
+ * loop nests it replaces: two passes of the un-fused GOcean kernel sequence (infrastructure_mod.f90:13-41 for the form).
+ * Single domain only: on a decomposed grid use dlesm_shallow_step_x2_dm. */
 int dlesm_shallow_step_x2_f64(const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
                               const double *u, const double *v, const double *p, const double *uold, const double *vold,
                               const double *pold, double *unew, double *vnew, double *pnew, double *unew2, double *vnew2,
@@ -347,7 +348,8 @@ int dlesm_shallow_step_x2_f64(const dlesm_sw_params *q, int ld, int ny, int xsta
  * unew2 / vnew2 / pnew2 and the FILTERED level n+1 in uold2 / vold2 / pold2 -- the new current and old levels two calls of
  * dlesm_shallow_step_smooth_f64 with the usual rotation leave, bit for bit, provided the boundary ring is the same at every time
  * level (the ring of the unfiltered level n+1, which no array holds, is taken from u, v, p).  48 B/cell/step against 96 for the
- * one-launch filtered step.  Time loop: ping-pong (u.., uold..) <-> (unew2.., uold2..). */
+ * one-launch filtered step.  Time loop: ping-pong (u.., uold..) <-> (unew2.., uold2..).
+ * Single domain only: on a decomposed grid use dlesm_shallow_step_smooth_x2_dm. */
 int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double alpha, int ld, int ny, int xstart, int xstop, int ystart,
                                      int ystop, const double *u, const double *v, const double *p, const double *uold,
                                      const double *vold, const double *pold, double *unew2, double *vnew2, double *pnew2,
@@ -740,6 +742,33 @@ int dlesm_shallow_step_smooth_dm_pipelined(dlesm_halo_plan *plan, const dlesm_sw
                                            const double *u, const double *v, const double *p,
                                            double *uold, double *vold, double *pold,
                                            double *unew, double *vnew, double *pnew, void *stream);
+
+/* The distributed forms of dlesm_shallow_step_x2_f64 / dlesm_shallow_step_smooth_x2_f64: two leapfrog steps per launch and ONE
+ * depth-2 exchange per two steps.  `plan` must come from dlesm_map_comms_depth(depth = 2) tables (a grid decomposed with
+ * halo_width = 2); a plan of another depth is refused, a plan without messages is the single-domain entry, bit for bit.
+ * Plain form.  In: u, v, p (level n) with valid depth-2 halos towards every neighbour, corners included; uold, vold, pold
+ * (level n-1) with valid depth-1 halos; on sides without a neighbour the ring rules of dlesm_shallow_step_x2_f64.  Out:
+ * unew2.. (level n+2) valid on the box and in its depth-2 halos (one exchange); unew.. (level n+1) valid on the box grown by
+ * one cell towards every side that has a neighbour (corners where both sides have one) -- computed there, not exchanged, and
+ * bit for bit the neighbour's interior cells -- other halo cells of unew.. keep what they held.  Both levels are what
+ * step + depth-2 exchange, twice, leave in those cells.  Time loop: (cur, old, new1, new2) <- (new2, new1, old, cur).
+ * Filtered form.  In: level n with depth-2 halos, the filtered level n-1 with depth-1 halos, both untouched.  Out: level n+2
+ * (unew2..) and the filtered level n+1 (uold2..), both with valid depth-2 halos: what two calls of dlesm_shallow_step_smooth_dm
+ * on a depth-2 plan leave as the new current and old levels.  The filtered level n+1 needs level n+2 at the cell, so it
+ * is exchanged with it: six fields in one aggregated exchange (two turns of three in mailbox mode).
+ * Twelve distinct arrays, as for the single-domain entries; plan dimensions ld x ny. */
+int dlesm_shallow_step_x2_dm(dlesm_halo_plan *plan, const dlesm_sw_params *q, int ld, int ny,
+                             int xstart, int xstop, int ystart, int ystop,
+                             const double *u, const double *v, const double *p,
+                             const double *uold, const double *vold, const double *pold,
+                             double *unew, double *vnew, double *pnew,
+                             double *unew2, double *vnew2, double *pnew2, void *stream);
+int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *plan, const dlesm_sw_params *q, double alpha, int ld, int ny,
+                                    int xstart, int xstop, int ystart, int ystop,
+                                    const double *u, const double *v, const double *p,
+                                    const double *uold, const double *vold, const double *pold,
+                                    double *unew2, double *vnew2, double *pnew2,
+                                    double *uold2, double *vold2, double *pold2, void *stream);
 
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
