@@ -617,6 +617,14 @@ extern "C" int dlesm_shallow_step_x2_f64(const dlesm_sw_params *q, int ld, int n
     return DLESM_OK;
 }
 
+// the 1-based inclusive box of one (ny, ld) array into the same cells of another, stream-ordered
+static hipError_t copy_box(double *dst, const double *src, int ld, int xstart, int xstop, int ystart, int ystop, hipStream_t s)
+{
+    const size_t o = (size_t)(ystart - 1) * ld + (xstart - 1), pitch = (size_t)ld * sizeof(double);
+    return hipMemcpy2DAsync(dst + o, pitch, src + o, pitch, (size_t)(xstop - xstart + 1) * sizeof(double), (size_t)(ystop - ystart + 1),
+                            hipMemcpyDeviceToDevice, s);
+}
+
 // Two FILTERED leapfrog steps, one launch: two whole time steps of the GOcean loop (update + time_smooth of the old level, twice).
 // With levels n (u, v, p) and n-1 (uold, vold, pold: the filtered one, as the loop keeps it) it leaves level n+2 in
 // (unew2, vnew2, pnew2) and the FILTERED level n+1 in (uold2, vold2, pold2) -- what two calls of dlesm_shallow_step_smooth_f64
@@ -646,8 +654,8 @@ extern "C" int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
-    // the definition: old2 <- old; T <- ring of u (the level-n+1 ring); step_smooth(u, old2 -> filtered n, T = n+1);
-    // step_smooth(T, old2 -> filtered n+1, new2 = n+2)
+    // the definition: old2 <- old on the box (the only cells the filter reads, and the only ones the fused kernel writes);
+    // T <- u (the level-n+1 ring); step_smooth(u, old2 -> filtered n, T = n+1); step_smooth(T, old2 -> filtered n+1, new2 = n+2)
     const size_t bytes = (size_t)ld * ny * sizeof(double);
     double *t[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; k++)
@@ -659,7 +667,9 @@ extern "C" int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double
     double *dst[6] = {uold2, vold2, pold2, t[0], t[1], t[2]};
     int rc = DLESM_OK;
     for (int k = 0; k < 6 && !rc; k++)
-        if (hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = fail(DLESM_EHIP, "dlesm_shallow_step_smooth_x2_f64: copy failed");
+        if ((k < 3 ? copy_box(dst[k], src[k], ld, xstart, xstop, ystart, ystop, s)
+                   : hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+            rc = fail(DLESM_EHIP, "dlesm_shallow_step_smooth_x2_f64: copy failed");
     if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
     if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
     for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
@@ -731,7 +741,8 @@ extern "C" int dlesm_shallow_step_sw_smooth_x2_periodic_f64(const dlesm_sw_param
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
-    // the definition, through three stream-ordered scratch arrays for the unfiltered level n+1
+    // the definition, through three stream-ordered scratch arrays for the unfiltered level n+1; old2 <- old on the box only
+    // (what the filter reads; the steps write the periodic images), so that no other cell of old2 is touched
     const size_t bytes = (size_t)ld * ny * sizeof(double);
     double *t[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; k++)
@@ -743,7 +754,8 @@ extern "C" int dlesm_shallow_step_sw_smooth_x2_periodic_f64(const dlesm_sw_param
     double *dst[3] = {uold2, vold2, pold2};
     int rc = DLESM_OK;
     for (int k = 0; k < 3 && !rc; k++)
-        if (hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = fail(DLESM_EHIP, "dlesm_shallow_step_sw_smooth_x2_periodic_f64: copy failed");
+        if (copy_box(dst[k], src[k], ld, internal->xstart, internal->xstop, internal->ystart, internal->ystop, s) != hipSuccess)
+            rc = fail(DLESM_EHIP, "dlesm_shallow_step_sw_smooth_x2_periodic_f64: copy failed");
     if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
     if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
     for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);

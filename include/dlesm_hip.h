@@ -349,6 +349,9 @@ int dlesm_shallow_step_x2_f64(const dlesm_sw_params *q, int ld, int ny, int xsta
  * dlesm_shallow_step_smooth_f64 with the usual rotation leave, bit for bit, provided the boundary ring is the same at every time
  * level (the ring of the unfiltered level n+1, which no array holds, is taken from u, v, p).  48 B/cell/step against 96 for the
  * one-launch filtered step.  Time loop: ping-pong (u.., uold..) <-> (unew2.., uold2..).
+ * Cells written: the box of unew2 / vnew2 / pnew2 and of uold2 / vold2 / pold2, nothing else; every other cell of the six outputs
+ * (ring, halos, padding columns) keeps the value it had before the call.  This holds on every path, the fall-back for arrays the
+ * wave tiles cannot take included.
  * Single domain only: on a decomposed grid use dlesm_shallow_step_smooth_x2_dm. */
 int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double alpha, int ld, int ny, int xstart, int xstop, int ystart,
                                      int ystop, const double *u, const double *v, const double *p, const double *uold,
@@ -358,7 +361,9 @@ int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double alpha, int
  * (field_mod.f90:675-751, 1394-1464): == two calls of dlesm_shallow_step_sw_periodic_f64 / dlesm_shallow_step_sw_smooth_periodic_f64
  * with the loop's rotation, periodic images of every level that comes out included.  Level n+1 one cell outside the box is the
  * image of level n+1 inside, so the first stage reads level n TWO cells outside the box from where it is the image of.  Beyond
- * the single steps' preconditions: level n-1 carries valid periodic halos as well. */
+ * the single steps' preconditions: level n-1 carries valid periodic halos as well.  Cells written: the internal region of each
+ * output and its periodic images (halo rows and columns, corners included), nothing else -- on every path, the fall-back
+ * included; every other cell (padding columns and rows beyond the halos) keeps the value it had before the call. */
 int dlesm_shallow_step_sw_x2_periodic_f64(const dlesm_sw_params *q, int ld, int ny, const dlesm_region *internal, int bc_x, int bc_y,
                                           const double *u, const double *v, const double *p, const double *uold, const double *vold,
                                           const double *pold, double *unew, double *vnew, double *pnew, double *unew2,

@@ -304,6 +304,66 @@ def sw_kernel(name, sw_offset, ld, box, out, ins, s0=0.0, s1=0.0):
     assert rc == 0, rc
 
 
+def slabs(fn, ld, box, ins, outs, ring, bands=None, threads=None):
+    """apply a single-threaded oracle entry to whole (ny, ld) fields by row slabs, in a thread pool (ctypes releases the
+    GIL). Each slab is a band of the box's rows plus the `ring` rows above and below that the entry reads, copied into
+    arrays of its own; fn(ld, local_box, *local_ins, *local_outs) runs on them and the band's rows of every output go
+    back into the whole array. Outputs are copied in too, so that cells the entry does not write (and outputs it also
+    reads) keep their values; an array passed as both an input and an output is one slab array. Bit for bit what one
+    whole-array call leaves, since every entry is pointwise."""
+    from concurrent.futures import ThreadPoolExecutor
+    xs, xe, ys, ye = box
+    if xe < xs or ye < ys:
+        return
+    ny = outs[0].shape[0]
+    threads = threads or host_threads()
+    nb = max(1, min(ye - ys + 1, bands or 4 * threads))
+    h = -(-(ye - ys + 1) // nb)
+
+    def band(b0):
+        b1 = min(ye, b0 + h - 1)
+        lo, hi = max(1, b0 - ring), min(ny, b1 + ring)          # 1-based rows of the slab
+        local = {}
+        for a in list(ins) + list(outs):
+            if id(a) not in local:
+                local[id(a)] = a[lo - 1:hi].copy()
+        fn(ld, (xs, xe, b0 - lo + 1, b1 - lo + 1), *[local[id(a)] for a in ins], *[local[id(a)] for a in outs])
+        for a in outs:
+            a[b0 - 1:b1] = local[id(a)][b0 - lo:b1 - lo + 1]
+
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        list(pool.map(band, range(ys, ye + 1, h)))
+
+
+def jacobi5_slabs(inp, out, ld, xs, xe, ys, ye):
+    slabs(lambda ld_, b, i, o: lib().orc_jacobi5(i, o, ld_, *b), ld, (xs, xe, ys, ye), [inp], [out], 1)
+
+
+def jacobi5_masked_slabs(inp, out, tmask, ld, xs, xe, ys, ye):
+    slabs(lambda ld_, b, i, t, o: lib().orc_jacobi5_masked(i, o, t, ld_, *b), ld, (xs, xe, ys, ye), [inp, tmask], [out], 1)
+
+
+def stencil9_slabs(inp, out, coef, ld, xs, xe, ys, ye):
+    slabs(lambda ld_, b, i, o: stencil9(i, o, coef, ld_, *b), ld, (xs, xe, ys, ye), [inp], [out], 1)
+
+
+def continuity_slabs(rdt, ld, box, sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t, ssha):
+    slabs(lambda ld_, b, *a: continuity(rdt, ld_, b, *a), ld, box, [sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t], [ssha], 1)
+
+
+def sw_step_slabs(prm, ld, box, u, v, p, uold, vold, pold, unew, vnew, pnew):
+    """orc_sw_step by slabs, scratch intermediates per slab (on the box grown by one, they read one row beyond the box)"""
+    slabs(lambda ld_, b, *a: sw_step(prm, ld_, b, *a), ld, box, [u, v, p, uold, vold, pold], [unew, vnew, pnew], 1)
+
+
+def sw_step_sw_slabs(prm, ld, box, u, v, p, uold, vold, pold, unew, vnew, pnew):
+    slabs(lambda ld_, b, *a: sw_step_sw(prm, ld_, b, *a), ld, box, [u, v, p, uold, vold, pold], [unew, vnew, pnew], 1)
+
+
+def sw_kernel_slabs(name, sw_offset, ld, box, out, ins, s0=0.0, s1=0.0):
+    slabs(lambda ld_, b, *a: sw_kernel(name, sw_offset, ld_, b, a[-1], a[:-1], s0, s1), ld, box, list(ins), [out], 1)
+
+
 def sw_step_fortran(prm, ld, box, u, v, p, uold, vold, pold, unew, vnew, pnew, threads=1, scratch=None):
     """the NE-offset step as the seven Fortran PSy loop nests over pointwise GOcean kernels (oracle/cpu_psy_loops.f90),
     OpenMP over jj: what a GOcean application runs on the CPU"""

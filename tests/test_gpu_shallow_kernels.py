@@ -264,15 +264,38 @@ def test_seven_launches_equal_the_fused_step(D, nx, ny, alignment, sw_offset):
         assert np.array_equal(f.get_data(), w), (n, "fused != oracle")
 
 
+def _oracle_sequence(g, it, H, sw_offset):
+    """the oracle's seven loop nests over whole fields (by slabs) on the boxes invoke_shallow_kernel_sequence uses: non-periodic
+    grids grow the intermediates' boxes towards their consumers, periodic ones take the internal region + periodic copies"""
+    prm = N.Params(g.dx, g.dy, DT)
+    xs, xe, ys, ye = box = it.box()
+    if sw_offset:
+        grown = dict(cu=box, cv=box, z=box, h=box)
+    else:
+        grown = dict(cu=(xs - 1, xe, ys, ye + 1), cv=(xs, xe + 1, ys - 1, ye), z=(xs - 1, xe, ys - 1, ye), h=(xs, xe + 1, ys, ye + 1))
+    u, v, p = H["u"], H["v"], H["p"]
+    O.sw_kernel_slabs("cu", sw_offset, g.nx, grown["cu"], H["cu"], [p, u])
+    O.sw_kernel_slabs("cv", sw_offset, g.nx, grown["cv"], H["cv"], [p, v])
+    O.sw_kernel_slabs("z", sw_offset, g.nx, grown["z"], H["z"], [p, u, v], prm.fsdx, prm.fsdy)
+    O.sw_kernel_slabs("h", sw_offset, g.nx, grown["h"], H["h"], [p, u, v])
+    if sw_offset:
+        for n in ("cu", "cv", "z", "h"):
+            O.apply_periodic_halos(H[n], g.nx, box, 0, 0)
+    O.sw_kernel_slabs("unew", sw_offset, g.nx, box, H["unew"], [H["uold"], H["z"], H["cv"], H["h"]], prm.tdts8, prm.tdtsdx)
+    O.sw_kernel_slabs("vnew", sw_offset, g.nx, box, H["vnew"], [H["vold"], H["z"], H["cu"], H["h"]], prm.tdts8, prm.tdtsdy)
+    O.sw_kernel_slabs("pnew", sw_offset, g.nx, box, H["pnew"], [H["pold"], H["cu"], H["cv"]], prm.tdtsdx, prm.tdtsdy)
+
+
 @pytest.mark.parametrize("sw_offset", [False, True], ids=["NE", "SW-periodic"])
 def test_seven_launches_equal_the_fused_step_at_8192(D, sw_offset):
-    """BASELINE configs[3]: 8192 x 8192, DL_ESM_ALIGNMENT = 64; compared on the device"""
+    """BASELINE configs[3]: 8192 x 8192, DL_ESM_ALIGNMENT = 64, default store policies: the seven launches == the fused step
+    on the device, and every cell of the four sentinel-filled intermediates and the three new levels == the oracle's loop nests"""
     import torch
     g = _grid(D, 8192, 8192, 64, sw_offset)
     names, F = _state(D, g)
     prm = D.psy.shallow_params(g.dx, g.dy, DT)
     fused = [D.r2d_field(g, F[n].defined_on) for n in ("u", "v", "p")]
-    for f in fused + [F[n] for n in ("unew", "vnew", "pnew")]:
+    for f in fused + [F[n] for n in ("unew", "vnew", "pnew", "cu", "cv", "z", "h")]:
         D.set_field(f, 9.0)
     step = D.psy.invoke_shallow_step_sw if sw_offset else D.psy.invoke_shallow_step
     step(prm, *[F[n] for n in names[:6]], *fused)
@@ -284,6 +307,12 @@ def test_seven_launches_equal_the_fused_step_at_8192(D, sw_offset):
         assert bool(torch.equal(F[n].data, f.data)), n
         inner = f.data[it.ystart - 1:it.ystop, it.xstart - 1:it.xstop]
         assert bool(torch.isfinite(inner).all()) and not bool((inner == 9.0).any()), n
+    del fused
+    H = {n: F[n].get_data() for n in names[:6]}
+    H.update({n: np.full((g.ny, g.nx), 9.0) for n in ("cu", "cv", "z", "h", "unew", "vnew", "pnew")})
+    _oracle_sequence(g, it, H, sw_offset)
+    for n in ("cu", "cv", "z", "h", "unew", "vnew", "pnew"):
+        assert np.array_equal(F[n].get_data(), H[n]), n
 
 
 @pytest.mark.parametrize("nx,ny,alignment", [(10, 10, None), (64, 48, 8), (300, 77, None)])
@@ -397,29 +426,45 @@ def test_step_with_the_filter_folded_in_equals_step_plus_time_smooth(D, nx, ny, 
 
 @pytest.mark.parametrize("sw_offset", [False, True], ids=["NE", "SW-periodic"])
 def test_step_with_the_filter_folded_in_at_8192(D, sw_offset):
-    """BASELINE configs[3]'s size: the one-launch time step against step + three time_smooth launches, on the device"""
+    """BASELINE configs[3]'s size: the one-launch time step against step + three time_smooth launches on the device, whole
+    arrays; and every cell of the sentinel-filled new level and of the filtered old level against the oracle's step +
+    time_smooth loop nests (+ the periodic copies of both levels)"""
     import torch
     g = _grid(D, 8192, 8192, 64, sw_offset)
     names, A = _state(D, g)
     del A["cu"], A["cv"], A["z"], A["h"]
     prm = D.psy.shallow_params(g.dx, g.dy, DT)
+    alpha = 0.001
     B = {n: D.r2d_field(g, A[n].defined_on) for n in names[3:]}
+    for n in names[6:]:
+        D.set_field(A[n], 9.0)
+        D.set_field(B[n], 9.0)
     for n in names[3:6]:
         D.copy_field(A[n], B[n])
+    torch.cuda.synchronize()
+    it = A["p"].internal
+    H = {n: A[n].get_data() for n in names}
     cur = [A[n] for n in names[:3]]
     a = cur + [A[n] for n in names[3:]]
     b = cur + [B[n] for n in names[3:]]
     if sw_offset:
-        D.psy.invoke_shallow_step_sw_smooth_periodic(prm, 0.001, *a)
+        D.psy.invoke_shallow_step_sw_smooth_periodic(prm, alpha, *a)
         D.psy.invoke_shallow_step_sw_periodic(prm, *b)
     else:
-        D.psy.invoke_shallow_step_smooth(prm, 0.001, *a)
+        D.psy.invoke_shallow_step_smooth(prm, alpha, *a)
         D.psy.invoke_shallow_step(prm, *b)
     for k in range(3):
-        D.psy.invoke_time_smooth(cur[k], b[6 + k], b[3 + k], 0.001)
+        D.psy.invoke_time_smooth(cur[k], b[6 + k], b[3 + k], alpha)
     if sw_offset:
         D.psy.apply_periodic_halos_multi(b[3:6])
     torch.cuda.synchronize()
-    n = 8192
     for k in range(3, 9):
-        assert bool(torch.equal(a[k].data[:n + 2, :n + 2], b[k].data[:n + 2, :n + 2])), names[k]
+        assert bool(torch.equal(a[k].data, b[k].data)), names[k]
+    del B, b
+    (O.sw_step_sw_slabs if sw_offset else O.sw_step_slabs)(N.Params(g.dx, g.dy, DT), g.nx, it.box(), *[H[n] for n in names])
+    for c, nw, o in zip(names[:3], names[6:], names[3:6]):
+        O.sw_kernel_slabs("time_smooth", sw_offset, g.nx, it.box(), H[o], [H[c], H[nw], H[o]], alpha)
+    for n in names[3:]:
+        if sw_offset:
+            O.apply_periodic_halos(H[n], g.nx, it.box(), 0, 0)
+        assert np.array_equal(A[n].get_data(), H[n]), n

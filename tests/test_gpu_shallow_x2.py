@@ -56,6 +56,14 @@ def _fields(D, g, seed=SEED):
     return F
 
 
+def _sentinel_but_ring(f, it, value=-3.0):
+    """every cell of f but the boundary ring (which the next step reads as level n's ring) set to value"""
+    ring = f.data[it.ystart - 2:it.ystop + 1, it.xstart - 2:it.xstop + 1].clone()
+    f.data.fill_(value)
+    f.data[it.ystart - 2:it.ystop + 1, it.xstart - 2:it.xstop + 1] = ring
+    f.data[it.ystart - 1:it.ystop, it.xstart - 1:it.xstop] = value
+
+
 def _oracle_two_steps(prm, g, box, H):
     """level n+1 and n+2 by two oracle steps (the second reads the first's output incl. its untouched ring)"""
     n1 = [H[n].copy() for n in NAMES[6:9]]
@@ -163,7 +171,8 @@ def test_time_loop_of_double_steps_equals_single_steps(D, nx, ny, alignment, pai
 
 
 def test_full_size_equals_two_single_steps(D):
-    """BASELINE configs[3]'s size: 8192^2, alignment 64, both new levels against the single-step kernel"""
+    """BASELINE configs[3]'s size: 8192^2, alignment 64, both new levels against the single-step kernel, and every cell of
+    them against the oracle's two steps"""
     import torch
     g = _grid(D, 8192, 8192, 64)
     F = _fields(D, g, SEED + 9)
@@ -171,12 +180,94 @@ def test_full_size_equals_two_single_steps(D):
     for x, n in zip(chk, NAMES[6:]):
         D.copy_field(F[n], x)
     prm = D.psy.shallow_params(1.0e5, 1.0e5, 90.0)
+    torch.cuda.synchronize()
+    H = {n: F[n].get_data() for n in NAMES}
     D.psy.invoke_shallow_step_x2(prm, *[F[n] for n in NAMES])
     D.psy.invoke_shallow_step(prm, *[F[n] for n in NAMES[:6]], *chk[:3])
     D.psy.invoke_shallow_step(prm, *chk[:3], *[F[n] for n in NAMES[:3]], *chk[3:])
     torch.cuda.synchronize()
     for x, n in zip(chk, NAMES[6:]):
         assert torch.equal(x.data, F[n].data), n
+    del chk
+    n1, n2 = [H[n] for n in NAMES[6:9]], [H[n] for n in NAMES[9:]]        # and every cell of both levels against the oracle
+    O.sw_step_slabs(prm, g.nx, F["p"].internal.box(), *[H[n] for n in NAMES[:6]], *n1)
+    O.sw_step_slabs(prm, g.nx, F["p"].internal.box(), *n1, *[H[n] for n in NAMES[:3]], *n2)
+    for name, want in zip(NAMES[6:], n1 + n2):
+        assert np.array_equal(F[name].get_data(), want), name
+
+
+def _oracle_x2(form, prm, alpha, g, it, cur, old, o1, o2):
+    """one call of a two-step entry as the oracle's leapfrog on whole host arrays (by slabs): plain forms leave level n+1 in o1
+    and n+2 in o2; filtered forms leave n+2 in o1 and the filtered n+1 in o2 -- their definition, old2 <- old on the box, the
+    unfiltered n+1 in a scratch array; the periodic forms write the periodic images of every level that comes out"""
+    sw = form.startswith("sw")
+    step = O.sw_step_sw_slabs if sw else O.sw_step_slabs
+    box = it.box()
+    images = (lambda fs: [O.apply_periodic_halos(f, g.nx, box, 0, 0) for f in fs]) if sw else (lambda fs: None)
+    if "smooth" not in form:
+        step(prm, g.nx, box, *cur, *old, *o1)
+        images(o1)
+        step(prm, g.nx, box, *o1, *cur, *o2)
+        images(o2)
+        return
+    cut = (slice(it.ystart - 1, it.ystop), slice(it.xstart - 1, it.xstop))
+    t = [c.copy() for c in cur]
+    for a, b in zip(o2, old):
+        a[cut] = b[cut]
+    for lev, new in ((cur, t), (t, o1)):
+        step(prm, g.nx, box, *lev, *o2, *new)
+        for f, fn, fo in zip(lev, new, o2):
+            O.sw_kernel_slabs("time_smooth", sw, g.nx, box, fo, [f, fn, fo], alpha)
+        images(new + o2)
+
+
+X2_LOOP_CASES = [("plain", 64), ("plain", None), ("smooth", 64), ("sw_plain", 64), ("sw_smooth", 64)]
+
+
+@pytest.mark.parametrize("form,alignment", X2_LOOP_CASES)
+def test_two_step_forms_at_8192_as_a_time_loop_against_the_oracle(D, form, alignment):
+    """BASELINE configs[3]'s size, default paths and store policies: three calls (six time steps) of each two-step entry with
+    the rotation bench.py uses, then every cell of all twelve arrays -- box, ring or periodic images, padding columns, the
+    filtered old level -- against the oracle's leapfrog.  Outputs start as a -3 sentinel (NE: all but the boundary ring)."""
+    import torch
+    sw = form.startswith("sw")
+    g = _grid_sw(D, 8192, 8192, alignment) if sw else _grid(D, 8192, 8192, alignment)
+    F = _periodic_fields(D, g, SEED + 400) if sw else _fields(D, g, SEED + 400)
+    it = F["p"].internal
+    if not sw:
+        for n in NAMES[6:]:
+            _sentinel_but_ring(F[n], it)
+        if form == "smooth":
+            for n in NAMES[9:]:                     # the filtered level's ring is never read
+                D.set_field(F[n], -3.0)
+    prm = D.psy.shallow_params(1.0e5, 0.9e5, 40.0)
+    alpha = 0.001
+    torch.cuda.synchronize()
+    A = [F[n] for n in NAMES]
+    H = [f.get_data() for f in A]
+    cur, old, o1, o2 = A[:3], A[3:6], A[6:9], A[9:]
+    hc, ho, h1, h2 = H[:3], H[3:6], H[6:9], H[9:]
+    for _ in range(3):
+        if form == "plain":
+            D.psy.invoke_shallow_step_x2(prm, *cur, *old, *o1, *o2)
+        elif form == "smooth":
+            D.psy.invoke_shallow_step_smooth_x2(prm, alpha, *cur, *old, *o1, *o2)
+        elif form == "sw_plain":
+            D.psy.invoke_shallow_step_sw_x2_periodic(prm, *cur, *old, *o1, *o2)
+        else:
+            D.psy.invoke_shallow_step_sw_smooth_x2_periodic(prm, alpha, *cur, *old, *o1, *o2)
+        _oracle_x2(form, prm, alpha, g, it, hc, ho, h1, h2)
+        if "smooth" in form:      # (n+2, filtered n+1) are the new (current, old)
+            cur, old, o1, o2 = o1, o2, cur, old
+            hc, ho, h1, h2 = h1, h2, hc, ho
+        else:                     # (n+2, n+1) are the new (current, old)
+            cur, old, o1, o2 = o2, o1, old, cur
+            hc, ho, h1, h2 = h2, h1, ho, hc
+    torch.cuda.synchronize()
+    for n, f, h in zip(NAMES, A, H):
+        got = f.get_data()
+        assert np.array_equal(got, h), (form, n, int(np.count_nonzero(got != h)), np.argwhere(got != h)[:6].tolist())
+    assert np.isfinite(hc[2][it.ystart - 1:it.ystop, it.xstart - 1:it.xstop]).all()
 
 
 # ---- with the Asselin filter after each step: two whole time steps of the GOcean loop per launch --------------------------------
@@ -192,8 +283,12 @@ def test_two_filtered_steps_per_launch(D, nx, ny, alignment, fallback, x2_rows):
     prm = D.psy.shallow_params(1.0e5, 0.9e5, 40.0)
     A, B = _fields(D, g, SEED + 21), _fields(D, g, SEED + 21)
     a_cur, a_old, a_n2, a_o2 = ([A[n] for n in NAMES[k:k + 3]] for k in (0, 3, 6, 9))
-    for src, dst in zip(a_cur, a_o2):                 # every array of the run carries the same boundary ring
-        D.copy_field(src, dst)
+    it = A["p"].internal
+    box = (slice(it.ystart - 1, it.ystop), slice(it.xstart - 1, it.xstop))
+    for f in a_n2:                                    # level n+2 becomes level n: it keeps the boundary ring; all else a sentinel
+        _sentinel_but_ring(f, it)
+    for f in a_o2:                                    # nothing reads the ring of the old level: a sentinel everywhere
+        D.set_field(f, -3.0)
     b_cur, b_old, b_new = ([B[n] for n in NAMES[k:k + 3]] for k in (0, 3, 6))
     L.dlesm_set_tuning(b"sw_x2_fused", 0 if fallback else 1)
     if x2_rows:
@@ -201,6 +296,7 @@ def test_two_filtered_steps_per_launch(D, nx, ny, alignment, fallback, x2_rows):
     try:
         for pair in range(3):
             keep = [f.data.clone() for f in a_cur + a_old]
+            before = [f.data.clone() for f in a_n2 + a_o2]
             D.psy.invoke_shallow_step_smooth_x2(prm, alpha, *a_cur, *a_old, *a_n2, *a_o2)
             torch.cuda.synchronize()
             assert all(torch.equal(k, f.data) for k, f in zip(keep, a_cur + a_old)), "inputs modified"
@@ -209,10 +305,10 @@ def test_two_filtered_steps_per_launch(D, nx, ny, alignment, fallback, x2_rows):
                 D.psy.invoke_shallow_step_smooth(prm, alpha, *b_cur, *b_old, *b_new)
                 b_cur, b_old, b_new = b_new, b_old, b_cur          # uold already holds the filtered former current
             torch.cuda.synchronize()
-            it = A["p"].internal
-            cut = lambda f: f.data[it.ystart - 1:it.ystop, it.xstart - 1:it.xstop]      # noqa: E731
-            for x, y in zip(a_cur + a_old, b_cur + b_old):
-                assert torch.equal(cut(x), cut(y)), (pair, int((cut(x) != cut(y)).sum()))
+            # whole arrays: the box is the two filtered steps, every other cell what the output held before the call
+            for x, y, want in zip(a_cur + a_old, b_cur + b_old, before):
+                want[box] = y.data[box]
+                assert torch.equal(x.data, want), (pair, int((x.data != want).sum()), (x.data != want).nonzero()[:6].tolist())
     finally:
         L.dlesm_set_tuning(b"sw_x2_fused", 1)
         if x2_rows:
@@ -334,20 +430,24 @@ def _filtered_periodic(D, nx, ny, alignment, fallback, sw_form):
     it = A["p"].internal
     a_cur, a_old, a_n2, a_o2 = ([A[n] for n in NAMES[k:k + 3]] for k in (0, 3, 6, 9))
     b_cur, b_old, b_new = ([B[n] for n in NAMES[k:k + 3]] for k in (0, 3, 6))
-    cut = lambda f: f.data[:it.ystop + 1, :it.xstop + 1]      # noqa: E731
+    model = (slice(0, it.ystop + 1), slice(0, it.xstop + 1))      # the internal region and its halo ring
     L.dlesm_set_tuning(b"sw_x2_fused", 0 if fallback else 1)
     if sw_form:
         L.dlesm_set_tuning(b"sw_x2_sw_form", sw_form)
     try:
         for pair in range(3):
+            before = [f.data.clone() for f in a_n2 + a_o2]           # (pair 0: the -3 sentinel everywhere)
             D.psy.invoke_shallow_step_sw_smooth_x2_periodic(prm, alpha, *a_cur, *a_old, *a_n2, *a_o2)
             a_cur, a_old, a_n2, a_o2 = a_n2, a_o2, a_cur, a_old
             for _ in range(2):
                 D.psy.invoke_shallow_step_sw_smooth_periodic(prm, alpha, *b_cur, *b_old, *b_new)
                 b_cur, b_old, b_new = b_new, b_old, b_cur
             torch.cuda.synchronize()
-            for x, y in zip(a_cur + a_old, b_cur + b_old):
-                assert torch.equal(cut(x), cut(y)), (pair, int((cut(x) != cut(y)).sum()), (cut(x) != cut(y)).nonzero()[:6].tolist())
+            # whole arrays: internal region and halos are the two filtered steps, every other cell (padding columns, rows beyond
+            # the halos) what the output held before the call
+            for x, y, want in zip(a_cur + a_old, b_cur + b_old, before):
+                want[model] = y.data[model]
+                assert torch.equal(x.data, want), (pair, int((x.data != want).sum()), (x.data != want).nonzero()[:6].tolist())
     finally:
         L.dlesm_set_tuning(b"sw_x2_fused", 1)
         if sw_form:
