@@ -86,6 +86,19 @@ class SwParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("fsdx", "fsdy", "tdts8", "tdtsdx", "tdtsdy")]
 
 
+class MomentumParams(C.Structure):
+    """dlesm_momentum_params"""
+    _fields_ = [(n, C.c_double) for n in ("rdt", "cbfr", "visc", "g")]
+
+
+MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
+
+
+class MomentumGrid(C.Structure):
+    """dlesm_momentum_grid: device pointers of the grid properties the momentum kernels read"""
+    _fields_ = [(n, C.c_void_p) for n in MOMENTUM_GRID_ARRAYS]
+
+
 # every entry point include/dlesm_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 _pi = C.POINTER(C.c_int)
@@ -117,6 +130,12 @@ PROTOTYPES = {
     "dlesm_stencil5_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil5_planned_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "dlesm_continuity_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
+    "dlesm_momentum_u_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_vp]),
+    "dlesm_momentum_v_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_vp]),
+    "dlesm_momentum_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _i, _i, C.POINTER(Region), C.POINTER(Region)] +
+                           [_vp] * 12 + [_vp]),
+    "dlesm_next_sshu_f64": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
+    "dlesm_next_sshv_f64": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
     "dlesm_stencil9_f64": (_i, [_vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil9_step_dm": (_i, [_vp, _vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil5_masked_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

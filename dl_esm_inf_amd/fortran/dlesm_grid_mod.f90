@@ -49,6 +49,9 @@ module grid_mod
      real(go_wp), allocatable :: gphiv(:,:)
      real(go_wp), allocatable :: gphif(:,:)
      type(c_ptr) :: gphiu_device, gphiv_device, gphif_device
+     !> Coriolis parameter at u / v points, (2*omega)*sin(gphiu/v*d2r): set by momentum_coriolis (dlesm_psy_mod)
+     real(go_wp), allocatable :: fcor_u(:,:), fcor_v(:,:)
+     type(c_ptr) :: fcor_u_device, fcor_v_device
      real(go_wp), allocatable :: xt(:,:), yt(:,:)
      type(c_ptr) :: xt_device, yt_device
    contains
@@ -114,6 +117,7 @@ contains
     self%area_v_device = c_null_ptr
     self%gphiu_device = c_null_ptr;  self%gphiv_device = c_null_ptr
     self%gphif_device = c_null_ptr
+    self%fcor_u_device = c_null_ptr;  self%fcor_v_device = c_null_ptr
     self%xt_device = c_null_ptr;  self%yt_device = c_null_ptr
   end function grid_constructor
 

@@ -41,6 +41,16 @@ module dlesm_hip_mod
      real(c_double) :: fsdx, fsdy, tdts8, tdtsdx, tdtsdy
   end type c_sw_params
 
+  !> struct dlesm_momentum_params (DESIGN.md section 6.5)
+  type, bind(C) :: c_momentum_params
+     real(c_double) :: rdt, cbfr, visc, g
+  end type c_momentum_params
+
+  !> struct dlesm_momentum_grid: device pointers of the grid properties the momentum kernels read
+  type, bind(C) :: c_momentum_grid
+     type(c_ptr) :: tmask, dx_t, dy_t, dx_u, dy_u, dx_v, dy_v, area_u, area_v, fcor_u, fcor_v
+  end type c_momentum_grid
+
   interface
      ! ---- host-side index maps -------------------------------------------
      function dlesm_alignment_from_env(alignment) bind(C, name="dlesm_alignment_from_env") result(rc)
@@ -181,6 +191,49 @@ module dlesm_hip_mod
        real(c_double), value :: rdt
        integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
        type(c_ptr), value :: sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t, ssha, stream
+       integer(c_int) :: rc
+     end function
+     ! ---- NEMOLite2D-class momentum and sea-surface-height interpolation (DESIGN.md section 6.5)
+     function dlesm_momentum_u_f64(params, grid, ld, ny, xstart, xstop, ystart, ystop, un, vn, ht, sshn_t, hu, sshn_u, &
+          hv, sshn_v, ssha_u, ua, stream) bind(C, name="dlesm_momentum_u_f64") result(rc)
+       import :: c_int, c_ptr, c_momentum_params, c_momentum_grid
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ua, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_momentum_v_f64(params, grid, ld, ny, xstart, xstop, ystart, ystop, un, vn, ht, sshn_t, hu, sshn_u, &
+          hv, sshn_v, ssha_v, va, stream) bind(C, name="dlesm_momentum_v_f64") result(rc)
+       import :: c_int, c_ptr, c_momentum_params, c_momentum_grid
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_v, va, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_momentum_f64(params, grid, ld, ny, ubox, vbox, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, &
+          ssha_u, ssha_v, ua, va, stream) bind(C, name="dlesm_momentum_f64") result(rc)
+       import :: c_int, c_ptr, c_momentum_params, c_momentum_grid, c_region
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: ubox, vbox
+       type(c_ptr), value :: un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ssha_v, ua, va, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_next_sshu_f64(ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, area_u, sshn_t, sshn_u, stream) &
+          bind(C, name="dlesm_next_sshu_f64") result(rc)
+       import :: c_int, c_ptr
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, area_u, sshn_t, sshn_u, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_next_sshv_f64(ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, area_v, sshn_t, sshn_v, stream) &
+          bind(C, name="dlesm_next_sshv_f64") result(rc)
+       import :: c_int, c_ptr
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, area_v, sshn_t, sshn_v, stream
        integer(c_int) :: rc
      end function
      function dlesm_stencil5_masked_f64(in, out, tmask, ld, ny, xstart, xstop, ystart, ystop, stream) &

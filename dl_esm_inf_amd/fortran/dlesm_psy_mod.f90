@@ -51,6 +51,8 @@ module dlesm_psy_mod
   public :: invoke_shallow_step_sw, invoke_periodic_halos, invoke_stencil9, invoke_stencil9_dm
   public :: invoke_jacobi5, invoke_jacobi5_dm, invoke_shallow_step, invoke_copy, invoke_hash_init
   public :: invoke_shallow_step_dm_pipelined, invoke_continuity
+  public :: momentum_params, c_momentum_params, momentum_coriolis, invoke_momentum_u, invoke_momentum_v, invoke_momentum
+  public :: invoke_next_sshu, invoke_next_sshv
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -175,6 +177,142 @@ contains
                               field_device_data(vn), ssha%grid%area_t_device, field_device_data(ssha), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_continuity: ' // dlesm_error_text())
   end subroutine invoke_continuity
+
+  !> Constants of the NEMOLite2D-class momentum kernels (DESIGN.md section 6.5): time step, bottom friction
+  !! coefficient, viscosity, gravity.
+  function momentum_params(rdt, cbfr, visc, g) result(p)
+    real(go_wp), intent(in) :: rdt, cbfr, visc, g
+    type(c_momentum_params) :: p
+    p = c_momentum_params(real(rdt, c_double), real(cbfr, c_double), real(visc, c_double), real(g, c_double))
+  end function momentum_params
+
+  !> The Coriolis parameter of the momentum kernels, once per grid (DESIGN.md section 6.5):
+  !! fcor_u = (2*omega)*sin(gphiu*d2r) and fcor_v from gphiv, computed on the host and uploaded.  The
+  !! kernels never evaluate a transcendental.  Called again, it recomputes and uploads again.
+  subroutine momentum_coriolis(grid, omega, d2r)
+    type(grid_type), intent(inout), target :: grid
+    real(go_wp), intent(in) :: omega, d2r
+    integer(c_size_t) :: nb
+    if (.not. allocated(grid%gphiu) .or. .not. allocated(grid%gphiv)) &
+         call gocean_stop('momentum_coriolis: grid_init has not been called for this grid')
+    if (.not. allocated(grid%fcor_u)) allocate(grid%fcor_u(grid%nx, grid%ny), grid%fcor_v(grid%nx, grid%ny))
+    grid%fcor_u = (2.0_go_wp * omega) * sin(grid%gphiu * d2r)
+    grid%fcor_v = (2.0_go_wp * omega) * sin(grid%gphiv * d2r)
+    nb = int(grid%nx, c_size_t) * int(grid%ny, c_size_t) * 8_c_size_t
+    if (.not. c_associated(grid%fcor_u_device)) then
+       if (hipMalloc(grid%fcor_u_device, nb) /= 0) call gocean_stop('momentum_coriolis: hipMalloc failed')
+    end if
+    if (.not. c_associated(grid%fcor_v_device)) then
+       if (hipMalloc(grid%fcor_v_device, nb) /= 0) call gocean_stop('momentum_coriolis: hipMalloc failed')
+    end if
+    if (hipMemcpy(grid%fcor_u_device, c_loc(grid%fcor_u), nb, 1_c_int) /= 0 .or. &
+        hipMemcpy(grid%fcor_v_device, c_loc(grid%fcor_v), nb, 1_c_int) /= 0) &
+         call gocean_stop('momentum_coriolis: upload failed')
+  end subroutine momentum_coriolis
+
+  !> the grid's device mirrors as a dlesm_momentum_grid; stops when momentum_coriolis was never called for the grid
+  function momentum_grid(grid, who) result(mg)
+    type(grid_type), intent(inout), target :: grid
+    character(len=*), intent(in) :: who
+    type(c_momentum_grid) :: mg
+    if (.not. c_associated(grid%fcor_u_device) .or. .not. c_associated(grid%fcor_v_device)) &
+         call gocean_stop(who // ': the Coriolis parameter of this grid has not been set: call momentum_coriolis first')
+    call grid_to_device(grid)
+    mg = c_momentum_grid(grid%tmask_device, grid%dx_t_device, grid%dy_t_device, grid%dx_u_device, grid%dy_u_device, &
+                         grid%dx_v_device, grid%dy_v_device, grid%area_u_device, grid%area_v_device, &
+                         grid%fcor_u_device, grid%fcor_v_device)
+  end function momentum_grid
+
+  !> momentum_u (DESIGN.md section 6.5) over ua%internal: ua where both T cells of the u face are wet.  The
+  !! kernel gets the grid's metric mirrors and the Coriolis parameter momentum_coriolis set.
+  subroutine invoke_momentum_u(params, ua, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u)
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: ua, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u
+    type(c_momentum_grid) :: mg
+    integer(c_int) :: rc
+    call need_device(ua);  call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(sshn_t)
+    call need_device(hu);  call need_device(sshn_u);  call need_device(hv);  call need_device(sshn_v)
+    call need_device(ssha_u)
+    mg = momentum_grid(ua%grid, 'invoke_momentum_u')
+    rc = dlesm_momentum_u_f64(params, mg, int(ua%grid%nx, c_int), int(ua%grid%ny, c_int), &
+                              int(ua%internal%xstart, c_int), int(ua%internal%xstop, c_int), &
+                              int(ua%internal%ystart, c_int), int(ua%internal%ystop, c_int), &
+                              field_device_data(un), field_device_data(vn), field_device_data(ht), field_device_data(sshn_t), &
+                              field_device_data(hu), field_device_data(sshn_u), field_device_data(hv), &
+                              field_device_data(sshn_v), field_device_data(ssha_u), field_device_data(ua), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_momentum_u: ' // dlesm_error_text())
+  end subroutine invoke_momentum_u
+
+  !> momentum_v (DESIGN.md section 6.5) over va%internal: va where both T cells of the v face are wet
+  subroutine invoke_momentum_v(params, va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_v)
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_v
+    type(c_momentum_grid) :: mg
+    integer(c_int) :: rc
+    call need_device(va);  call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(sshn_t)
+    call need_device(hu);  call need_device(sshn_u);  call need_device(hv);  call need_device(sshn_v)
+    call need_device(ssha_v)
+    mg = momentum_grid(va%grid, 'invoke_momentum_v')
+    rc = dlesm_momentum_v_f64(params, mg, int(va%grid%nx, c_int), int(va%grid%ny, c_int), &
+                              int(va%internal%xstart, c_int), int(va%internal%xstop, c_int), &
+                              int(va%internal%ystart, c_int), int(va%internal%ystop, c_int), &
+                              field_device_data(un), field_device_data(vn), field_device_data(ht), field_device_data(sshn_t), &
+                              field_device_data(hu), field_device_data(sshn_u), field_device_data(hv), &
+                              field_device_data(sshn_v), field_device_data(ssha_v), field_device_data(va), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_momentum_v: ' // dlesm_error_text())
+  end subroutine invoke_momentum_v
+
+  !> Both momentum loop nests in one sweep: momentum_u over ua%internal and momentum_v over va%internal, bit for
+  !! bit invoke_momentum_u followed by invoke_momentum_v, at 180 instead of 2 x 140 B/cell.
+  subroutine invoke_momentum(params, ua, va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ssha_v)
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: ua, va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ssha_v
+    type(c_momentum_grid) :: mg
+    type(c_region) :: ubox, vbox
+    integer(c_int) :: rc
+    call need_device(ua);  call need_device(va);  call need_device(un);  call need_device(vn);  call need_device(ht)
+    call need_device(sshn_t);  call need_device(hu);  call need_device(sshn_u);  call need_device(hv)
+    call need_device(sshn_v);  call need_device(ssha_u);  call need_device(ssha_v)
+    mg = momentum_grid(ua%grid, 'invoke_momentum')
+    ubox = c_region(ua%internal%nx, ua%internal%ny, ua%internal%xstart, ua%internal%xstop, &
+                    ua%internal%ystart, ua%internal%ystop)
+    vbox = c_region(va%internal%nx, va%internal%ny, va%internal%xstart, va%internal%xstop, &
+                    va%internal%ystart, va%internal%ystop)
+    rc = dlesm_momentum_f64(params, mg, int(ua%grid%nx, c_int), int(ua%grid%ny, c_int), ubox, vbox, &
+                            field_device_data(un), field_device_data(vn), field_device_data(ht), field_device_data(sshn_t), &
+                            field_device_data(hu), field_device_data(sshn_u), field_device_data(hv), &
+                            field_device_data(sshn_v), field_device_data(ssha_u), field_device_data(ssha_v), &
+                            field_device_data(ua), field_device_data(va), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_momentum: ' // dlesm_error_text())
+  end subroutine invoke_momentum
+
+  !> next_sshu (DESIGN.md section 6.5) over sshn_u%internal, from sshn_t and the grid's tmask, area_t and area_u
+  subroutine invoke_next_sshu(sshn_u, sshn_t)
+    type(r2d_field), intent(inout), target :: sshn_u, sshn_t
+    integer(c_int) :: rc
+    call need_device(sshn_u);  call need_device(sshn_t)
+    call grid_to_device(sshn_u%grid)
+    rc = dlesm_next_sshu_f64(int(sshn_u%grid%nx, c_int), int(sshn_u%grid%ny, c_int), &
+                             int(sshn_u%internal%xstart, c_int), int(sshn_u%internal%xstop, c_int), &
+                             int(sshn_u%internal%ystart, c_int), int(sshn_u%internal%ystop, c_int), &
+                             sshn_u%grid%tmask_device, sshn_u%grid%area_t_device, sshn_u%grid%area_u_device, &
+                             field_device_data(sshn_t), field_device_data(sshn_u), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_next_sshu: ' // dlesm_error_text())
+  end subroutine invoke_next_sshu
+
+  !> next_sshv (DESIGN.md section 6.5) over sshn_v%internal, from sshn_t and the grid's tmask, area_t and area_v
+  subroutine invoke_next_sshv(sshn_v, sshn_t)
+    type(r2d_field), intent(inout), target :: sshn_v, sshn_t
+    integer(c_int) :: rc
+    call need_device(sshn_v);  call need_device(sshn_t)
+    call grid_to_device(sshn_v%grid)
+    rc = dlesm_next_sshv_f64(int(sshn_v%grid%nx, c_int), int(sshn_v%grid%ny, c_int), &
+                             int(sshn_v%internal%xstart, c_int), int(sshn_v%internal%xstop, c_int), &
+                             int(sshn_v%internal%ystart, c_int), int(sshn_v%internal%ystop, c_int), &
+                             sshn_v%grid%tmask_device, sshn_v%grid%area_t_device, sshn_v%grid%area_v_device, &
+                             field_device_data(sshn_t), field_device_data(sshn_v), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_next_sshv: ' // dlesm_error_text())
+  end subroutine invoke_next_sshv
 
   !> Optional planning call (once per field geometry, outside the time loop): lets the library time
   !! its launch shapes for invoke_jacobi5 / invoke_jacobi5_dm on these fields and keep the fastest.

@@ -12,7 +12,9 @@ GO_BC_PERIODIC, GO_BC_EXTERNAL, GO_BC_NONE = 0, 1, 2
 class grid_type:
     """grid_type (grid_mod.f90:75-157): only what the hot path touches -- extents,
     decomposition, spacing and the halo-exchange tables.  The 16 metric arrays of the
-    reference are constant fills (grid_mod.f90:479-556) and are not materialised here."""
+    reference are constant fills (grid_mod.f90:479-556): the ones a kernel reads exist as device
+    mirrors made on first use (tmask_device, area_t_device, dx_t_device ... area_v_device), the
+    latitudes of u and v points as host arrays (gphiu, gphiv)."""
 
     def __init__(self, grid_name, boundary_conditions, grid_offsets=None):
         if grid_offsets is None:
@@ -37,6 +39,9 @@ class grid_type:
         self.tmask = None              # host copy, (ny, nx) int32 (grid_mod.f90:100)
         self._tmask_device = None      # its HBM mirror (grid_mod.f90:104-106), made on first use
         self._area_t_device = None
+        self._metric_device = {}       # the other metric mirrors, made on first use (_metric_mirror)
+        self.gphiu = self.gphiv = None # host latitudes of u and v points (grid_mod.f90:512-523)
+        self.fcor = None               # (omega, d2r, fcor_u, fcor_v device tensors): psy.coriolis, once per grid
 
     @property
     def tmask_device(self):
@@ -64,6 +69,26 @@ class grid_type:
             self._area_t_device = torch.full((self.ny, self.nx), self.dx * self.dy, dtype=torch.float64, device="cuda")
             torch.cuda.current_stream().synchronize()      # in place before a kernel on another stream reads it
         return self._area_t_device
+
+    def _metric_mirror(self, name, value):
+        """device mirror of a metric array grid_init fills with a constant on a regular grid (grid_mod.f90:104-150)"""
+        if name not in self._metric_device:
+            import torch
+            if not self.nx:
+                raise _cabi.GoceanStop(_cabi.EABORT, f"grid%{name} requested before grid_init")
+            self._metric_device[name] = torch.full((self.ny, self.nx), value, dtype=torch.float64, device="cuda")
+            torch.cuda.current_stream().synchronize()      # in place before a kernel on another stream reads it
+        return self._metric_device[name]
+
+    # device mirrors of grid%dx_t ... grid%area_v, (ny, nx) float64 tensors filled as grid_init fills the arrays
+    dx_t_device = property(lambda self: self._metric_mirror("dx_t", self.dx))
+    dy_t_device = property(lambda self: self._metric_mirror("dy_t", self.dy))
+    dx_u_device = property(lambda self: self._metric_mirror("dx_u", self.dx))
+    dy_u_device = property(lambda self: self._metric_mirror("dy_u", self.dy))
+    dx_v_device = property(lambda self: self._metric_mirror("dx_v", self.dx))
+    dy_v_device = property(lambda self: self._metric_mirror("dy_v", self.dy))
+    area_u_device = property(lambda self: self._metric_mirror("area_u", self.dx * self.dy))
+    area_v_device = property(lambda self: self._metric_mirror("area_v", self.dx * self.dy))
 
     def decompose(self, domainx, domainy, ndomains=None, ndomainx=None, ndomainy=None, halo_width=1):
         """grid_mod.f90:183-211"""
@@ -93,6 +118,11 @@ def grid_init(grid, dxarg, dyarg, tmask=None):
     grid.tmask = _make_tmask(grid, tmask)
     grid._tmask_device = None
     grid._area_t_device = None
+    grid._metric_device = {}
+    import numpy as np
+    grid.gphiu = np.full((grid.ny, grid.nx), 50.0)         # the reference's f-plane (grid_mod.f90:512-523)
+    grid.gphiv = np.full((grid.ny, grid.nx), 50.0)
+    grid.fcor = None
     if nranks > 1:
         if periodic:                                       # grid_mod.f90:559-564
             raise _cabi.GoceanStop(_cabi.EABORT, "map_comms call needs to be implemented for "

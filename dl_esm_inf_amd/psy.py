@@ -3,6 +3,7 @@
 infrastructure_mod.f90:32-41) becomes one launch of the matching HIP kernel over the same
 index box."""
 import ctypes as C
+import math
 
 from . import _cabi, grid_mod
 from ._cabi import SwParams, check
@@ -47,6 +48,85 @@ def invoke_continuity(ssha, sshn_t, sshn_u, sshn_v, hu, hv, un, vn, rdt, stream=
                                            sshn_t.device_ptr, sshn_u.device_ptr, sshn_v.device_ptr, hu.device_ptr,
                                            hv.device_ptr, un.device_ptr, vn.device_ptr,
                                            C.c_void_p(g.area_t_device.data_ptr()), ssha.device_ptr, _stream_ptr(stream)))
+
+
+def momentum_params(rdt, cbfr, visc, g):
+    """constants of the momentum kernels: time step, bottom friction, viscosity, gravity"""
+    return _cabi.MomentumParams(rdt=float(rdt), cbfr=float(cbfr), visc=float(visc), g=float(g))
+
+
+def coriolis(grid, omega=7.292116e-5, d2r=math.pi / 180.0):
+    """the Coriolis parameter of the momentum kernels, once per grid: fcor_u = (2*omega)*sin(gphiu*d2r) and fcor_v from
+    gphiv, computed on the host with the host's sin and uploaded.  Returns (fcor_u, fcor_v), the
+    device tensors; a second call with the same constants returns the cached pair."""
+    import numpy as np
+    import torch
+    if grid.gphiu is None:
+        raise _cabi.GoceanStop(_cabi.EABORT, "coriolis: grid%gphiu requested before grid_init")
+    if grid.fcor is not None and grid.fcor[0] == omega and grid.fcor[1] == d2r:
+        return grid.fcor[2], grid.fcor[3]
+    fu, fv = ((2.0 * omega) * np.sin(gphi * d2r) for gphi in (grid.gphiu, grid.gphiv))
+    fu, fv = torch.from_numpy(np.ascontiguousarray(fu)).cuda(), torch.from_numpy(np.ascontiguousarray(fv)).cuda()
+    torch.cuda.current_stream().synchronize()              # in place before a kernel on another stream reads them
+    grid.fcor = (omega, d2r, fu, fv)
+    return fu, fv
+
+
+def _momentum_grid(g, who):
+    """the grid's device mirrors as a dlesm_momentum_grid; refuses a grid whose Coriolis parameter was never set"""
+    if g.fcor is None:
+        raise _cabi.GoceanStop(_cabi.EABORT, f"{who}: the Coriolis parameter of this grid has not been set: call "
+                                             "psy.coriolis(grid) once before the momentum kernels")
+    mg = _cabi.MomentumGrid()
+    for name in _cabi.MOMENTUM_GRID_ARRAYS:
+        t = g.fcor[2 if name == "fcor_u" else 3] if name.startswith("fcor") else getattr(g, name + "_device")
+        setattr(mg, name, t.data_ptr())
+    return mg
+
+
+def invoke_momentum_u(params, ua, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, stream=None):
+    """momentum_u over ua%internal: ua where both T cells of the u face are wet"""
+    g, it = ua.grid, ua.internal
+    mg = _momentum_grid(g, "invoke_momentum_u")
+    check(_cabi.lib().dlesm_momentum_u_f64(C.byref(params), C.byref(mg), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
+                                           *[f.device_ptr for f in (un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ua)],
+                                           _stream_ptr(stream)))
+
+
+def invoke_momentum_v(params, va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_v, stream=None):
+    """momentum_v over va%internal: va where both T cells of the v face are wet"""
+    g, it = va.grid, va.internal
+    mg = _momentum_grid(g, "invoke_momentum_v")
+    check(_cabi.lib().dlesm_momentum_v_f64(C.byref(params), C.byref(mg), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
+                                           *[f.device_ptr for f in (un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_v, va)],
+                                           _stream_ptr(stream)))
+
+
+def invoke_momentum(params, ua, va, un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ssha_v, stream=None):
+    """both momentum loop nests in one sweep: momentum_u over ua%internal and momentum_v over va%internal, bit for bit
+    invoke_momentum_u then invoke_momentum_v, at 180 instead of 2 x 140 B/cell"""
+    g = ua.grid
+    mg = _momentum_grid(g, "invoke_momentum")
+    check(_cabi.lib().dlesm_momentum_f64(C.byref(params), C.byref(mg), g.nx, g.ny, C.byref(ua.internal), C.byref(va.internal),
+                                         *[f.device_ptr for f in (un, vn, ht, sshn_t, hu, sshn_u, hv, sshn_v, ssha_u, ssha_v,
+                                                                  ua, va)],
+                                         _stream_ptr(stream)))
+
+
+def invoke_next_sshu(sshn_u, sshn_t, stream=None):
+    """next_sshu over sshn_u%internal: the grid's tmask, area_t and area_u mirrors"""
+    g, it = sshn_u.grid, sshn_u.internal
+    check(_cabi.lib().dlesm_next_sshu_f64(g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+                                          C.c_void_p(g.area_t_device.data_ptr()), C.c_void_p(g.area_u_device.data_ptr()),
+                                          sshn_t.device_ptr, sshn_u.device_ptr, _stream_ptr(stream)))
+
+
+def invoke_next_sshv(sshn_v, sshn_t, stream=None):
+    """next_sshv over sshn_v%internal: the grid's tmask, area_t and area_v mirrors"""
+    g, it = sshn_v.grid, sshn_v.internal
+    check(_cabi.lib().dlesm_next_sshv_f64(g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+                                          C.c_void_p(g.area_t_device.data_ptr()), C.c_void_p(g.area_v_device.data_ptr()),
+                                          sshn_t.device_ptr, sshn_v.device_ptr, _stream_ptr(stream)))
 
 
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):

@@ -277,6 +277,49 @@ int dlesm_continuity_f64(double rdt, int ld, int ny, int xstart, int xstop, int 
                          const double *hu, const double *hv, const double *un, const double *vn,
                          const double *area_t, double *ssha, void *stream);
 
+/* The momentum update and the interpolation of the sea-surface height onto u and v points of a NEMOLite2D-class model:
+ * the kernels that read the metric grid properties (GO_GRID_DX_U, GO_GRID_DY_U/V, GO_GRID_AREA_U/V and, through the
+ * Coriolis parameter, GO_GRID_LAT_U/V; argument_mod.f90:75-112).  Specification frozen in DESIGN.md section 6.5 (the
+ * reference holds none of these loops): NE offset, every operation rounded in double precision in the order the
+ * parentheses give.  Boxes are 1-based and inclusive and need a one-cell ring inside the array; a cell the rule does not
+ * write keeps its content, nothing outside the box is written.  No output may overlap any input, and ua may not overlap
+ * va (DLESM_EINVAL).  Constants of the time step: */
+typedef struct dlesm_momentum_params {
+    double rdt, cbfr, visc, g;
+} dlesm_momentum_params;
+/* Device copies of the grid properties the momentum kernels read, all with the field layout (tmask: int32).  fcor_u/v are
+ * the Coriolis parameter at u / v points, (2*omega)*sin(gphiu/v*d2r), computed on the host once per grid (DESIGN.md
+ * section 6.5).  A loop nest reads only the arrays its rule names; the others may be NULL. */
+typedef struct dlesm_momentum_grid {
+    const int *tmask;
+    const double *dx_t, *dy_t, *dx_u, *dy_u, *dx_v, *dy_v, *area_u, *area_v, *fcor_u, *fcor_v;
+} dlesm_momentum_grid;
+/* momentum_u over the box: ua(i,j) where tmask(i,j) > 0 and tmask(i+1,j) > 0.  140 B/cell. */
+int dlesm_momentum_u_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, int ld, int ny,
+                         int xstart, int xstop, int ystart, int ystop,
+                         const double *un, const double *vn, const double *ht, const double *sshn_t,
+                         const double *hu, const double *sshn_u, const double *hv, const double *sshn_v,
+                         const double *ssha_u, double *ua, void *stream);
+/* momentum_v over the box: va(i,j) where tmask(i,j) > 0 and tmask(i,j+1) > 0.  140 B/cell. */
+int dlesm_momentum_v_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, int ld, int ny,
+                         int xstart, int xstop, int ystart, int ystop,
+                         const double *un, const double *vn, const double *ht, const double *sshn_t,
+                         const double *hu, const double *sshn_u, const double *hv, const double *sshn_v,
+                         const double *ssha_v, double *va, void *stream);
+/* Both loop nests in one sweep: bit for bit dlesm_momentum_u_f64 over ubox (the U-point internal
+ * region) followed by dlesm_momentum_v_f64 over vbox (the V-point internal region).  180 B/cell instead of 2 x 140. */
+int dlesm_momentum_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, int ld, int ny,
+                       const dlesm_region *ubox, const dlesm_region *vbox,
+                       const double *un, const double *vn, const double *ht, const double *sshn_t,
+                       const double *hu, const double *sshn_u, const double *hv, const double *sshn_v,
+                       const double *ssha_u, const double *ssha_v, double *ua, double *va, void *stream);
+/* next_sshu / next_sshv: the sea-surface height at u (v) points from sshn_t, area-weighted where
+ * both T cells are wet, the wet side's value on a coast, unwritten between two dry cells. */
+int dlesm_next_sshu_f64(int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
+                        const double *area_t, const double *area_u, const double *sshn_t, double *sshn_u, void *stream);
+int dlesm_next_sshv_f64(int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
+                        const double *area_t, const double *area_v, const double *sshn_t, double *sshn_v, void *stream);
+
 /* Shallow-water u/v/h update: reads u,v,p (3x3 footprint)
  * and uold,vold,pold, writes unew,vnew,pnew on the box. */
 typedef struct dlesm_sw_params {
