@@ -136,6 +136,13 @@ PROTOTYPES = {
                            [_vp] * 12 + [_vp]),
     "dlesm_next_sshu_f64": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
     "dlesm_next_sshv_f64": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
+    "dlesm_obc_create": (_i, [_vp, _i, _i, C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), C.POINTER(_vp)]),
+    "dlesm_obc_destroy": (_i, [_vp]),
+    "dlesm_obc_counts": (_i, [_vp, _pi, _pi, _pi]),
+    "dlesm_bc_ssh_f64": (_i, [_vp, _d, _vp, _vp]),
+    "dlesm_bc_flather_u_f64": (_i, [_vp, C.POINTER(MomentumParams)] + [_vp] * 4 + [_vp]),
+    "dlesm_bc_flather_v_f64": (_i, [_vp, C.POINTER(MomentumParams)] + [_vp] * 4 + [_vp]),
+    "dlesm_bc_open_f64": (_i, [_vp, C.POINTER(MomentumParams), _d] + [_vp] * 8 + [_vp]),
     "dlesm_stencil9_f64": (_i, [_vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil9_step_dm": (_i, [_vp, _vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil5_masked_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -52,6 +52,8 @@ module grid_mod
      !> Coriolis parameter at u / v points, (2*omega)*sin(gphiu/v*d2r): set by momentum_coriolis (dlesm_psy_mod)
      real(go_wp), allocatable :: fcor_u(:,:), fcor_v(:,:)
      type(c_ptr) :: fcor_u_device, fcor_v_device
+     !> the open-boundary plan (dlesm_obc, DESIGN.md section 6.6): made by open_boundary (dlesm_psy_mod) once per grid
+     type(c_ptr) :: obc
      real(go_wp), allocatable :: xt(:,:), yt(:,:)
      type(c_ptr) :: xt_device, yt_device
    contains
@@ -118,6 +120,7 @@ contains
     self%gphiu_device = c_null_ptr;  self%gphiv_device = c_null_ptr
     self%gphif_device = c_null_ptr
     self%fcor_u_device = c_null_ptr;  self%fcor_v_device = c_null_ptr
+    self%obc = c_null_ptr
     self%xt_device = c_null_ptr;  self%yt_device = c_null_ptr
   end function grid_constructor
 

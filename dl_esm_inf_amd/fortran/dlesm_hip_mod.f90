@@ -236,6 +236,58 @@ module dlesm_hip_mod
        type(c_ptr), value :: tmask, area_t, area_v, sshn_t, sshn_v, stream
        integer(c_int) :: rc
      end function
+     ! ---- open boundary: bc_ssh and Flather (DESIGN.md section 6.6)
+     function dlesm_obc_create(tmask_host, ld, ny, tbox, ubox, vbox, plan) bind(C, name="dlesm_obc_create") result(rc)
+       import :: c_int, c_ptr, c_region
+       type(c_ptr), value :: tmask_host
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: tbox, ubox, vbox
+       type(c_ptr), intent(out) :: plan
+       integer(c_int) :: rc
+     end function
+     function dlesm_obc_destroy(plan) bind(C, name="dlesm_obc_destroy") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+       integer(c_int) :: rc
+     end function
+     function dlesm_obc_counts(plan, nt, nu, nv) bind(C, name="dlesm_obc_counts") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+       integer(c_int), intent(out) :: nt, nu, nv
+       integer(c_int) :: rc
+     end function
+     function dlesm_bc_ssh_f64(plan, ssh_bc, ssha, stream) bind(C, name="dlesm_bc_ssh_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: plan
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: ssha, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_bc_flather_u_f64(plan, params, hu, sshn_u, sshn_t, ua, stream) bind(C, name="dlesm_bc_flather_u_f64") &
+          result(rc)
+       import :: c_int, c_ptr, c_momentum_params
+       type(c_ptr), value :: plan
+       type(c_momentum_params), intent(in) :: params
+       type(c_ptr), value :: hu, sshn_u, sshn_t, ua, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_bc_flather_v_f64(plan, params, hv, sshn_v, sshn_t, va, stream) bind(C, name="dlesm_bc_flather_v_f64") &
+          result(rc)
+       import :: c_int, c_ptr, c_momentum_params
+       type(c_ptr), value :: plan
+       type(c_momentum_params), intent(in) :: params
+       type(c_ptr), value :: hv, sshn_v, sshn_t, va, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_bc_open_f64(plan, params, ssh_bc, hu, sshn_u, hv, sshn_v, sshn_t, ssha, ua, va, stream) &
+          bind(C, name="dlesm_bc_open_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_momentum_params
+       type(c_ptr), value :: plan
+       type(c_momentum_params), intent(in) :: params
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: hu, sshn_u, hv, sshn_v, sshn_t, ssha, ua, va, stream
+       integer(c_int) :: rc
+     end function
      function dlesm_stencil5_masked_f64(in, out, tmask, ld, ny, xstart, xstop, ystart, ystop, stream) &
           bind(C, name="dlesm_stencil5_masked_f64") result(rc)
        import :: c_int, c_ptr

@@ -53,6 +53,7 @@ module dlesm_psy_mod
   public :: invoke_shallow_step_dm_pipelined, invoke_continuity
   public :: momentum_params, c_momentum_params, momentum_coriolis, invoke_momentum_u, invoke_momentum_v, invoke_momentum
   public :: invoke_next_sshu, invoke_next_sshv
+  public :: open_boundary, tide_ssh, invoke_bc_ssh, invoke_bc_flather_u, invoke_bc_flather_v, invoke_bc_open
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -313,6 +314,88 @@ contains
                              field_device_data(sshn_t), field_device_data(sshn_v), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_next_sshv: ' // dlesm_error_text())
   end subroutine invoke_next_sshv
+
+  !> The open-boundary plan of a grid (DESIGN.md section 6.6), made once from the host tmask and the T-, U- and V-point
+  !! internal regions: the lists of open T cells, open u faces and open v faces.  Stops if the library refuses the mask (an
+  !! open face whose inner face is open -- a wet region one cell wide between two open cells -- or lies at the edge of the
+  !! array).
+  function open_boundary(grid) result(plan)
+    type(grid_type), intent(inout), target :: grid
+    type(c_ptr) :: plan
+    type(c_region) :: sub, box(3), whole
+    integer, parameter :: pts(3) = (/GO_T_POINTS, GO_U_POINTS, GO_V_POINTS/)
+    integer :: k
+    integer(c_int) :: rc
+    if (.not. c_associated(grid%obc)) then
+       if (.not. allocated(grid%tmask)) call gocean_stop('open_boundary: grid_init has not been called for this grid')
+       associate (s => grid%subdomain%internal)
+         sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+       end associate
+       do k = 1, 3                    ! the internal regions of T, U and V fields (set_field_bounds)
+          rc = dlesm_field_bounds(int(pts(k), c_int), int(grid%offset, c_int), int(grid%boundary_conditions(1), c_int), &
+                                  int(grid%boundary_conditions(2), c_int), sub, int(grid%nx, c_int), int(grid%ny, c_int), &
+                                  box(k), whole)
+          if (rc /= 0) call gocean_stop('open_boundary: ' // dlesm_error_text())
+       end do
+       rc = dlesm_obc_create(c_loc(grid%tmask), int(grid%nx, c_int), int(grid%ny, c_int), box(1), box(2), box(3), grid%obc)
+       if (rc /= 0) call gocean_stop('open_boundary: ' // dlesm_error_text())
+    end if
+    plan = grid%obc
+  end function open_boundary
+
+  !> The boundary sea-surface height of bc_ssh, amp*sin(omega*t), with the host's sin (DESIGN.md section 6.6)
+  function tide_ssh(amp, omega, t) result(ssh_bc)
+    real(go_wp), intent(in) :: amp, omega, t
+    real(go_wp) :: ssh_bc
+    ssh_bc = amp * sin(omega * t)
+  end function tide_ssh
+
+  !> bc_ssh (DESIGN.md section 6.6): ssha = ssh_bc on the open T cells of ssha%internal
+  subroutine invoke_bc_ssh(ssha, ssh_bc)
+    type(r2d_field), intent(inout), target :: ssha
+    real(go_wp), intent(in) :: ssh_bc
+    integer(c_int) :: rc
+    call need_device(ssha)
+    rc = dlesm_bc_ssh_f64(open_boundary(ssha%grid), real(ssh_bc, c_double), field_device_data(ssha), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_bc_ssh: ' // dlesm_error_text())
+  end subroutine invoke_bc_ssh
+
+  !> Flather on the open u faces of ua%internal (DESIGN.md section 6.6), ua in place
+  subroutine invoke_bc_flather_u(params, ua, hu, sshn_u, sshn_t)
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: ua, hu, sshn_u, sshn_t
+    integer(c_int) :: rc
+    call need_device(ua);  call need_device(hu);  call need_device(sshn_u);  call need_device(sshn_t)
+    rc = dlesm_bc_flather_u_f64(open_boundary(ua%grid), params, field_device_data(hu), field_device_data(sshn_u), &
+                                field_device_data(sshn_t), field_device_data(ua), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_bc_flather_u: ' // dlesm_error_text())
+  end subroutine invoke_bc_flather_u
+
+  !> Flather on the open v faces of va%internal (DESIGN.md section 6.6), va in place
+  subroutine invoke_bc_flather_v(params, va, hv, sshn_v, sshn_t)
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: va, hv, sshn_v, sshn_t
+    integer(c_int) :: rc
+    call need_device(va);  call need_device(hv);  call need_device(sshn_v);  call need_device(sshn_t)
+    rc = dlesm_bc_flather_v_f64(open_boundary(va%grid), params, field_device_data(hv), field_device_data(sshn_v), &
+                                field_device_data(sshn_t), field_device_data(va), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_bc_flather_v: ' // dlesm_error_text())
+  end subroutine invoke_bc_flather_v
+
+  !> bc_ssh, Flather on u and Flather on v in one launch, bit for bit the three separate wrappers (DESIGN.md section 6.6)
+  subroutine invoke_bc_open(params, ssh_bc, ssha, ua, va, hu, sshn_u, hv, sshn_v, sshn_t)
+    type(c_momentum_params), intent(in) :: params
+    real(go_wp), intent(in) :: ssh_bc
+    type(r2d_field), intent(inout), target :: ssha, ua, va, hu, sshn_u, hv, sshn_v, sshn_t
+    integer(c_int) :: rc
+    call need_device(ssha);  call need_device(ua);  call need_device(va);  call need_device(hu);  call need_device(sshn_u)
+    call need_device(hv);  call need_device(sshn_v);  call need_device(sshn_t)
+    rc = dlesm_bc_open_f64(open_boundary(ssha%grid), params, real(ssh_bc, c_double), field_device_data(hu), &
+                           field_device_data(sshn_u), field_device_data(hv), field_device_data(sshn_v), &
+                           field_device_data(sshn_t), field_device_data(ssha), field_device_data(ua), &
+                           field_device_data(va), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_bc_open: ' // dlesm_error_text())
+  end subroutine invoke_bc_open
 
   !> Optional planning call (once per field geometry, outside the time loop): lets the library time
   !! its launch shapes for invoke_jacobi5 / invoke_jacobi5_dm on these fields and keep the fastest.

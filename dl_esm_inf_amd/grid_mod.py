@@ -42,6 +42,7 @@ class grid_type:
         self._metric_device = {}       # the other metric mirrors, made on first use (_metric_mirror)
         self.gphiu = self.gphiv = None # host latitudes of u and v points (grid_mod.f90:512-523)
         self.fcor = None               # (omega, d2r, fcor_u, fcor_v device tensors): psy.coriolis, once per grid
+        self._obc = None               # the open-boundary plan (dlesm_obc): psy.open_boundary, once per grid
 
     @property
     def tmask_device(self):
@@ -123,6 +124,9 @@ def grid_init(grid, dxarg, dyarg, tmask=None):
     grid.gphiu = np.full((grid.ny, grid.nx), 50.0)         # the reference's f-plane (grid_mod.f90:512-523)
     grid.gphiv = np.full((grid.ny, grid.nx), 50.0)
     grid.fcor = None
+    if grid._obc is not None:                              # made from the previous mask
+        check(L.dlesm_obc_destroy(grid._obc.handle))
+        grid._obc = None
     if nranks > 1:
         if periodic:                                       # grid_mod.f90:559-564
             raise _cabi.GoceanStop(_cabi.EABORT, "map_comms call needs to be implemented for "

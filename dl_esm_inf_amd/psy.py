@@ -129,6 +129,67 @@ def invoke_next_sshv(sshn_v, sshn_t, stream=None):
                                           sshn_t.device_ptr, sshn_v.device_ptr, _stream_ptr(stream)))
 
 
+class OpenBoundary:
+    """the open-boundary plan of a grid (dlesm_obc): lists of the open T cells, u faces and v faces of
+    the T-, U- and V-point internal regions, in HBM.  Made by open_boundary(grid); grid_init releases it."""
+
+    def __init__(self, handle, nt, nu, nv):
+        self.handle, self.nt, self.nu, self.nv = handle, nt, nu, nv
+
+    def __repr__(self):
+        return f"OpenBoundary(open T cells {self.nt}, u faces {self.nu}, v faces {self.nv})"
+
+
+def open_boundary(grid):
+    """the grid's open-boundary plan, built once per grid from its host tmask and the T/U/V internal regions (DESIGN.md
+    section 6.6).  A mask the plan refuses (an open face whose inner face is open, or lies at the edge of the array) stops
+    with GoceanStop."""
+    if grid._obc is None:
+        from .field_mod import GO_T_POINTS, GO_U_POINTS, GO_V_POINTS, field_bounds
+        if grid.tmask is None:
+            raise _cabi.GoceanStop(_cabi.EABORT, "open_boundary: grid%tmask requested before grid_init")
+        import numpy as np
+        tm = np.ascontiguousarray(grid.tmask, dtype=np.int32)
+        boxes = [field_bounds(grid, p)[0] for p in (GO_T_POINTS, GO_U_POINTS, GO_V_POINTS)]
+        h = C.c_void_p()
+        rc = _cabi.lib().dlesm_obc_create(tm.ctypes.data, grid.nx, grid.ny, *[C.byref(b) for b in boxes], C.byref(h))
+        if rc != 0:
+            raise _cabi.GoceanStop(_cabi.EABORT, "open_boundary: " + _cabi.lib().dlesm_last_error().decode())
+        n = [C.c_int() for _ in range(3)]
+        check(_cabi.lib().dlesm_obc_counts(h, *[C.byref(x) for x in n]))
+        grid._obc = OpenBoundary(h, *[x.value for x in n])
+    return grid._obc
+
+
+def tide_ssh(amp, omega, t):
+    """the boundary sea-surface height of bc_ssh, amp*sin(omega*t), with the host's sin"""
+    return float(amp) * math.sin(float(omega) * float(t))
+
+
+def invoke_bc_ssh(ssha, ssh_bc, stream=None):
+    """bc_ssh: ssha = ssh_bc on the open T cells of ssha%internal"""
+    check(_cabi.lib().dlesm_bc_ssh_f64(open_boundary(ssha.grid).handle, float(ssh_bc), ssha.device_ptr, _stream_ptr(stream)))
+
+
+def invoke_bc_flather_u(params, ua, hu, sshn_u, sshn_t, stream=None):
+    """Flather on the open u faces of ua%internal, ua in place"""
+    check(_cabi.lib().dlesm_bc_flather_u_f64(open_boundary(ua.grid).handle, C.byref(params), hu.device_ptr, sshn_u.device_ptr,
+                                             sshn_t.device_ptr, ua.device_ptr, _stream_ptr(stream)))
+
+
+def invoke_bc_flather_v(params, va, hv, sshn_v, sshn_t, stream=None):
+    """Flather on the open v faces of va%internal, va in place"""
+    check(_cabi.lib().dlesm_bc_flather_v_f64(open_boundary(va.grid).handle, C.byref(params), hv.device_ptr, sshn_v.device_ptr,
+                                             sshn_t.device_ptr, va.device_ptr, _stream_ptr(stream)))
+
+
+def invoke_bc_open(params, ssh_bc, ssha, ua, va, hu, sshn_u, hv, sshn_v, sshn_t, stream=None):
+    """bc_ssh, Flather on u and Flather on v in one launch, bit for bit the three separate calls"""
+    check(_cabi.lib().dlesm_bc_open_f64(open_boundary(ssha.grid).handle, C.byref(params), float(ssh_bc),
+                                        *[f.device_ptr for f in (hu, sshn_u, hv, sshn_v, sshn_t, ssha, ua, va)],
+                                        _stream_ptr(stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

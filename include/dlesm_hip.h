@@ -320,6 +320,36 @@ int dlesm_next_sshu_f64(int ld, int ny, int xstart, int xstop, int ystart, int y
 int dlesm_next_sshv_f64(int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
                         const double *area_t, const double *area_v, const double *sshn_t, double *sshn_v, void *stream);
 
+/* The open boundary of a NEMOLite2D-class model: bc_ssh, the tidal sea-surface height on open T cells,
+ * and the Flather condition on u and v faces.  "Open" is tmask < 0, "wet" tmask > 0.  A plan holds three lists of linear
+ * indices in HBM, made once per grid from the host mask: the open T cells of tbox, the open u faces of ubox and the open v
+ * faces of vbox (a face is open when one of its two T cells is open and the other wet), each face with its inner face (across
+ * the wet cell) and its open T cell.  Boxes are 1-based and inclusive; ubox and vbox need a one-cell ring inside the array,
+ * an empty box gives an empty list.  Refused with DLESM_EINVAL: a box that does not fit, an open face whose inner face or
+ * either of that face's T cells lies outside the array, and an open face whose inner face is itself open (a wet region one
+ * cell wide between two open cells).  A mask with no open cell gives empty lists, and the entries below then launch nothing. */
+typedef struct dlesm_obc dlesm_obc;
+int dlesm_obc_create(const int *tmask_host, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                     const dlesm_region *vbox, dlesm_obc **plan);
+int dlesm_obc_destroy(dlesm_obc *plan);
+/* the lengths of the plan's three lists (host only) */
+int dlesm_obc_counts(const dlesm_obc *plan, int *nt, int *nu, int *nv);
+/* bc_ssh: ssha = ssh_bc on every open T cell of the plan.  ssh_bc is a host scalar (amp*sin(omega*t), computed by the
+ * caller with the host's sin: the kernel evaluates no transcendental). */
+int dlesm_bc_ssh_f64(const dlesm_obc *plan, double ssh_bc, double *ssha, void *stream);
+/* Flather on the open u (v) faces of the plan, with c = sqrt(g/hu(i,j)) and g = params->g: open side west (south), inner face
+ * iu = i+1: ua(i,j) = ua(iu,j) - c*(sshn_u(iu,j) - sshn_t(o)); open side east (north), iu = i-1: ua(iu,j) + c*(...).
+ * ua is written in place; it may not overlap hu, sshn_u or sshn_t (DLESM_EINVAL). */
+int dlesm_bc_flather_u_f64(const dlesm_obc *plan, const dlesm_momentum_params *params, const double *hu, const double *sshn_u,
+                           const double *sshn_t, double *ua, void *stream);
+int dlesm_bc_flather_v_f64(const dlesm_obc *plan, const dlesm_momentum_params *params, const double *hv, const double *sshn_v,
+                           const double *sshn_t, double *va, void *stream);
+/* All three lists in one launch: bit for bit dlesm_bc_ssh_f64, dlesm_bc_flather_u_f64 and dlesm_bc_flather_v_f64.  No output
+ * may overlap an input, and ssha, ua and va may not overlap each other (DLESM_EINVAL). */
+int dlesm_bc_open_f64(const dlesm_obc *plan, const dlesm_momentum_params *params, double ssh_bc, const double *hu,
+                      const double *sshn_u, const double *hv, const double *sshn_v, const double *sshn_t, double *ssha,
+                      double *ua, double *va, void *stream);
+
 /* Shallow-water u/v/h update: reads u,v,p (3x3 footprint)
  * and uold,vold,pold, writes unew,vnew,pnew on the box. */
 typedef struct dlesm_sw_params {
