@@ -143,6 +143,8 @@ PROTOTYPES = {
     "dlesm_bc_flather_u_f64": (_i, [_vp, C.POINTER(MomentumParams)] + [_vp] * 4 + [_vp]),
     "dlesm_bc_flather_v_f64": (_i, [_vp, C.POINTER(MomentumParams)] + [_vp] * 4 + [_vp]),
     "dlesm_bc_open_f64": (_i, [_vp, C.POINTER(MomentumParams), _d] + [_vp] * 8 + [_vp]),
+    "dlesm_nemolite_step_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i, C.POINTER(Region),
+                                     C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
     "dlesm_stencil9_f64": (_i, [_vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil9_step_dm": (_i, [_vp, _vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil5_masked_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

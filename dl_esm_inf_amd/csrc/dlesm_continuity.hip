@@ -21,7 +21,7 @@
 // 2 columns x 2 rows swept linearly, like the other sweeps: the u-point operands at ji-1 come from the
 // neighbouring lane (lane 0 fetches the one column outside the wave), the v-point operands at jj-1
 // from the row loaded for the tile's row below.
-#include "dlesm_internal.h"
+#include "dlesm_nemolite.h"
 
 namespace dlesm {
 
@@ -29,14 +29,7 @@ namespace {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ double cont_point(double rdt, double st, double su, double su_w, double sv, double sv_s,
-                                             double hu, double hu_w, double hv, double hv_s, double un, double un_w,
-                                             double vn, double vn_s, double area)
-{
-    const double r1 = (su + hu) * un, r2 = (su_w + hu_w) * un_w;
-    const double r3 = (sv + hv) * vn, r4 = (sv_s + hv_s) * vn_s;
-    return st + (((r2 - r1) + r4) - r3) * rdt / area;
-}
+using nemo::cont_point;   // dlesm_nemolite.h
 
 struct ContFields {
     const double *sshn_t, *sshn_u, *sshn_v, *hu, *hv, *un, *vn, *area_t;

@@ -11,6 +11,13 @@
 #include "dlesm_error.h"
 #include "dlesm_hip.h"
 
+// the open-boundary plan (dlesm_open_bc.hip makes it; dlesm_nemolite_step.hip checks its extents)
+struct dlesm_obc {
+    int ld, ny;
+    int nt, nu, nv;   // open T cells, open u faces, open v faces
+    int *dev;         // one allocation: t[nt] | uf[nu] ui[nu] uo[nu] | vf[nv] vi[nv] vo[nv]; NULL when all lists are empty
+};
+
 namespace dlesm {
 
 #define DLESM_HIP_TRY(expr)                                                                 \

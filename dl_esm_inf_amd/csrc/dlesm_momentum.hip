@@ -14,7 +14,7 @@
 // next_ssh<DI, DJ>: the pointwise interpolation of the new surface height onto u (1,0) or v (0,1) points, 36 B/cell.
 #include <algorithm>
 
-#include "dlesm_internal.h"
+#include "dlesm_nemolite.h"
 
 namespace dlesm {
 
@@ -23,97 +23,12 @@ namespace {
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
 
-// the double-precision operands, by number
-enum { UN, VN, HT, SST, HU, SSU, HV, SSV, SAU, SAV, DXT, DYT, DXU, DYU, DXV, DYV, AU, AV, FU, FV, NF };
+using namespace nemo;   // the operands, MomArgs, Box and the point expressions mom_u / mom_v / ssh_point (dlesm_nemolite.h)
 
 // which operands each loop nest reads
 __host__ __device__ constexpr bool read_by_u(int f) { return f != SAV && f != DYV && f != AV && f != FV; }
 __host__ __device__ constexpr bool read_by_v(int f) { return f != SAU && f != DXU && f != AU && f != FU; }
 template <bool WU, bool WV> __host__ __device__ constexpr bool needed(int f) { return (WU && read_by_u(f)) || (WV && read_by_v(f)); }
-
-struct MomArgs {
-    const double *f[NF];
-    const int *tmask;
-    double *ua, *va;
-    double rdt, visc, g, den;                 // den = 1.0 + cbfr*rdt
-};
-
-struct Box {                                  // 0-based inclusive; empty: x0 > x1
-    int x0, x1, y0, y1;
-    __host__ __device__ bool has(int i, int j) const { return i >= x0 && i <= x1 && j >= y0 && j <= y1; }
-};
-
-__device__ __forceinline__ double sg(double x) { return copysign(0.5, x); }
-
-// ua(i,j) of DESIGN.md section 6.5.  X(f, di, dj) = operand f at (i+di, j+dj), T(di, dj) = tmask there.
-template <class XF, class TF>
-__device__ __forceinline__ double mom_u(const MomArgs &a, XF X, TF T)
-{
-    const bool sw = T(0, -1) > 0 && T(1, -1) > 0, nw = T(0, 1) > 0 && T(1, 1) > 0;
-    const double un = X(UN, 0, 0), hsu = X(HU, 0, 0) + X(SSU, 0, 0);
-    const double u_e = (0.5 * (un + X(UN, 1, 0))) * X(DYT, 1, 0);
-    const double depe = X(HT, 1, 0) + X(SST, 1, 0);
-    const double u_w = (0.5 * (un + X(UN, -1, 0))) * X(DYT, 0, 0);
-    const double depw = X(HT, 0, 0) + X(SST, 0, 0);
-    const double v_sc = 0.5 * (X(VN, 0, -1) + X(VN, 1, -1));
-    const double v_s = (0.5 * v_sc) * (X(DXV, 0, -1) + X(DXV, 1, -1));
-    const double deps = 0.5 * (((X(HV, 0, -1) + X(SSV, 0, -1)) + X(HV, 1, -1)) + X(SSV, 1, -1));
-    const double v_nc = 0.5 * (X(VN, 0, 0) + X(VN, 1, 0));
-    const double v_n = (0.5 * v_nc) * (X(DXV, 0, 0) + X(DXV, 1, 0));
-    const double depn = 0.5 * (((X(HV, 0, 0) + X(SSV, 0, 0)) + X(HV, 1, 0)) + X(SSV, 1, 0));
-    const double uu_w = (0.5 - sg(u_w)) * un + (0.5 + sg(u_w)) * X(UN, -1, 0);
-    const double uu_e = (0.5 + sg(u_e)) * un + (0.5 - sg(u_e)) * X(UN, 1, 0);
-    const double uu_s = sw ? (0.5 - sg(v_s)) * un + (0.5 + sg(v_s)) * X(UN, 0, -1) : (0.5 - sg(v_s)) * un;
-    const double uu_n = nw ? (0.5 + sg(v_n)) * un + (0.5 - sg(v_n)) * X(UN, 0, 1) : (0.5 + sg(v_n)) * un;
-    const double adv = (((uu_w * u_w) * depw - (uu_e * u_e) * depe) + (uu_s * v_s) * deps) - (uu_n * v_n) * depn;
-    const double dudx_e = ((X(UN, 1, 0) - un) / X(DXT, 1, 0)) * (X(HT, 1, 0) + X(SST, 1, 0));
-    const double dudx_w = ((un - X(UN, -1, 0)) / X(DXT, 0, 0)) * (X(HT, 0, 0) + X(SST, 0, 0));
-    const double dudy_s = sw ? ((un - X(UN, 0, -1)) / (X(DYU, 0, 0) + X(DYU, 0, -1))) *
-                                   ((hsu + X(HU, 0, -1)) + X(SSU, 0, -1))
-                             : 0.0;
-    const double dudy_n = nw ? ((X(UN, 0, 1) - un) / (X(DYU, 0, 0) + X(DYU, 0, 1))) *
-                                   ((hsu + X(HU, 0, 1)) + X(SSU, 0, 1))
-                             : 0.0;
-    const double vis = a.visc * ((dudx_e - dudx_w) * X(DYU, 0, 0) + ((dudy_n - dudy_s) * X(DXU, 0, 0)) * 0.5);
-    const double cor = ((0.5 * (X(FU, 0, 0) * (v_sc + v_nc))) * X(AU, 0, 0)) * hsu;
-    const double hpg = -(((a.g * hsu) * X(DYU, 0, 0)) * (X(SST, 1, 0) - X(SST, 0, 0)));
-    return ((un * hsu + (a.rdt * (((adv + vis) + cor) + hpg)) / X(AU, 0, 0)) / (X(HU, 0, 0) + X(SAU, 0, 0))) / a.den;
-}
-
-// va(i,j) of DESIGN.md section 6.5
-template <class XF, class TF>
-__device__ __forceinline__ double mom_v(const MomArgs &a, XF X, TF T)
-{
-    const bool ww = T(-1, 0) > 0 && T(-1, 1) > 0, ew = T(1, 0) > 0 && T(1, 1) > 0;
-    const double vn = X(VN, 0, 0), hsv = X(HV, 0, 0) + X(SSV, 0, 0);
-    const double v_n = (0.5 * (vn + X(VN, 0, 1))) * X(DXT, 0, 1);
-    const double depn = X(HT, 0, 1) + X(SST, 0, 1);
-    const double v_s = (0.5 * (vn + X(VN, 0, -1))) * X(DXT, 0, 0);
-    const double deps = X(HT, 0, 0) + X(SST, 0, 0);
-    const double u_wc = 0.5 * (X(UN, -1, 0) + X(UN, -1, 1));
-    const double u_w = (0.5 * u_wc) * (X(DYU, -1, 0) + X(DYU, -1, 1));
-    const double depw = 0.5 * (((X(HU, -1, 0) + X(SSU, -1, 0)) + X(HU, -1, 1)) + X(SSU, -1, 1));
-    const double u_ec = 0.5 * (X(UN, 0, 0) + X(UN, 0, 1));
-    const double u_e = (0.5 * u_ec) * (X(DYU, 0, 0) + X(DYU, 0, 1));
-    const double depe = 0.5 * (((X(HU, 0, 0) + X(SSU, 0, 0)) + X(HU, 0, 1)) + X(SSU, 0, 1));
-    const double vv_s = (0.5 - sg(v_s)) * vn + (0.5 + sg(v_s)) * X(VN, 0, -1);
-    const double vv_n = (0.5 + sg(v_n)) * vn + (0.5 - sg(v_n)) * X(VN, 0, 1);
-    const double vv_w = ww ? (0.5 - sg(u_w)) * vn + (0.5 + sg(u_w)) * X(VN, -1, 0) : (0.5 - sg(u_w)) * vn;
-    const double vv_e = ew ? (0.5 + sg(u_e)) * vn + (0.5 - sg(u_e)) * X(VN, 1, 0) : (0.5 + sg(u_e)) * vn;
-    const double adv = (((vv_w * u_w) * depw - (vv_e * u_e) * depe) + (vv_s * v_s) * deps) - (vv_n * v_n) * depn;
-    const double dvdy_n = ((X(VN, 0, 1) - vn) / X(DYT, 0, 1)) * (X(HT, 0, 1) + X(SST, 0, 1));
-    const double dvdy_s = ((vn - X(VN, 0, -1)) / X(DYT, 0, 0)) * (X(HT, 0, 0) + X(SST, 0, 0));
-    const double dvdx_w = ww ? ((vn - X(VN, -1, 0)) / (X(DXV, 0, 0) + X(DXV, -1, 0))) *
-                                   ((hsv + X(HV, -1, 0)) + X(SSV, -1, 0))
-                             : 0.0;
-    const double dvdx_e = ew ? ((X(VN, 1, 0) - vn) / (X(DXV, 0, 0) + X(DXV, 1, 0))) *
-                                   ((hsv + X(HV, 1, 0)) + X(SSV, 1, 0))
-                             : 0.0;
-    const double vis = a.visc * ((dvdy_n - dvdy_s) * X(DXV, 0, 0) + ((dvdx_e - dvdx_w) * X(DYV, 0, 0)) * 0.5);
-    const double cor = -(((0.5 * (X(FV, 0, 0) * (u_ec + u_wc))) * X(AV, 0, 0)) * hsv);
-    const double hpg = -(((a.g * hsv) * X(DXV, 0, 0)) * (X(SST, 0, 1) - X(SST, 0, 0)));
-    return ((vn * hsv + (a.rdt * (((adv + vis) + cor) + hpg)) / X(AV, 0, 0)) / (X(HV, 0, 0) + X(SAV, 0, 0))) / a.den;
-}
 
 constexpr int MR = 1;   // rows per wave tile: 2 rows need more than 256 VGPRs in every instantiation (one wave per SIMD)
 
@@ -241,14 +156,8 @@ __global__ __launch_bounds__(256) void next_ssh(const int *__restrict__ tmask, c
         const long long t0 = tmask[o], t1 = tmask[on];
         const double a0 = area_t[o], a1 = area_t[on], s0 = sshn_t[o], s1 = sshn_t[on], ax = area_x[o];
         if (t0 + t1 <= 0) continue;
-        out[o] = t0 * t1 > 0 ? (0.5 * (a0 * s0 + a1 * s1)) / ax : (t0 <= 0 ? s1 : s0);
+        out[o] = ssh_point(t0, t1, a0, a1, s0, s1, ax);
     }
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
 }
 
 // the momentum entries: boxes 1-based (an empty one: xstop < xstart or ystop < ystart)

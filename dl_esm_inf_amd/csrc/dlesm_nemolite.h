@@ -1,0 +1,127 @@
+// The point expressions of the NEMOLite2D-class kernels (DESIGN.md sections 5.10 and 6.5), shared by every entry that
+// evaluates them -- continuity (dlesm_continuity.hip), momentum and next_ssh* (dlesm_momentum.hip) and the one-sweep time
+// step (dlesm_nemolite_step.hip) -- so that the entries cannot drift apart.  Every operation is rounded in double precision
+// in the order the parentheses give: the sources that include this header are built with -ffp-contract=off and no
+// expression here replaces a division by a reciprocal.
+#pragma once
+
+#include "dlesm_internal.h"
+
+namespace dlesm {
+
+namespace nemo {
+
+// the double-precision operands of the momentum loop nests, by number
+enum { UN, VN, HT, SST, HU, SSU, HV, SSV, SAU, SAV, DXT, DYT, DXU, DYU, DXV, DYV, AU, AV, FU, FV, NF };
+
+struct MomArgs {
+    const double *f[NF];
+    const int *tmask;
+    double *ua, *va;
+    double rdt, visc, g, den;                 // den = 1.0 + cbfr*rdt
+};
+
+struct Box {                                  // 0-based inclusive; empty: x0 > x1
+    int x0, x1, y0, y1;
+    __host__ __device__ bool has(int i, int j) const { return i >= x0 && i <= x1 && j >= y0 && j <= y1; }
+};
+
+__device__ __forceinline__ double sg(double x) { return copysign(0.5, x); }
+
+// ssha(ji,jj) of the continuity kernel: _w operands at (ji-1, jj), _s operands at (ji, jj-1)
+__device__ __forceinline__ double cont_point(double rdt, double st, double su, double su_w, double sv, double sv_s,
+                                             double hu, double hu_w, double hv, double hv_s, double un, double un_w,
+                                             double vn, double vn_s, double area)
+{
+    const double r1 = (su + hu) * un, r2 = (su_w + hu_w) * un_w;
+    const double r3 = (sv + hv) * vn, r4 = (sv_s + hv_s) * vn_s;
+    return st + (((r2 - r1) + r4) - r3) * rdt / area;
+}
+
+// next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,
+// 1 = the one east (north) of it; ax = area_u (area_v) of the face
+__device__ __forceinline__ double ssh_point(long long t0, long long t1, double a0, double a1, double s0, double s1, double ax)
+{
+    return t0 * t1 > 0 ? (0.5 * (a0 * s0 + a1 * s1)) / ax : (t0 <= 0 ? s1 : s0);
+}
+
+// ua(i,j) of DESIGN.md section 6.5.  X(f, di, dj) = operand f at (i+di, j+dj), T(di, dj) = tmask there.
+template <class XF, class TF>
+__device__ __forceinline__ double mom_u(const MomArgs &a, XF X, TF T)
+{
+    const bool sw = T(0, -1) > 0 && T(1, -1) > 0, nw = T(0, 1) > 0 && T(1, 1) > 0;
+    const double un = X(UN, 0, 0), hsu = X(HU, 0, 0) + X(SSU, 0, 0);
+    const double u_e = (0.5 * (un + X(UN, 1, 0))) * X(DYT, 1, 0);
+    const double depe = X(HT, 1, 0) + X(SST, 1, 0);
+    const double u_w = (0.5 * (un + X(UN, -1, 0))) * X(DYT, 0, 0);
+    const double depw = X(HT, 0, 0) + X(SST, 0, 0);
+    const double v_sc = 0.5 * (X(VN, 0, -1) + X(VN, 1, -1));
+    const double v_s = (0.5 * v_sc) * (X(DXV, 0, -1) + X(DXV, 1, -1));
+    const double deps = 0.5 * (((X(HV, 0, -1) + X(SSV, 0, -1)) + X(HV, 1, -1)) + X(SSV, 1, -1));
+    const double v_nc = 0.5 * (X(VN, 0, 0) + X(VN, 1, 0));
+    const double v_n = (0.5 * v_nc) * (X(DXV, 0, 0) + X(DXV, 1, 0));
+    const double depn = 0.5 * (((X(HV, 0, 0) + X(SSV, 0, 0)) + X(HV, 1, 0)) + X(SSV, 1, 0));
+    const double uu_w = (0.5 - sg(u_w)) * un + (0.5 + sg(u_w)) * X(UN, -1, 0);
+    const double uu_e = (0.5 + sg(u_e)) * un + (0.5 - sg(u_e)) * X(UN, 1, 0);
+    const double uu_s = sw ? (0.5 - sg(v_s)) * un + (0.5 + sg(v_s)) * X(UN, 0, -1) : (0.5 - sg(v_s)) * un;
+    const double uu_n = nw ? (0.5 + sg(v_n)) * un + (0.5 - sg(v_n)) * X(UN, 0, 1) : (0.5 + sg(v_n)) * un;
+    const double adv = (((uu_w * u_w) * depw - (uu_e * u_e) * depe) + (uu_s * v_s) * deps) - (uu_n * v_n) * depn;
+    const double dudx_e = ((X(UN, 1, 0) - un) / X(DXT, 1, 0)) * (X(HT, 1, 0) + X(SST, 1, 0));
+    const double dudx_w = ((un - X(UN, -1, 0)) / X(DXT, 0, 0)) * (X(HT, 0, 0) + X(SST, 0, 0));
+    const double dudy_s = sw ? ((un - X(UN, 0, -1)) / (X(DYU, 0, 0) + X(DYU, 0, -1))) *
+                                   ((hsu + X(HU, 0, -1)) + X(SSU, 0, -1))
+                             : 0.0;
+    const double dudy_n = nw ? ((X(UN, 0, 1) - un) / (X(DYU, 0, 0) + X(DYU, 0, 1))) *
+                                   ((hsu + X(HU, 0, 1)) + X(SSU, 0, 1))
+                             : 0.0;
+    const double vis = a.visc * ((dudx_e - dudx_w) * X(DYU, 0, 0) + ((dudy_n - dudy_s) * X(DXU, 0, 0)) * 0.5);
+    const double cor = ((0.5 * (X(FU, 0, 0) * (v_sc + v_nc))) * X(AU, 0, 0)) * hsu;
+    const double hpg = -(((a.g * hsu) * X(DYU, 0, 0)) * (X(SST, 1, 0) - X(SST, 0, 0)));
+    return ((un * hsu + (a.rdt * (((adv + vis) + cor) + hpg)) / X(AU, 0, 0)) / (X(HU, 0, 0) + X(SAU, 0, 0))) / a.den;
+}
+
+// va(i,j) of DESIGN.md section 6.5
+template <class XF, class TF>
+__device__ __forceinline__ double mom_v(const MomArgs &a, XF X, TF T)
+{
+    const bool ww = T(-1, 0) > 0 && T(-1, 1) > 0, ew = T(1, 0) > 0 && T(1, 1) > 0;
+    const double vn = X(VN, 0, 0), hsv = X(HV, 0, 0) + X(SSV, 0, 0);
+    const double v_n = (0.5 * (vn + X(VN, 0, 1))) * X(DXT, 0, 1);
+    const double depn = X(HT, 0, 1) + X(SST, 0, 1);
+    const double v_s = (0.5 * (vn + X(VN, 0, -1))) * X(DXT, 0, 0);
+    const double deps = X(HT, 0, 0) + X(SST, 0, 0);
+    const double u_wc = 0.5 * (X(UN, -1, 0) + X(UN, -1, 1));
+    const double u_w = (0.5 * u_wc) * (X(DYU, -1, 0) + X(DYU, -1, 1));
+    const double depw = 0.5 * (((X(HU, -1, 0) + X(SSU, -1, 0)) + X(HU, -1, 1)) + X(SSU, -1, 1));
+    const double u_ec = 0.5 * (X(UN, 0, 0) + X(UN, 0, 1));
+    const double u_e = (0.5 * u_ec) * (X(DYU, 0, 0) + X(DYU, 0, 1));
+    const double depe = 0.5 * (((X(HU, 0, 0) + X(SSU, 0, 0)) + X(HU, 0, 1)) + X(SSU, 0, 1));
+    const double vv_s = (0.5 - sg(v_s)) * vn + (0.5 + sg(v_s)) * X(VN, 0, -1);
+    const double vv_n = (0.5 + sg(v_n)) * vn + (0.5 - sg(v_n)) * X(VN, 0, 1);
+    const double vv_w = ww ? (0.5 - sg(u_w)) * vn + (0.5 + sg(u_w)) * X(VN, -1, 0) : (0.5 - sg(u_w)) * vn;
+    const double vv_e = ew ? (0.5 + sg(u_e)) * vn + (0.5 - sg(u_e)) * X(VN, 1, 0) : (0.5 + sg(u_e)) * vn;
+    const double adv = (((vv_w * u_w) * depw - (vv_e * u_e) * depe) + (vv_s * v_s) * deps) - (vv_n * v_n) * depn;
+    const double dvdy_n = ((X(VN, 0, 1) - vn) / X(DYT, 0, 1)) * (X(HT, 0, 1) + X(SST, 0, 1));
+    const double dvdy_s = ((vn - X(VN, 0, -1)) / X(DYT, 0, 0)) * (X(HT, 0, 0) + X(SST, 0, 0));
+    const double dvdx_w = ww ? ((vn - X(VN, -1, 0)) / (X(DXV, 0, 0) + X(DXV, -1, 0))) *
+                                   ((hsv + X(HV, -1, 0)) + X(SSV, -1, 0))
+                             : 0.0;
+    const double dvdx_e = ew ? ((X(VN, 1, 0) - vn) / (X(DXV, 0, 0) + X(DXV, 1, 0))) *
+                                   ((hsv + X(HV, 1, 0)) + X(SSV, 1, 0))
+                             : 0.0;
+    const double vis = a.visc * ((dvdy_n - dvdy_s) * X(DXV, 0, 0) + ((dvdx_e - dvdx_w) * X(DYV, 0, 0)) * 0.5);
+    const double cor = -(((0.5 * (X(FV, 0, 0) * (u_ec + u_wc))) * X(AV, 0, 0)) * hsv);
+    const double hpg = -(((a.g * hsv) * X(DXV, 0, 0)) * (X(SST, 0, 1) - X(SST, 0, 0)));
+    return ((vn * hsv + (a.rdt * (((adv + vis) + cor) + hpg)) / X(AV, 0, 0)) / (X(HV, 0, 0) + X(SAV, 0, 0))) / a.den;
+}
+
+// true if [a, a+na) and [b, b+nb) share a byte
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+} // namespace nemo
+
+} // namespace dlesm

@@ -13,12 +13,6 @@
 
 #include "dlesm_internal.h"
 
-struct dlesm_obc {
-    int ld, ny;
-    int nt, nu, nv;   // open T cells, open u faces, open v faces
-    int *dev;         // one allocation: t[nt] | uf[nu] ui[nu] uo[nu] | vf[nv] vi[nv] vo[nv]; NULL when all lists are empty
-};
-
 namespace dlesm {
 
 namespace {

@@ -190,6 +190,27 @@ def invoke_bc_open(params, ssh_bc, ssha, ua, va, hu, sshn_u, hv, sshn_v, sshn_t,
                                         _stream_ptr(stream)))
 
 
+def invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc=None,
+                         stream=None):
+    """one NEMOLite2D-class time step in one call, bit for bit invoke_continuity (rdt = params.rdt)
+    -> invoke_next_sshu / invoke_next_sshv on ssha -> invoke_momentum -> invoke_bc_open on the grid's open_boundary plan.
+    ssh_bc=None: a closed basin, no boundary pass.  ssha is in/out (the ring cells east and north of the box are read).
+    Single domain: stops on a decomposed grid, and when the grid's Coriolis parameter was never set."""
+    g = ssha.grid
+    if g.decomp is not None and g.decomp.ndomains > 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_nemolite_step: the grid is decomposed (%d subdomains): the step needs an "
+                                             "ssha halo exchange between continuity and next_ssh*, which one call cannot "
+                                             "hold; use the separate wrappers" % g.decomp.ndomains)
+    mg = _momentum_grid(g, "invoke_nemolite_step")
+    plan = None if ssh_bc is None else open_boundary(g).handle
+    check(_cabi.lib().dlesm_nemolite_step_f64(C.byref(params), C.byref(mg), C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny,
+                                              C.byref(ssha.internal), C.byref(ua.internal), C.byref(va.internal), plan,
+                                              0.0 if ssh_bc is None else float(ssh_bc),
+                                              *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u,
+                                                                       ssha_v, ua, va)],
+                                              _stream_ptr(stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

@@ -350,6 +350,24 @@ int dlesm_bc_open_f64(const dlesm_obc *plan, const dlesm_momentum_params *params
                       const double *sshn_u, const double *hv, const double *sshn_v, const double *sshn_t, double *ssha,
                       double *ua, double *va, void *stream);
 
+/* One NEMOLite2D-class time step in one call: bit for bit the sequence
+ *   dlesm_continuity_f64 over tbox (rdt = params->rdt) -> dlesm_next_sshu_f64 over ubox and dlesm_next_sshv_f64 over vbox
+ *   (reading ssha) -> dlesm_momentum_f64 over ubox / vbox (reading ssha_u / ssha_v) -> dlesm_bc_open_f64(obc, params, ssh_bc,
+ *   ...) when obc is not NULL (NULL: a closed basin, no boundary pass).
+ * Every cell of every array is written where that sequence writes it and keeps its content elsewhere.  ssha is in/out:
+ * next_ssh* read ssha(xstop+1, j) and ssha(i, ystop+1) in the ring, which continuity does not write; the call reads them
+ * from ssha.  tbox == ubox == vbox (every NE grid) with an even ld and 16-byte aligned arrays is one sweep, 196 B/cell
+ * against 324 for the sequence; anything else runs the sequence itself.  No output may overlap an input (tmask, area_t,
+ * the grid arrays and the ten fields), and ssha, ssha_u, ssha_v, ua and va may not overlap each other (DLESM_EINVAL,
+ * refused before anything is launched); the plan must have been made for ld x ny arrays.  Single domain, rank-local: on a
+ * decomposed grid the sequence needs an ssha halo exchange between continuity and next_ssh*, which one call cannot hold. */
+int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, const double *area_t,
+                            int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+                            const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn, const double *ht,
+                            const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                            const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                            void *stream);
+
 /* Shallow-water u/v/h update: reads u,v,p (3x3 footprint)
  * and uold,vold,pold, writes unew,vnew,pnew on the box. */
 typedef struct dlesm_sw_params {
