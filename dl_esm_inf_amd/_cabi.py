@@ -222,6 +222,8 @@ PROTOTYPES = {
     "dlesm_shallow_step_smooth_dm": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_shallow_step_x2_dm": (_i, [_vp, C.POINTER(SwParams), _i, _i, _i, _i, _i, _i] + [_vp] * 12 + [_vp]),
     "dlesm_shallow_step_smooth_x2_dm": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 12 + [_vp]),
+    "dlesm_nemolite_step_dm": (_i, [_vp, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i, C.POINTER(Region),
+                                    C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
     "dlesm_shallow_step_smooth_dm_pipelined": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_global_sum_f64": (_i, [C.POINTER(_d)]),
     "dlesm_gather_f64": (_i, [_vp, _vp, _i]),

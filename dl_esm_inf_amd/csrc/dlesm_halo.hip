@@ -37,6 +37,7 @@
 
 #include "dlesm_internal.h"
 #include "dlesm_device.h"
+#include "dlesm_nemolite.h"
 
 using namespace dlesm;
 
@@ -1833,6 +1834,114 @@ extern "C" int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *p, const dlesm_s
     const double *all[12] = {u, v, pf, uold, vold, pold, uold2, vold2, pold2, unew2, vnew2, pnew2};
     return shallow_x2_dm_impl("dlesm_shallow_step_smooth_x2_dm", p, q, &alpha, ld, ny, xstart, xstop, ystart, ystop, all,
                               (hipStream_t)stream);
+}
+
+// One NEMOLite2D-class time step on a decomposed grid (dlesm_nemolite_step_dm).  The definition
+// exchanges ssha between continuity and next_ssh* only so that the faces of the east column and the north row of the box can
+// read ssha in the ring; where a neighbour sends those ring cells they are its interior cells, and continuity computes them
+// here from the depth-1 halos of level n with the same expression tree and operands, so they are its bits.  Then the
+// single-domain step (section 6.7) unchanged, then ONE exchange of the five outputs.
+
+// the ring cells one receive message of the plan writes that a face of the box reads: its rectangle intersected with the
+// east column (x1+1, y0:y1) and the north row (x0:x1, y1+1); 0-based inclusive
+struct RingRects {
+    static constexpr int MAX = 32;
+    int n;
+    int x0[MAX], x1[MAX], y0[MAX], y1[MAX];
+};
+
+// one thread per ring cell: continuity's point expression (dlesm_nemolite.h), operands at (i-1, j) and (i, j-1) from the
+// depth-1 halos of level n
+__global__ __launch_bounds__(256) void nemolite_ssha_ring(RingRects r, double rdt, int ld, const double *sshn_t,
+                                                          const double *sshn_u, const double *sshn_v, const double *hu,
+                                                          const double *hv, const double *un, const double *vn,
+                                                          const double *area_t, double *ssha)
+{
+    const int k = blockIdx.y;
+    const int w = r.x1[k] - r.x0[k] + 1, n = w * (r.y1[k] - r.y0[k] + 1);
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        const int i = r.x0[k] + t % w, j = r.y0[k] + t / w;
+        const size_t o = (size_t)j * ld + i;
+        ssha[o] = nemo::cont_point(rdt, sshn_t[o], sshn_u[o], sshn_u[o - 1], sshn_v[o], sshn_v[o - ld], hu[o], hu[o - 1], hv[o],
+                                   hv[o - ld], un[o], un[o - 1], vn[o], vn[o - ld], area_t[o]);
+    }
+}
+
+extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                      const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                                      const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un,
+                                      const double *vn, const double *ht, const double *hu, const double *hv,
+                                      const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
+                                      double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+{
+    static const char *who = "dlesm_nemolite_step_dm";
+    clear_error();
+    DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
+    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
+    if (int rc = ensure_device()) return rc;
+    if (int rc = nemo::step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t,
+                                  sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va))
+        return rc;
+    const bool comms = !p->sends.empty() || !p->recvs.empty();
+    auto step = [&] {
+        return dlesm_nemolite_step_f64(params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, sshn_t,
+                                       sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+    };
+    if (!comms) return step();       // no neighbour: the single-domain entry, bit for bit
+
+    // ---- every refusal of a plan with messages, before anything is launched or exchanged
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
+    for (const Msg &m : p->recvs) {
+        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
+        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
+        if (!xdir && !ydir) continue;
+        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 1, "%s: the plan exchanges depth-%d halos, the step needs depth 1 "
+                      "(a grid decomposed with halo_width = 1)", who, xdir ? m.nx : m.ny);
+    }
+    DLESM_REQUIRE(nemo::same_box(tbox, ubox) && nemo::same_box(tbox, vbox),
+                  "%s: on a decomposed grid the T, U and V boxes must be one box (every NE grid): T (%d:%d,%d:%d), "
+                  "U (%d:%d,%d:%d), V (%d:%d,%d:%d)", who, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, ubox->xstart,
+                  ubox->xstop, ubox->ystart, ubox->ystop, vbox->xstart, vbox->xstop, vbox->ystart, vbox->ystop);
+    DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
+    RingRects r{};
+    if (!nemo::empty(tbox)) {
+        const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
+        const nemo::Box ring[2] = {{x1 + 1, x1 + 1, y0, y1}, {x0, x1, y1 + 1, y1 + 1}};   // east column, north row
+        for (const Msg &m : p->recvs)
+            for (const nemo::Box &b : ring) {
+                const int a0 = std::max(b.x0, m.i0), a1 = std::min(b.x1, m.i0 + m.nx - 1);
+                const int c0 = std::max(b.y0, m.j0), c1 = std::min(b.y1, m.j0 + m.ny - 1);
+                if (a0 > a1 || c0 > c1) continue;
+                DLESM_REQUIRE(r.n < RingRects::MAX, "%s: more than %d receive strips border the box", who, RingRects::MAX);
+                r.x0[r.n] = a0, r.x1[r.n] = a1, r.y0[r.n] = c0, r.y1[r.n] = c1;
+                r.n++;
+            }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double *const outs[5] = {ssha, ssha_u, ssha_v, ua, va};
+    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil(5 / peer_fcap) mailbox
+    // operations per call on every rank -- nothing rank-local (obc, the path step 2 takes, the box) changes that number
+    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
+    const int turn = mailbox ? p->peer_fcap : 5;
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
+    if (int rc = join_pending(p, s)) return rc;
+
+    // 1. ssha on the ring cells the neighbours send
+    if (r.n) {
+        int most = 0;
+        for (int k = 0; k < r.n; k++) most = std::max(most, (r.x1[k] - r.x0[k] + 1) * (r.y1[k] - r.y0[k] + 1));
+        const unsigned gx = (unsigned)std::min((most + 255) / 256, 64);
+        hipLaunchKernelGGL(nemolite_ssha_ring, dim3(gx, r.n), dim3(256), 0, s, r, params->rdt, ld, sshn_t, sshn_u, sshn_v, hu,
+                           hv, un, vn, area_t, ssha);
+        DLESM_HIP_TRY(hipGetLastError());
+    }
+    // 2. the single-domain step: the sweep, or the five entries, then bc_open
+    if (int rc = step()) return rc;
+    // 3. one exchange of the five outputs (mailboxes: in turns of peer_fcap fields)
+    for (int k = 0; k < 5; k += turn)
+        if (int rc = exchange_on(p, outs + k, std::min(turn, 5 - k), DLESM_DIRS_ALL, s)) return rc;
+    return DLESM_OK;
 }
 
 extern "C" int dlesm_global_sum_f64(double *value)

@@ -122,6 +122,22 @@ inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
     return x < y + nb && y < x + na;
 }
 
+inline bool empty(const dlesm_region *r) { return r->xstop < r->xstart || r->ystop < r->ystart; }
+
+inline bool same_box(const dlesm_region *a, const dlesm_region *b)
+{
+    return (empty(a) && empty(b)) ||
+           (a->xstart == b->xstart && a->xstop == b->xstop && a->ystart == b->ystart && a->ystop == b->ystop);
+}
+
+// every refusal of DESIGN.md section 6.7 (null pointers, boxes, overlaps, the Coriolis parameter, an open-boundary plan of
+// other extents), messages prefixed with `who`; DLESM_OK or DLESM_EINVAL.  Launches nothing (dlesm_nemolite_step.hip).
+int step_check(const char *who, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, const double *area_t,
+               int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+               const dlesm_obc *obc, const double *un, const double *vn, const double *ht, const double *hu,
+               const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
+               double *ssha_u, double *ssha_v, double *ua, double *va);
+
 } // namespace nemo
 
 } // namespace dlesm

@@ -148,35 +148,21 @@ __global__ __launch_bounds__(256) void nemolite_step_tile(StepArgs s, int ld, in
     store_pair(a.va + oj, ov[0], ov[1], wv[0], wv[1]);
 }
 
-bool empty(const dlesm_region *r) { return r->xstop < r->xstart || r->ystop < r->ystart; }
-
-bool same_box(const dlesm_region *a, const dlesm_region *b)
-{
-    return (empty(a) && empty(b)) ||
-           (a->xstart == b->xstart && a->xstop == b->xstop && a->ystart == b->ystart && a->ystop == b->ystop);
-}
-
 } // namespace
 
-} // namespace dlesm
-
-using namespace dlesm;
-
-extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
-                                       const double *area_t, int ld, int ny, const dlesm_region *tbox,
-                                       const dlesm_region *ubox, const dlesm_region *vbox, const dlesm_obc *obc,
-                                       double ssh_bc, const double *un, const double *vn, const double *ht, const double *hu,
-                                       const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v,
-                                       double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+// every refusal of DESIGN.md section 6.7, before anything is launched (dlesm_nemolite_step_f64, dlesm_nemolite_step_dm)
+int nemo::step_check(const char *who, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                     const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                     const dlesm_region *vbox, const dlesm_obc *obc, const double *un, const double *vn, const double *ht,
+                     const double *hu, const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                     double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va)
 {
-    static const char *who = "dlesm_nemolite_step_f64";
-    if (int rc = ensure_device()) return rc;
     DLESM_REQUIRE(params && grid && tbox && ubox && vbox, "%s: null parameter, grid or region pointer", who);
     for (const dlesm_region *r : {tbox, ubox, vbox})
         if (!empty(r))
             if (int rc = check_box(who, ld, ny, r->xstart, r->xstop, r->ystart, r->ystop, 1)) return rc;
 
-    // every input of the five entries, every output; refused before anything is launched
+    // every input of the five entries, every output
     const double *const ins[19] = {un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, area_t, grid->dx_t, grid->dy_t, grid->dx_u,
                                    grid->dy_u, grid->dx_v, grid->dy_v, grid->area_u, grid->area_v, grid->fcor_u,
                                    grid->fcor_v};
@@ -200,6 +186,29 @@ extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, cons
     }
     DLESM_REQUIRE(!obc || (obc->ld == ld && obc->ny == ny), "%s: the open-boundary plan was made for %dx%d arrays, not %dx%d",
                   who, obc ? obc->ld : 0, obc ? obc->ny : 0, ld, ny);
+    return DLESM_OK;
+}
+
+} // namespace dlesm
+
+using namespace dlesm;
+
+extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                       const double *area_t, int ld, int ny, const dlesm_region *tbox,
+                                       const dlesm_region *ubox, const dlesm_region *vbox, const dlesm_obc *obc,
+                                       double ssh_bc, const double *un, const double *vn, const double *ht, const double *hu,
+                                       const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                                       double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+{
+    static const char *who = "dlesm_nemolite_step_f64";
+    if (int rc = ensure_device()) return rc;
+    if (int rc = step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t, sshn_u,
+                            sshn_v, ssha, ssha_u, ssha_v, ua, va))
+        return rc;
+    const double *const ins[19] = {un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, area_t, grid->dx_t, grid->dy_t, grid->dx_u,
+                                   grid->dy_u, grid->dx_v, grid->dy_v, grid->area_u, grid->area_v, grid->fcor_u,
+                                   grid->fcor_v};
+    double *const outs[5] = {ssha, ssha_u, ssha_v, ua, va};
 
     bool aligned = ld % 2 == 0 && (uintptr_t)grid->tmask % 8 == 0;
     for (const double *p : ins) aligned = aligned && (uintptr_t)p % 16 == 0;

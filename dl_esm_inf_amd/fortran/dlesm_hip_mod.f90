@@ -689,6 +689,20 @@ module dlesm_hip_mod
        type(c_ptr), value :: u, v, p, uold, vold, pold, unew, vnew, pnew, stream
        integer(c_int) :: rc
      end function
+     function dlesm_nemolite_step_dm(plan, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, &
+          sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream) bind(C, name="dlesm_nemolite_step_dm") result(rc)
+       import :: c_int, c_ptr, c_double, c_momentum_params, c_momentum_grid, c_region
+       type(c_ptr), value :: plan
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       type(c_ptr), value :: area_t
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: tbox, ubox, vbox
+       type(c_ptr), value :: obc
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream
+       integer(c_int) :: rc
+     end function
      function dlesm_shallow_step_x2_dm(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, &
           unew, vnew, pnew, unew2, vnew2, pnew2, stream) bind(C, name="dlesm_shallow_step_x2_dm") result(rc)
        import :: c_int, c_ptr, c_sw_params

@@ -54,7 +54,7 @@ module dlesm_psy_mod
   public :: momentum_params, c_momentum_params, momentum_coriolis, invoke_momentum_u, invoke_momentum_v, invoke_momentum
   public :: invoke_next_sshu, invoke_next_sshv
   public :: open_boundary, tide_ssh, invoke_bc_ssh, invoke_bc_flather_u, invoke_bc_flather_v, invoke_bc_open
-  public :: invoke_nemolite_step
+  public :: invoke_nemolite_step, invoke_nemolite_step_dm
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -439,6 +439,55 @@ contains
                                  field_device_data(ua), field_device_data(va), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_nemolite_step: ' // dlesm_error_text())
   end subroutine invoke_nemolite_step
+
+  !> One NEMOLite2D-class time step and ONE exchange of its five outputs on a decomposed grid (dlesm_nemolite_step_dm, DESIGN.md
+  !! section 6.8): bit for bit invoke_continuity, ssha%halo_exchange(1), invoke_next_sshu / invoke_next_sshv, invoke_momentum,
+  !! (ssh_bc present) invoke_bc_open on this rank's open_boundary plan, then the exchange of ssha, ssha_u, ssha_v, ua, va.  The
+  !! inputs need valid depth-1 halos, corners included; the outputs leave with them.  Collective.  The grid must have been
+  !! decomposed with halo_width = 1 (without distributed memory the plan has no messages: invoke_nemolite_step, bit for bit).
+  !! Stops on another halo width and without momentum_coriolis.
+  subroutine invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    type(c_momentum_params), intent(in) :: params
+    type(r2d_field), intent(inout), target :: ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    real(go_wp), intent(in), optional :: ssh_bc
+    type(c_momentum_grid) :: mg
+    type(c_region) :: tbox, ubox, vbox
+    type(c_ptr) :: plan, obc
+    real(c_double) :: bc
+    integer(c_int) :: rc
+    if (ssha%grid%subdomain%internal%xstart - 1 /= 1 .or. ssha%grid%subdomain%internal%ystart - 1 /= 1) &
+         call gocean_stop('invoke_nemolite_step_dm: the grid must be decomposed with halo_width = 1')
+    call need_device(ssha);  call need_device(ssha_u);  call need_device(ssha_v);  call need_device(ua);  call need_device(va)
+    call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(hu);  call need_device(hv)
+    call need_device(sshn_t);  call need_device(sshn_u);  call need_device(sshn_v)
+    mg = momentum_grid(ssha%grid, 'invoke_nemolite_step_dm')
+    tbox = c_region(ssha%internal%nx, ssha%internal%ny, ssha%internal%xstart, ssha%internal%xstop, &
+                    ssha%internal%ystart, ssha%internal%ystop)
+    ubox = c_region(ua%internal%nx, ua%internal%ny, ua%internal%xstart, ua%internal%xstop, &
+                    ua%internal%ystart, ua%internal%ystop)
+    vbox = c_region(va%internal%nx, va%internal%ny, va%internal%xstart, va%internal%xstop, &
+                    va%internal%ystart, va%internal%ystop)
+    obc = c_null_ptr
+    bc = 0.0_c_double
+    if (present(ssh_bc)) then
+       obc = open_boundary(ssha%grid)
+       bc = real(ssh_bc, c_double)
+    end if
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(ssha%grid%nx, ssha%grid%ny)
+    else
+       plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
+    end if
+    rc = dlesm_nemolite_step_dm(plan, params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), &
+                                int(ssha%grid%ny, c_int), tbox, ubox, vbox, obc, bc, field_device_data(un), &
+                                field_device_data(vn), field_device_data(ht), field_device_data(hu), field_device_data(hv), &
+                                field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                field_device_data(ssha), field_device_data(ssha_u), field_device_data(ssha_v), &
+                                field_device_data(ua), field_device_data(va), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_nemolite_step_dm: ' // dlesm_error_text())
+  end subroutine invoke_nemolite_step_dm
 
   !> Optional planning call (once per field geometry, outside the time loop): lets the library time
   !! its launch shapes for invoke_jacobi5 / invoke_jacobi5_dm on these fields and keep the fastest.

@@ -211,6 +211,32 @@ def invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, h
                                               _stream_ptr(stream)))
 
 
+def invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc=None,
+                            stream=None):
+    """one NEMOLite2D-class time step and ONE exchange of its five outputs on a decomposed grid, bit for
+    bit invoke_continuity -> ssha.halo_exchange(1) -> invoke_next_sshu / invoke_next_sshv -> invoke_momentum ->
+    invoke_bc_open on this rank's open_boundary plan (ssh_bc=None: none) -> halo_exchange_multi of ssha, ssha_u, ssha_v, ua,
+    va.  The inputs need valid depth-1 halos, corners included; the outputs leave with them.  Collective.  Stops on a grid
+    with halo_width other than 1, and when the grid's Coriolis parameter was never set."""
+    g = ssha.grid
+    hw = getattr(g, "halo_width", 1)
+    if hw != 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_nemolite_step_dm: the grid has halo_width %d; the step exchanges depth-1 "
+                                             "halos: decompose the grid with halo_width = 1" % hw)
+    mg = _momentum_grid(g, "invoke_nemolite_step_dm")
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_nemolite_step_dm: the grid has no message tables (grid_init after "
+                                             "decompose)")
+    obc = None if ssh_bc is None else open_boundary(g).handle
+    check(_cabi.lib().dlesm_nemolite_step_dm(grid_mod.halo_plan(g), C.byref(params), C.byref(mg),
+                                             C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal),
+                                             C.byref(ua.internal), C.byref(va.internal), obc,
+                                             0.0 if ssh_bc is None else float(ssh_bc),
+                                             *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u,
+                                                                      ssha_v, ua, va)],
+                                             _stream_ptr(stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

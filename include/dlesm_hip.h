@@ -866,6 +866,27 @@ int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *plan, const dlesm_sw_params
                                     double *unew2, double *vnew2, double *pnew2,
                                     double *uold2, double *vold2, double *pold2, void *stream);
 
+/* The distributed form of dlesm_nemolite_step_f64: one NEMOLite2D-class time step and ONE exchange of
+ * its five outputs.  Bit for bit, in every cell of every array (halos and padding included), what this definition leaves:
+ * dlesm_continuity_f64 over tbox; dlesm_halo_exchange_f64(plan, ssha, DLESM_DIRS_ALL); next_sshu / next_sshv, momentum and,
+ * when obc is not NULL, bc_open, as dlesm_nemolite_step_f64 runs them; dlesm_halo_exchange_multi_f64 of {ssha, ssha_u,
+ * ssha_v, ua, va} over DLESM_DIRS_ALL.
+ * In: un, vn, sshn_t, sshn_u, sshn_v, ht, hu, hv with valid depth-1 halos towards every neighbour, corners included (the
+ * ssha cells a neighbour would send are computed here by continuity, which reads e.g. vn(xe+1, ys-1)); on sides without a
+ * neighbour the ring rules of dlesm_nemolite_step_f64 (ssha there is the caller's).  Out: ssha, ssha_u, ssha_v, ua, va with
+ * valid depth-1 halos; a time loop only rotates the pointers.
+ * A plan without messages: dlesm_nemolite_step_f64, bit for bit, for any boxes.  A plan with messages needs a depth-1 plan
+ * (a grid decomposed with halo_width = 1) and tbox == ubox == vbox; another depth or unequal boxes give DLESM_EINVAL, as do
+ * a null plan, a plan for other extents and every refusal of dlesm_nemolite_step_f64 -- all before anything is launched or
+ * exchanged.  obc is rank-local (each rank's plan from its own mask, possibly empty).  Collective: every rank calls it, in
+ * the same order. */
+int dlesm_nemolite_step_dm(dlesm_halo_plan *plan, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                           const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                           const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+                           const double *ht, const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                           const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                           void *stream);
+
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);
