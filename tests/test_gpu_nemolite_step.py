@@ -14,14 +14,9 @@ import pytest
 import momentum_numpy as M
 import open_bc_numpy as B
 import oracle_lib as O
+from nemolite_boxes import INS, METRICS, MOM, OUTS, PRM, _dev, _host_inputs, _host_outputs, _plan, _raw_grid
 
 pytestmark = pytest.mark.gpu
-
-PRM = (20.0, 0.00015, 50.0, 9.80665)          # rdt, cbfr, visc, g
-METRICS = ("dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_t", "area_u", "area_v")
-INS = ("un", "vn", "ht", "hu", "hv", "sshn_t", "sshn_u", "sshn_v")
-OUTS = ("ssha", "ssha_u", "ssha_v", "ua", "va")
-MOM = ("un", "vn", "ht", "sshn_t", "hu", "sshn_u", "hv", "sshn_v", "ssha_u", "ssha_v")
 
 
 @pytest.fixture(scope="module")
@@ -42,74 +37,6 @@ def _set_tuning(D, **kw):
 
 def _p(t):
     return C.c_void_p(t.data_ptr())
-
-
-def _vel(rng, shape):
-    v = rng.normal(0.0, 0.3, shape)
-    pick = rng.random(shape)
-    v[pick < 0.15] = 0.0
-    v[(pick >= 0.15) & (pick < 0.3)] = -0.0
-    return v
-
-
-def _host_inputs(rng, shape):
-    """un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v"""
-    H = {"un": _vel(rng, shape), "vn": _vel(rng, shape)}
-    for k in ("ht", "hu", "hv"):
-        H[k] = 10.0 + rng.random(shape)
-    for k in ("sshn_t", "sshn_u", "sshn_v"):
-        H[k] = 0.1 * rng.normal(size=shape)
-    return H
-
-
-def _host_outputs(rng, shape):
-    """ssha: distinct values everywhere (the ring's are read by next_ssh*, the box's overwritten); the others sentinels"""
-    H = {"ssha": 1000.0 + rng.random(shape)}
-    for k in OUTS[1:]:
-        H[k] = np.full(shape, -7.0)
-    return H
-
-
-def _raw_grid(torch, rng, tm):
-    """a dlesm_momentum_grid of non-uniform metrics (zero T spacings on land: dry cells divide by zero) with a varying
-    Coriolis parameter, area_t beside it; host copies in G"""
-    ny, ld = tm.shape
-    G = {"tmask": np.ascontiguousarray(tm, dtype=np.int32)}
-    land = tm <= 0
-    for name in METRICS:
-        a = 900.0 + 200.0 * rng.random((ny, ld))
-        if name.startswith("area"):
-            a *= 1000.0
-        elif name.endswith("_t"):
-            a[land] = 0.0
-        G[name] = a
-    G["fcor_u"] = M.coriolis(40.0 + 20.0 * rng.random((ny, ld)), 7.292116e-5, math.pi / 180.0)
-    G["fcor_v"] = M.coriolis(40.0 + 20.0 * rng.random((ny, ld)), 7.292116e-5, math.pi / 180.0)
-    dev = {k: torch.from_numpy(v).cuda() for k, v in G.items()}
-    from dl_esm_inf_amd import _cabi
-    mg = _cabi.MomentumGrid(**{k: dev[k].data_ptr() for k in M.GRID_ARRAYS})
-    return M.SimpleNamespace(**G), dev, mg
-
-
-def _dev(torch, host, shift):
-    """device copies; shift: bases 8 bytes off a 16-byte boundary"""
-    out = {}
-    for k, a in host.items():
-        t = torch.from_numpy(a.copy()).cuda()
-        if shift:
-            t = torch.cat([torch.zeros(1, dtype=torch.float64, device="cuda"), t.flatten()])[1:].view(a.shape)
-        out[k] = t
-    return out
-
-
-def _plan(D, tm, tbox, ubox, vbox):
-    ny, ld = tm.shape
-    tm = np.ascontiguousarray(tm, dtype=np.int32)
-    h = C.c_void_p()
-    D._cabi.check(D._cabi.lib().dlesm_obc_create(tm.ctypes.data, ld, ny, C.byref(D._cabi.Region(0, 0, *tbox)),
-                                                 C.byref(D._cabi.Region(0, 0, *ubox)), C.byref(D._cabi.Region(0, 0, *vbox)),
-                                                 C.byref(h)))
-    return h
 
 
 def _sequence(D, prm, mg, gdev, ld, ny, tbox, ubox, vbox, plan, ssh_bc, I, O_):
