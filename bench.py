@@ -2,7 +2,7 @@
 """Headline benchmark: fp64 5-point Jacobi over a dl_esm_inf r2d_field (+ RCCL halo exchange
 when N > 1), BASELINE.json metric "stencil Mcells/s + achieved HBM GB/s, 16384^2 fp64 grid".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tile 16384] [--alignment 64] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tile 16384] [--alignment 64] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch: (halo exchange +) one Jacobi sweep of the
@@ -10,7 +10,13 @@ per-GPU tile.  Weak scaling: every GPU owns a tile x tile T-point field; the glo
 (tile*P) x (tile*Q) with P x Q what go_decompose picks for N ranks.  Inputs are generated on
 the device (counter-based hash of the global cell index) before the timed region starts.
 
-Prints ONE JSON line (rank 0).  The CPU oracle is used only for the `cpu_baseline` leg.
+A plain run does what the headline needs: set-up, planning call, (N > 1: the self-check that decides
+the form of the distributed step,) warm-up, timed steps, --dump-outputs, the line.  --full adds every
+secondary object and check: the CPU baselines, the other BASELINE configurations, the shallow-water,
+fused-step, weak-scaling and peer-transport legs, the copy ceilings and, N > 1, the DLESM_DM_SAFE
+re-run of the timed steps.
+
+Prints ONE JSON line (rank 0).  The CPU oracle is used only for the `cpu_baseline` leg (--full).
 """
 import argparse
 import ctypes as C
@@ -35,6 +41,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--tile", type=int, default=16384, help="per-GPU interior is tile x tile")
     ap.add_argument("--alignment", type=int, default=64, help="DL_ESM_ALIGNMENT for the run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the secondary objects and checks too (the --no-* options below "
+                         "leave single ones out); without it the line carries the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg")
     ap.add_argument("--fused", type=int, default=1,
@@ -58,7 +67,8 @@ def parse():
     ap.add_argument("--selfcheck-steps", type=int, default=50,
                     help="N > 1: back-to-back steps of the timed form compared with as many stencil + exchange steps before timing")
     ap.add_argument("--force-dm-leg", action="store_true",
-                    help="rehearsal on 1 GPU: run the N>1 secondary leg with a 1-rank process group")
+                    help="rehearsal on 1 GPU: run the N>1 self-check (and, with --full, the N>1 secondary legs) "
+                         "with a 1-rank process group")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=INT",
                     help="experiments: dlesm_set_tuning(KEY, INT) before the run (repeatable)")
     ap.add_argument("--rows", type=int, default=None, help="tuning: rows per strip")
@@ -1432,9 +1442,10 @@ def main():
     dm_safe_fallback = False
     a0 = None
     if world > 1 or args.force_dm_leg:
-        a0 = D.r2d_field(grid, D.GO_T_POINTS)                # the initial state, halos included: start of the dm_safe re-run below
-        with torch.cuda.stream(stream):
-            D.copy_field(a, a0, stream=stream)
+        if args.full:
+            a0 = D.r2d_field(grid, D.GO_T_POINTS)            # the initial state, halos included: start of the dm_safe re-run below
+            with torch.cuda.stream(stream):
+                D.copy_field(a, a0, stream=stream)
         nchk = max(3, args.selfcheck_steps)
 
         def run_selfcheck():
@@ -1509,7 +1520,7 @@ def main():
         dump_outputs(args.dump_outputs, torch, a, rank, world)      # `a`: what the last timed step wrote
     stage(rank, world, "global checksum (ncclAllReduce)")
     checksum = D.field_checksum(a)
-    # N > 1: the SAME warm-up + timed steps once more from the same initial state in the conservative form (DLESM_DM_SAFE:
+    # N > 1, --full: the SAME warm-up + timed steps once more from the same initial state in the conservative form (DLESM_DM_SAFE:
     # own frame launch, events, unpack into the field -- kernel boundaries only), untimed: the field the timed loop left
     # behind must equal it bit for bit on every rank, and so must the global checksum
     dm_rerun = None
@@ -1579,7 +1590,7 @@ def main():
                      "launch_ms": round(launch_ms, 5),
                      "algorithmic_bytes_per_launch": BYTES_PER_CELL * args.tile * args.tile},
     }
-    secondary = fused == 1 and not args.force_dm_leg
+    secondary = args.full and fused == 1 and not args.force_dm_leg
     failed = []                                              # names of secondary legs that raised
 
     def guarded(name, fn):
@@ -1594,10 +1605,10 @@ def main():
         out["config"]["fused_steps_per_launch"] = fused
         out["roofline"]["note"] = (f"one launch advances {fused} time steps; bytes are per launch, so Mcells/s "
                                    f"exceeds what 16 B/cell/step allows at this bandwidth")
-    elif world == 1 and not args.force_dm_leg:
+    elif args.full and world == 1 and not args.force_dm_leg:
         if not args.no_temporal_blocking:
             guarded("temporal_blocking", lambda: temporal_blocking(D, torch, grid, a, stream, args.steps, args.tile))
-    else:
+    elif args.full:
         # N > 1 (or its 1-rank rehearsal): every secondary leg contains collectives, so a rank that
         # fails would leave the others waiting.  If a leg raises, or the legs have not finished in
         # 180 s, rank 0 prints the line with what it has and EVERY rank leaves with a non-zero status:
@@ -1690,7 +1701,7 @@ def main():
                 except Exception as e:                       # noqa: BLE001
                     out["configs"].append({"tile": t, "DL_ESM_ALIGNMENT": al, "error": f"{type(e).__name__}: {e}"})
                     failed.append(f"configs[{t},A{al}]")
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # N > 1: a shorter sample (the other ranks wait at the barrier below), same tile, rank 0's cores
         host = a.get_data()
         out["cpu_baseline"] = cpu_baseline(host, grid.nx, it.box(), args.cpu_seconds if world == 1

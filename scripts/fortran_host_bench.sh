@@ -25,7 +25,7 @@ for mode in 0 1 2 3 4; do
     done
 done
 echo "# the same kernels hosted by Python/ctypes (bench.py, same box, same process launch):"
-timeout -k 10 400 python bench.py --no-cpu-baseline --no-temporal-blocking --no-weak-tile > /tmp/bench_fh.json 2>/dev/null
+timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-temporal-blocking --no-weak-tile > /tmp/bench_fh.json 2>/dev/null
 python - <<'PY'
 import json
 d = json.load(open("/tmp/bench_fh.json"))

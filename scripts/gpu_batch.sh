@@ -29,7 +29,7 @@ tests)
     tail -15 $OUT/gpu_tests.log ;;
 prof)
     rm -rf $OUT/prof_stats
-    step prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python3 bench.py --no-cpu-baseline > $OUT/prof_stats.log 2>&1
+    step prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python3 bench.py --full --no-cpu-baseline > $OUT/prof_stats.log 2>&1
     tail -2 $OUT/prof_stats.log
     python scripts/parse_rocprof.py stats $OUT/prof_stats $OUT/prof_stats_summary.md > /dev/null 2>&1 || echo "parse failed" ;;
 pmc)
@@ -50,7 +50,7 @@ benchx)
     step benchx 400 python bench.py --fused $F --steps $((F*25)) --no-cpu-baseline > $OUT/bench_fused$F.json 2> $OUT/bench_fused$F.err
     cat $OUT/bench_fused$F.json ;;
 bench)
-    step bench 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+    step bench 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
     cat $OUT/bench.json ;;
 smoke)
     step smoke 200 python __graft_entry__.py smoke ;;
@@ -113,7 +113,7 @@ configs)
     : > $OUT/configs.jsonl
     for cfg in "4096 64" "8192 64" "16384 64" "16384 1" "4096 1"; do
         set -- $cfg
-        step "cfg$1a$2" 300 python bench.py --tile $1 --alignment $2 --steps 100 --warmup 10 --cpu-seconds 4 >> $OUT/configs.jsonl 2>> $OUT/configs.err
+        step "cfg$1a$2" 300 python bench.py --tile $1 --alignment $2 --steps 100 --warmup 10 --full --cpu-seconds 4 >> $OUT/configs.jsonl 2>> $OUT/configs.err
     done
     python - <<'PYEOF'
 import json
@@ -135,7 +135,7 @@ membench)
 pmcmulti)   # one counter per pass, default bench (single-step kernel + the fused-4 secondary leg)
     rm -rf $OUT/pmcmulti
     for cnt in ${PMC_LIST:-VALUBusy MemUnitStalled TCC_HIT_sum TCC_MISS_sum MeanOccupancyPerActiveCU SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU TCP_TCC_READ_REQ_sum}; do
-        step pmc_$cnt 200 rocprofv3 --pmc $cnt --output-format csv -d $OUT/pmcmulti/$cnt -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline > $OUT/pmcmulti_$cnt.log 2>&1
+        step pmc_$cnt 200 rocprofv3 --pmc $cnt --output-format csv -d $OUT/pmcmulti/$cnt -- python3 bench.py --steps 8 --warmup 2 --full --no-cpu-baseline > $OUT/pmcmulti_$cnt.log 2>&1
     done
     python scripts/pmc_table.py $OUT/pmcmulti jacobi5_tile jacobi5xt_tile > $OUT/pmcmulti_table.txt 2>&1
     cat $OUT/pmcmulti_table.txt ;;

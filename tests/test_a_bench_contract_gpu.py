@@ -31,8 +31,23 @@ def _bench(*flags):
     return json.loads(lines[0])
 
 
-def test_bench_line_and_secondary_legs():
+def test_plain_run_is_the_headline_alone():
+    """without --full the line carries the headline and nothing that needs a run of its own: no secondary leg, no CPU
+    baseline, no copy ceiling; at N > 1 (here its 1-rank rehearsal) the self-check that decides the timed form still runs,
+    the DLESM_DM_SAFE re-run after timing does not"""
+    legs = {"temporal_blocking", "copy_ceiling", "shallow_water", "weak_scaling_tile", "dm_loopback", "configs",
+            "peer_transport", "shallow_water_dm", "secondary_legs_error"}
     d = _bench()
+    assert KEYS <= set(d) and d["n_gpus"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0, d
+    assert d["cpu_baseline"] is None and not legs & set(d), sorted(legs & set(d))
+    assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1 and "frac_of_copy_ceiling" not in d["roofline"]
+    r = _bench("--force-dm-leg")
+    assert r["dm_step_equals_stencil_plus_exchange"] is True and r["dm_selfcheck_steps"] == 50, r
+    assert r["dm_safe_rerun"] is None and r["cpu_baseline"] is None and not legs & set(r), sorted(legs & set(r))
+
+
+def test_bench_line_and_secondary_legs():
+    d = _bench("--full")
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["unit"] == "Mcells/s" and d["dtype"] == "f64"
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
@@ -80,7 +95,8 @@ def test_reference_default_alignment():
     """DL_ESM_ALIGNMENT unset is the reference's default (grid_mod.f90:349-369): ld = N + 3, odd for even N, so nx * ny is
     odd -- round 3's `bench.py --alignment 1` left with status 5 because the copy-ceiling legs handed that odd count to a
     sweep of 16-byte elements.  Every leg that times a copy ceiling must come back, headline and shallow-water alike."""
-    d = _bench("--alignment", "1", "--no-cpu-baseline", "--no-temporal-blocking", "--no-configs", "--no-weak-tile", "--no-peer")
+    d = _bench("--full", "--alignment", "1", "--no-cpu-baseline", "--no-temporal-blocking", "--no-configs", "--no-weak-tile",
+               "--no-peer")
     assert d["config"]["ld"] % 2 == 1 and "secondary_legs_error" not in d, d.get("secondary_legs_error")
     assert d["copy_ceiling"]["best_gbs"] > 0 and 0 < d["roofline"]["frac_of_copy_ceiling"] < 2, d["copy_ceiling"]
     sw = d["shallow_water"]
@@ -129,7 +145,7 @@ def test_dump_outputs_is_the_last_timed_step(tmp_path, tile):
 
 
 def test_rehearsal_of_the_multi_gpu_secondary_leg():
-    d = _bench("--force-dm-leg", "--no-cpu-baseline")
+    d = _bench("--full", "--force-dm-leg", "--no-cpu-baseline")
     assert d["dm_form"] == "timeloop" and d["dm_selfcheck_steps"] == 50 and d["dm_step_equals_stencil_plus_exchange"] is True, d
     assert d["dm_safe_rerun"]["fields_equal_on_every_rank"] is True and d["dm_safe_rerun"]["checksums_equal"] is True, d["dm_safe_rerun"]
     tb = d["temporal_blocking"]
@@ -163,8 +179,8 @@ def test_multi_rank_bench_in_mailbox_mode(world, form):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), DLESM_TRANSPORT="mailbox", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--tile", "2048",
-                                       "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--dm-form", form], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--dm-form", form],
+                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
         try:
