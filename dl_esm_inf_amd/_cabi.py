@@ -16,6 +16,7 @@ OK, EINVAL, ENODEV, EHIP, ERCCL, EABORT, ECOMMS = 0, -1, -2, -3, -4, -5, -12
 # dirs_mask of dlesm_halo_exchange_f64: bit d-1 per edge direction; 0 exchanges nothing
 PEER_BLOB_BYTES = 1024
 DIRS_ALL, DIRS_NO_DIAGONALS = 0xF, 0x10
+NORM_MAX, NORM_SUMSQ = 0, 1           # dlesm_stencil5_resid_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
 
 
@@ -128,6 +129,7 @@ PROTOTYPES = {
     "dlesm_write_to_device": (None, [_vp, _vp, _i, _i, _i, _i, C.c_bool]),
     "dlesm_transfer_sync": (_i, []),
     "dlesm_stencil5_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dlesm_stencil5_resid_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dlesm_stencil5_planned_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "dlesm_continuity_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_momentum_u_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_vp]),
@@ -226,6 +228,7 @@ PROTOTYPES = {
                                     C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
     "dlesm_shallow_step_smooth_dm_pipelined": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_global_sum_f64": (_i, [C.POINTER(_d)]),
+    "dlesm_global_max_f64": (_i, [C.POINTER(_d)]),
     "dlesm_gather_f64": (_i, [_vp, _vp, _i]),
     "dlesm_pack_inner_f64": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_long, _vp]),
     "dlesm_unpack_gathered_f64": (_i, [_vp, C.c_long, C.POINTER(Decomp), C.POINTER(Subdomain), _i, _vp, _vp]),

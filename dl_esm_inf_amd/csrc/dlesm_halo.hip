@@ -1967,6 +1967,38 @@ extern "C" int dlesm_global_sum_f64(double *value)
     return DLESM_OK;
 }
 
+// max over the ranks: the values gathered (the board, or one double per rank all-gathered over RCCL -- not ncclMax, whose
+// NaN behaviour is unspecified), then the max in rank order on the host, a NaN winning
+extern "C" int dlesm_global_max_f64(double *value)
+{
+    DLESM_REQUIRE(value != nullptr, "null pointer");
+    if (g_size <= 1) return DLESM_OK;
+    std::vector<double> all(g_size);
+    if (g_mailbox) {
+        if (int rc = dlesm_board_allgather(value, sizeof(double), all.data())) return rc;
+    } else {
+        if (int rc = ensure_device()) return rc;
+        static double *d = nullptr;
+        static int d_n = 0;
+        if (d_n < g_size + 1) {
+            if (d) DLESM_HIP_TRY(hipFree(d));
+            d = nullptr, d_n = 0;
+            DLESM_HIP_TRY(hipMalloc((void **)&d, (size_t)(g_size + 1) * sizeof(double)));
+            d_n = g_size + 1;
+        }
+        hipStream_t s = side_stream();
+        DLESM_HIP_TRY(hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, s));
+        DLESM_NCCL_TRY(ncclAllGather(d, d + 1, 1, ncclDouble, g_comm, s));
+        DLESM_HIP_TRY(hipMemcpyAsync(all.data(), d + 1, (size_t)g_size * sizeof(double), hipMemcpyDeviceToHost, s));
+        DLESM_HIP_TRY(hipStreamSynchronize(s));
+    }
+    double m = all[0];
+    for (int r = 1; r < g_size; r++)
+        if (m == m && (all[r] > m || all[r] != all[r])) m = all[r];     // (the first NaN stays)
+    *value = m;
+    return DLESM_OK;
+}
+
 // MPI_Gather in mailbox mode: the root publishes an IPC handle of its receive buffer over the board, every other rank maps
 // it and copies its block STRAIGHT into its slot (one device-to-device copy over xGMI), a second round of the board tells
 // the root that all blocks have landed.  A root buffer that cannot be exported (not a hipMalloc allocation) takes the

@@ -234,12 +234,68 @@ __global__ __launch_bounds__(256) void jacobi5_march(const double *__restrict__ 
 // Per-XCD row bands and an XCD-affine column-major tile order were built, measured
 // (70 %, 69-70 % against 75-78 %; profiles/r01_sweep_tile_group.txt) and removed.
 // ===========================================================================
+// Residual of a step (dlesm_stencil5_resid_f64): RES = 1 + DLESM_NORM_MAX (max|out - in|, a NaN wins) or
+// 1 + DLESM_NORM_SUMSQ (SUM (out - in)^2); 0 = none.
+template <int RES>
+__device__ __forceinline__ double resid_combine(double a, double b)
+{
+    if constexpr (RES == 1 + DLESM_NORM_MAX) return (a > b || a != a) ? a : b;   // not fmax: that drops a NaN
+    else return a + b;
+}
+
+// this lane's share of one output row: its masked cells' |d| (max) or d*d (sum), column 2c before 2c+1
+template <int VEC, int RES>
+__device__ __forceinline__ double resid_lane(const double (&o)[VEC], const Vec<VEC> &mid, bool m0, bool m1)
+{
+    const double d0 = m0 ? o[0] - mid.v[0] : 0.0;
+    if constexpr (RES == 1 + DLESM_NORM_MAX) {
+        if constexpr (VEC == 2) return resid_combine<RES>(fabs(d0), m1 ? fabs(o[1] - mid.v[1]) : 0.0);
+        else return fabs(d0);
+    } else {
+        if constexpr (VEC == 2) {
+            const double d1 = m1 ? o[1] - mid.v[1] : 0.0;
+            return d0 * d0 + d1 * d1;
+        } else {
+            return d0 * d0;
+        }
+    }
+}
+
+// v combined with the value of the lane the DPP control CTRL names
+template <int RES, int CTRL>
+__device__ __forceinline__ double resid_dpp(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return resid_combine<RES>(v, __hiloint2double(__builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false),
+                                                  __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false)));
+}
+
+// A fixed reduction over the 64 lanes on the VALU (no LDS round trips at the end of these short-lived waves): within each
+// row of 16 lanes a butterfly by DPP -- xor 1 and xor 2 (quad permutes), then the half-row and row mirrors; every lane of
+// a row ends with the same bits, as a + b == b + a -- then the four rows' values read into scalars and combined as
+// (row 0 . row 1) . (row 2 . row 3).  The result is the same in every lane.
+template <int RES>
+__device__ __forceinline__ double resid_wave(double v)
+{
+    v = resid_dpp<RES, 0xB1>(v);                       // quad_perm [1,0,3,2]
+    v = resid_dpp<RES, 0x4E>(v);                       // quad_perm [2,3,0,1]
+    v = resid_dpp<RES, 0x141>(v);                      // row_half_mirror
+    v = resid_dpp<RES, 0x140>(v);                      // row_mirror
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto row = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)); };
+    return resid_combine<RES>(resid_combine<RES>(row(0), row(16)), resid_combine<RES>(row(32), row(48)));
+}
+
 // NT: cache policy -- bit 0: non-temporal loads, bit 1: non-temporal stores.  Loads never pay (the rows are
 // re-read by the tile below); stores do once the two arrays no longer fit the Infinity Cache -- see launch_tile.
-template <int VEC, int R, int NT>
+// RES != 0: also one residual partial per (row, 64-lane column group xw) into partial[(row - y0) * nxr + xw], nxr
+// being the number of groups that hold box columns: an order fixed by (box, lane width) alone, whatever the tile
+// height, the waves per group or the padding tiles (which write nothing).
+template <int VEC, int R, int NT, int RES = 0>
 __device__ __forceinline__ void jacobi5_tile_body(const double *__restrict__ in, double *__restrict__ out,
                                                   int ld, int x0, int x1, int y0, int y1, int c_first,
-                                                  int nxw, int flags, unsigned block)
+                                                  int nxw, int flags, unsigned block,
+                                                  double *__restrict__ partial = nullptr, int nxr = 0)
 {
     const int lane = threadIdx.x & 63;
 #if DLESM_J5_SCALAR
@@ -283,12 +339,24 @@ __device__ __forceinline__ void jacobi5_tile_body(const double *__restrict__ in,
         r[u] = load_chunk<VEC, (NT & 1) != 0>(pin + (size_t)jj * ld);
         e[u] = ecol >= 0 ? in[(size_t)jj * ld + ecol] : 0.0;
     }
+    [[maybe_unused]] double res[R];
 #pragma unroll
     for (int u = 0; u < R; u++) {
         if (jb + u <= je) {
             double o[VEC];
             jacobi_row<VEC>(r[u], r[u + 1], r[u + 2], e[u + 1], lane, o);
             store_chunk<VEC, (NT & 2) != 0>(pout + (size_t)(jb + u) * ld, o, m0, m1);
+            if constexpr (RES != 0) res[u] = resid_lane<VEC, RES>(o, r[u + 1], m0, m1);
+        }
+    }
+    if constexpr (RES != 0) {
+        // (c <= c_ld wherever m0 or m1 holds -- the box keeps its ring inside the row -- so r[u + 1] is the centre)
+#pragma unroll
+        for (int u = 0; u < R; u++) {
+            if (jb + u <= je) {
+                const double v = resid_wave<RES>(res[u]);
+                if (lane == 0) partial[(size_t)(jb + u - y0) * nxr + xw] = v;
+            }
         }
     }
 }
@@ -299,6 +367,15 @@ __global__ __launch_bounds__(1024) void jacobi5_tile(const double *__restrict__ 
                                                     int y0, int y1, int c_first, int nxw, int flags)
 {
     jacobi5_tile_body<VEC, R, NT>(in, out, ld, x0, x1, y0, y1, c_first, nxw, flags, blockIdx.x);
+}
+
+// the sweep of dlesm_stencil5_resid_f64: jacobi5_tile's stores, plus the residual partials
+template <int VEC, int R, int NT, int RES>
+__global__ __launch_bounds__(1024) void jacobi5_tile_resid(const double *__restrict__ in, double *__restrict__ out, int ld,
+                                                          int x0, int x1, int y0, int y1, int c_first, int nxw,
+                                                          double *__restrict__ partial, int nxr)
+{
+    jacobi5_tile_body<VEC, R, NT, RES>(in, out, ld, x0, x1, y0, y1, c_first, nxw, 0, blockIdx.x, partial, nxr);
 }
 
 // WT: store with device-scope write-through (relaxed agent-scope atomic stores), for frame cells that
@@ -820,22 +897,37 @@ int nt_stores_for(int ld, int y0, int y1)
     return t >= 0 ? (t != 0) : (size_t)ld * (size_t)(y1 - y0 + 3) * sizeof(double) >= ((size_t)150 << 20);
 }
 
-template <int VEC, bool NT>
+// Wave tiles per row of the box columns x0..x1 (0-based) with VEC-double lanes, the first one anchored on a 128-byte line
+// at chunk *c_first -- before any padding; also the residual sweep's partials per row.
+static int tile_columns(int x0, int x1, int vec, int *c_first)
+{
+    *c_first = (x0 / vec) & ~(128 / (8 * vec) - 1);
+    return (x1 / vec - *c_first + 64) / 64;
+}
+
+// RES != 0 (dlesm_stencil5_resid_f64): the residual sweep, partials into `partial` (jacobi5_tile_body); always a product
+// tile height, in the lab build too.
+template <int VEC, bool NT, int RES = 0>
 static void launch_tile(const double *in, double *out, int ld, int x0, int x1, int y0, int y1, int R,
-                        int flags, hipStream_t s, FrameJob *fj = nullptr, PeerJob *pj = nullptr)
+                        int flags, hipStream_t s, FrameJob *fj = nullptr, PeerJob *pj = nullptr,
+                        double *partial = nullptr)
 {
 #ifdef DLESM_LAB
-    if (R != 1 && R != 2 && R != 3 && R != 4 && R != 6 && R != 12 && R != 16) R = 8;
-#else
+    if (RES == 0) {
+        if (R != 1 && R != 2 && R != 3 && R != 4 && R != 6 && R != 12 && R != 16) R = 8;
+    } else
+#endif
+    {
     // the product's tile heights: 2 or 3 rows with 16-byte lanes (the planning call chooses), 4 rows with the 8-byte-lane
     // fall-back; the other heights were comparison points and live in libdlesm_hip_lab.so
     if (VEC == 2) { if (R != 3) R = 2; }
     else R = 4;
-#endif
+    }
     // tiles are anchored on a 128-byte line of the row (not on the first interior column), so
     // every wave access covers whole lines whatever the box: lanes left of x0 are masked
-    const int c_first = (x0 / VEC) & ~(128 / (8 * VEC) - 1), c_last = x1 / VEC;
-    int nxw = (c_last - c_first + 64) / 64;             // wave tiles per row
+    int c_first;
+    int nxw = tile_columns(x0, x1, VEC, &c_first);       // wave tiles per row
+    const int nxr = nxw;                                 // of which hold box columns (residual partials per row)
     int tpb = 4;                                         // tiles (waves) per block
     // Blocks go round-robin to the 8 XCDs, so the tile below a given tile runs on the XCD
     // (blocks per row) mod 8 further on: the re-read of the shared rows is an L2 hit only when
@@ -890,6 +982,19 @@ static void launch_tile(const double *in, double *out, int ld, int x0, int x1, i
                 hipLaunchKernelGGL((jacobi5_tile_framed<2, 2, 0>), dim3(grid + fj->nblocks), dim3(64 * tpb), 0, s, in,
                                    out, ld, x0, x1, y0, y1, c_first, nxw, flags, *fj);
         }
+        return;
+    }
+    if constexpr (RES != 0) {   // the product instantiations of the plain sweep below, with the residual
+#define DLESM_RESID(V, RR, N)                                                                                          \
+    hipLaunchKernelGGL((jacobi5_tile_resid<V, RR, N, RES>), dim3(grid), dim3(64 * tpb), 0, s, in, out, ld, x0, x1, y0, y1, \
+                       c_first, nxw, partial, nxr)
+        if constexpr (VEC == 2) {
+            if (nts) { if (R == 3) DLESM_RESID(2, 3, 2); else DLESM_RESID(2, 2, 2); }
+            else { if (R == 3) DLESM_RESID(2, 3, 0); else DLESM_RESID(2, 2, 0); }
+        } else {
+            DLESM_RESID(1, 4, 0);
+        }
+#undef DLESM_RESID
         return;
     }
     // (capping the resident waves with unused LDS -- 32 down to 16 waves per CU -- changes nothing
@@ -1019,6 +1124,14 @@ static int auto_rows(int ncols_vec, int height)
 
 #endif // DLESM_LAB
 
+// 16-byte lanes for this (in, out, ld, east box column x1)?  variant: j5_variant bits 4 (8-byte lanes) and 16 (no 16-byte
+// lanes on an odd pitch).
+static bool stencil5_lanes16(const double *in, const double *out, int ld, int x1, int variant)
+{
+    const bool odd_ok = !(variant & 16) && x1 + 1 <= 2 * (ld / 2) - 1;
+    return !(variant & 4) && ((ld % 2 == 0) || odd_ok) && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0);
+}
+
 int launch_stencil5(const double *in, double *out, int ld, int ny, int xstart, int xstop, int ystart,
                     int ystop, hipStream_t s)
 {
@@ -1040,9 +1153,7 @@ int launch_stencil5(const double *in, double *out, int ld, int ny, int xstart, i
     // every other row is then only 8-byte aligned, which global_load/store_dwordx4 accept --
     // 72 % of HBM peak at 16384^2 against 67 % with 8-byte lanes (variant bit 16 turns it off).
     // Only when the box's east ring column is still inside the last whole 2-column chunk.
-    const bool odd_ok = !(variant & 16) && x1 + 1 <= 2 * (ld / 2) - 1;
-    const bool vec2 = !(variant & 4) && ((ld % 2 == 0) || odd_ok) && ((uintptr_t)in % 16 == 0) &&
-                      ((uintptr_t)out % 16 == 0);
+    const bool vec2 = stencil5_lanes16(in, out, ld, x1, variant);
     if (tuning("j5_kernel", 0) == 0) { // XCD band sweep (default)
         // rows per tile: 2 for 16-byte lanes, 4 for the 8-byte-lane fallback (measured, scripts/size_probe.py)
         int R = tuning("j5_tile_rows", 0);
@@ -1657,6 +1768,22 @@ __global__ __launch_bounds__(256) void sum_partials(const double *__restrict__ p
     if (threadIdx.x == 0) *result = acc;
 }
 
+// one level of the fixed tree over the residual partials of dlesm_stencil5_resid_f64: workgroup b combines
+// partial[b*chunk .. (b+1)*chunk) -- per lane in index order, then the lanes by resid_wave, then the four waves
+template <int RES>
+__global__ __launch_bounds__(256) void resid_partials_level(const double *__restrict__ partial, long n, int chunk,
+                                                            double *__restrict__ out)
+{
+    __shared__ double wv[4];
+    const long lo = (long)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    double acc = 0.0;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) acc = resid_combine<RES>(acc, partial[i]);
+    acc = resid_wave<RES>(acc);
+    if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = resid_combine<RES>(resid_combine<RES>(wv[0], wv[1]), resid_combine<RES>(wv[2], wv[3]));
+}
+
 static std::mutex g_scratch_mu;
 static double *g_partials = nullptr; // 4096 partials + 1 result
 static const int kMaxPartials = 4096;
@@ -1686,13 +1813,11 @@ extern "C" int dlesm_stencil5_autotune_f64(const double *in, double *out, int ld
     if (int rc = launch_stencil5(in, out, ld, ny, xstart, xstop, ystart, ystop, s)) return rc;   // validates, warms
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
     const int variant = tuning("j5_variant", 0) & (kLab ? ~0 : 0x14);
-    const bool odd_ok = !(variant & 16) && x1 + 1 <= 2 * (ld / 2) - 1;
-    const bool vec2 = !(variant & 4) && ((ld % 2 == 0) || odd_ok) && ((uintptr_t)in % 16 == 0) &&
-                      ((uintptr_t)out % 16 == 0);
+    const bool vec2 = stencil5_lanes16(in, out, ld, x1, variant);
     if (tuning("j5_kernel", 0) != 0) return DLESM_OK;            // only the default kernel has shapes
     const int VEC = vec2 ? 2 : 1;
-    const int c_first = (x0 / VEC) & ~(128 / (8 * VEC) - 1), c_last = x1 / VEC;
-    const int nxw = (c_last - c_first + 64) / 64;
+    int c_first;
+    const int nxw = tile_columns(x0, x1, VEC, &c_first);
     if (nxw < 8) return DLESM_OK;                                 // thin boxes: nothing to choose
     std::vector<Shape> cand;
     auto add = [&](int tpb, int t, int rows) {
@@ -2011,6 +2136,75 @@ extern "C" int dlesm_checksum_async_f64(const double *f, int ld, int ny, int xst
     const int rc = enqueue_checksum(f, ld, xstart - 1, ystart - 1, nx, nyb, scratch, result_dev, s);
     DLESM_HIP_TRY(hipFreeAsync(scratch, s));
     return rc;
+}
+
+// Levels of 4096 over the n residual partials until one value is left, that one into *result_dev; `next` has room for
+// the intermediate levels (resid_tree_doubles).
+template <int RES>
+static void enqueue_resid_tree(const double *partial, long n, double *next, double *result_dev, hipStream_t s)
+{
+    for (;;) {
+        const long nb = (n + 4095) / 4096;
+        double *dst = nb == 1 ? result_dev : next;
+        hipLaunchKernelGGL(resid_partials_level<RES>, dim3((unsigned)nb), dim3(256), 0, s, partial, n, 4096, dst);
+        if (nb == 1) return;
+        partial = next;
+        next += nb;
+        n = nb;
+    }
+}
+
+static long resid_tree_doubles(long n)
+{
+    long need = 0;
+    for (n = (n + 4095) / 4096; n > 1; n = (n + 4095) / 4096) need += n;
+    return need;
+}
+
+// The Jacobi step with its residual: jacobi5_tile with the residual compiled in writes one partial
+// per (box row, 64-lane column group), and a fixed tree reduces them into *result_dev -- all on `stream`, scratch
+// stream-ordered as in dlesm_checksum_async_f64.  The launch shape is chosen exactly as for dlesm_stencil5_f64.
+extern "C" int dlesm_stencil5_resid_f64(const double *in, double *out, int ld, int ny, int xstart, int xstop, int ystart,
+                                        int ystop, int norm, double *result_dev, void *stream)
+{
+    if (int rc = ensure_device()) return rc;
+    DLESM_REQUIRE(norm == DLESM_NORM_MAX || norm == DLESM_NORM_SUMSQ, "dlesm_stencil5_resid_f64: unknown norm %d", norm);
+    DLESM_REQUIRE(in != nullptr && out != nullptr && result_dev != nullptr, "dlesm_stencil5_resid_f64: null pointer");
+    DLESM_REQUIRE(in != out, "dlesm_stencil5_resid_f64: in and out are the same array");
+    if (ld >= 1 && ny >= 1) {
+        const size_t bytes = (size_t)ld * (size_t)ny * sizeof(double);
+        const char *r = (const char *)result_dev;
+        auto inside = [&](const double *a) { return r + sizeof(double) > (const char *)a && r < (const char *)a + bytes; };
+        DLESM_REQUIRE(!inside(in) && !inside(out), "dlesm_stencil5_resid_f64: result_dev lies inside in or out");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (xstop < xstart || ystop < ystart) {
+        DLESM_HIP_TRY(hipMemsetAsync(result_dev, 0, sizeof(double), s));
+        return DLESM_OK;
+    }
+    if (int rc = check_box("dlesm_stencil5_resid_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
+    const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
+    // the product's lanes and tile heights, in the lab build too (j5_kernel and the lab-only variant bits do not apply)
+    const bool vec2 = stencil5_lanes16(in, out, ld, x1, tuning("j5_variant", 0) & 0x14);
+    int c_first;
+    const long np = (long)tile_columns(x0, x1, vec2 ? 2 : 1, &c_first) * (y1 - y0 + 1);   // = launch_tile's nxr * rows
+    int R = tuning("j5_tile_rows", 0);
+    if (R < 1) R = vec2 ? 2 : 4;
+    double *scratch = nullptr;
+    DLESM_HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)(np + resid_tree_doubles(np)) * sizeof(double), s));
+    if (norm == DLESM_NORM_MAX) {
+        if (vec2) launch_tile<2, false, 1 + DLESM_NORM_MAX>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);
+        else launch_tile<1, false, 1 + DLESM_NORM_MAX>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);
+        enqueue_resid_tree<1 + DLESM_NORM_MAX>(scratch, np, scratch + np, result_dev, s);
+    } else {
+        if (vec2) launch_tile<2, false, 1 + DLESM_NORM_SUMSQ>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);
+        else launch_tile<1, false, 1 + DLESM_NORM_SUMSQ>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);
+        enqueue_resid_tree<1 + DLESM_NORM_SUMSQ>(scratch, np, scratch + np, result_dev, s);
+    }
+    const hipError_t err = hipGetLastError();
+    DLESM_HIP_TRY(hipFreeAsync(scratch, s));
+    DLESM_HIP_TRY(err);
+    return DLESM_OK;
 }
 
 extern "C" int dlesm_probe_stream_concurrency(void *stream)

@@ -12,6 +12,8 @@ module dlesm_hip_mod
   integer, parameter :: DLESM_UNIQUE_ID_BYTES = 128
   !> dirs_mask values of dlesm_halo_exchange_f64 (include/dlesm_hip.h)
   integer(c_int), parameter :: DLESM_DIRS_ALL = 15_c_int, DLESM_DIRS_NO_DIAGONALS = 16_c_int
+  !> norm values of dlesm_stencil5_resid_f64
+  integer(c_int), parameter :: DLESM_NORM_MAX = 0_c_int, DLESM_NORM_SUMSQ = 1_c_int
 
   !> struct dlesm_region
   type, bind(C) :: c_region
@@ -167,6 +169,13 @@ module dlesm_hip_mod
        import :: c_int, c_ptr
        type(c_ptr), value :: in, out, stream
        integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       integer(c_int) :: rc
+     end function
+     function dlesm_stencil5_resid_f64(in, out, ld, ny, xstart, xstop, ystart, ystop, norm, result_dev, stream) &
+          bind(C, name="dlesm_stencil5_resid_f64") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: in, out, result_dev, stream
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop, norm
        integer(c_int) :: rc
      end function
      function dlesm_stencil9_f64(in, out, coef, ld, ny, xstart, xstop, ystart, ystop, stream) &
@@ -732,6 +741,11 @@ module dlesm_hip_mod
        integer(c_int) :: rc
      end function
      function dlesm_global_sum_f64(val) bind(C, name="dlesm_global_sum_f64") result(rc)
+       import :: c_int, c_double
+       real(c_double), intent(inout) :: val
+       integer(c_int) :: rc
+     end function
+     function dlesm_global_max_f64(val) bind(C, name="dlesm_global_max_f64") result(rc)
        import :: c_int, c_double
        real(c_double), intent(inout) :: val
        integer(c_int) :: rc

@@ -47,7 +47,7 @@ module dlesm_psy_mod
   implicit none
   private
 
-  public :: invoke_jacobi5_masked, invoke_jacobi5_dm_pipelined, halo_join, halo_connect_peers
+  public :: invoke_jacobi5_masked, invoke_jacobi5_dm_pipelined, halo_join, halo_connect_peers, invoke_jacobi5_residual
   public :: invoke_shallow_step_sw, invoke_periodic_halos, invoke_stencil9, invoke_stencil9_dm
   public :: invoke_jacobi5, invoke_jacobi5_dm, invoke_shallow_step, invoke_copy, invoke_hash_init
   public :: invoke_shallow_step_dm_pipelined, invoke_continuity
@@ -546,6 +546,54 @@ contains
                                          int(out%internal%ystop, c_int), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_jacobi5_dm_pipelined: ' // dlesm_error_text())
   end subroutine invoke_jacobi5_dm_pipelined
+
+  !> The step of invoke_jacobi5 (the same `out`, bit for bit) that also returns how far it moved the field over
+  !! out%internal on all ranks: max|out - in| (norm = 'max') or sqrt(SUM (out - in)**2) (norm = 'l2') -- what a solver
+  !! checks every few steps to know when to stop.  Synchronous.  Distributed: joins a pipelined step's exchange first and
+  !! leaves `out` with its depth-1 halos exchanged, as invoke_jacobi5_dm.
+  function invoke_jacobi5_residual(out, in, norm) result(r)
+    use parallel_comms_mod, only: halo_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    type(r2d_field), intent(inout), target :: out, in
+    character(len=*), intent(in) :: norm
+    real(go_wp) :: r
+    type(c_ptr), save :: dres = c_null_ptr          ! one device double, kept
+    real(c_double), target :: val
+    integer(c_int) :: rc, code
+    select case (norm)
+    case ('max')
+       code = DLESM_NORM_MAX
+    case ('l2')
+       code = DLESM_NORM_SUMSQ
+    case default
+       call gocean_stop("invoke_jacobi5_residual: norm '" // norm // "' is not 'max' or 'l2'")
+    end select
+    call need_device(in);  call need_device(out)
+    if (DIST_MEM_ENABLED) then
+       rc = dlesm_halo_plan_join(halo_plan_for(out%grid%nx, out%grid%ny), c_null_ptr)
+       if (rc /= 0) call gocean_stop('invoke_jacobi5_residual: ' // dlesm_error_text())
+    end if
+    if (.not. c_associated(dres)) then
+       if (hipMalloc(dres, int(c_sizeof(val), c_size_t)) /= 0) call gocean_stop('invoke_jacobi5_residual: hipMalloc failed')
+    end if
+    rc = dlesm_stencil5_resid_f64(field_device_data(in), field_device_data(out), &
+                                  int(out%grid%nx, c_int), int(out%grid%ny, c_int), &
+                                  int(out%internal%xstart, c_int), int(out%internal%xstop, c_int), &
+                                  int(out%internal%ystart, c_int), int(out%internal%ystop, c_int), code, dres, c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_jacobi5_residual: ' // dlesm_error_text())
+    if (DIST_MEM_ENABLED) call out%halo_exchange(1)
+    ! (hipMemcpy to pageable memory waits for the null stream, which the sweep and the exchange are on)
+    if (hipMemcpy(c_loc(val), dres, int(c_sizeof(val), c_size_t), 2_c_int) /= 0) &
+         call gocean_stop('invoke_jacobi5_residual: copy of the result failed')
+    if (code == DLESM_NORM_MAX) then
+       rc = dlesm_global_max_f64(val)
+    else
+       rc = dlesm_global_sum_f64(val)
+       val = sqrt(val)
+    end if
+    if (rc /= 0) call gocean_stop('invoke_jacobi5_residual: ' // dlesm_error_text())
+    r = val
+  end function invoke_jacobi5_residual
 
   !> COLLECTIVE, once per grid: connect the grid's message plan to the neighbours' mailboxes.  From then on
   !! invoke_jacobi5_dm / invoke_jacobi5_dm_pipelined exchange by storing straight into the neighbours' memory over

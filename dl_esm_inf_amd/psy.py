@@ -312,6 +312,39 @@ def invoke_jacobi5_dm_pipelined(out_fld, in_fld, stream=None):
                                                       _stream_ptr(stream)))
 
 
+def invoke_jacobi5_residual(out_fld, in_fld, norm="max", stream=None):
+    """the Jacobi step of invoke_jacobi5 (same `out`, bit for bit) that also says how far it moved the field over
+    out_fld%internal on all ranks: max|out - in| (norm="max") or sqrt(SUM (out - in)**2) (norm="l2").  Synchronous: what a
+    solver checks every few steps to know when to stop.  On a decomposed grid it first joins a pipelined step's exchange
+    (`in`'s halos) and leaves `out` with its depth-1 halos exchanged, as invoke_jacobi5_dm does."""
+    import torch
+
+    from . import parallel_mod
+    codes = {"max": _cabi.NORM_MAX, "l2": _cabi.NORM_SUMSQ}
+    if norm not in codes:
+        raise ValueError(f"invoke_jacobi5_residual: norm {norm!r} is not 'max' or 'l2'")
+    g, it = out_fld.grid, out_fld.internal
+    L = _cabi.lib()
+    dm = parallel_mod.get_num_ranks() > 1
+    if dm:
+        halo_join(g, stream)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    # the value lands in device memory allocated on the step's own stream and comes back by a copy on it -- not in torch's
+    # pinned host memory, which ROCm allocates non-coherent by default: a device store there may reach the host late
+    with torch.cuda.stream(s):
+        res = torch.empty(1, dtype=torch.float64, device=out_fld.data.device)
+        check(L.dlesm_stencil5_resid_f64(in_fld.device_ptr, out_fld.device_ptr, g.nx, g.ny, it.xstart, it.xstop,
+                                         it.ystart, it.ystop, codes[norm], C.c_void_p(res.data_ptr()), _stream_ptr(s)))
+        if dm:
+            out_fld.halo_exchange(1, stream=s)
+        val = C.c_double(res.item())                        # (a copy on `s` that the host waits for)
+    if norm == "max":
+        check(L.dlesm_global_max_f64(C.byref(val)))
+        return val.value
+    check(L.dlesm_global_sum_f64(C.byref(val)))
+    return math.sqrt(val.value)
+
+
 def halo_connect_peers(grid, nfields=1):
     """collective: connect the grid's plan to the neighbours' mailboxes (grid_mod.connect_peers) -- the distributed
     Jacobi steps then exchange with stores over xGMI instead of an RCCL group"""

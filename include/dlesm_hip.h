@@ -207,6 +207,21 @@ int dlesm_transfer_sync(void);
 int dlesm_stencil5_f64(const double *in, double *out, int ld, int ny,
                        int xstart, int xstop, int ystart, int ystop, void *stream);
 
+/* The same step, reporting how far it moved the field: with d = out - in over the box (xstart:xstop, ystart:ystop),
+ *   norm = DLESM_NORM_MAX:   max |d|  -- exact; a NaN d gives NaN (as numpy.max; fmax would drop it), an infinite one inf;
+ *   norm = DLESM_NORM_SUMSQ: SUM d*d  -- summed in an order fixed by (ld, box, lane width) alone: the launch shape, the
+ *                            planning call and the padding do not change its bits (16- or 8-byte lanes may).
+ * `out` is bit for bit what dlesm_stencil5_f64 writes, and no other cell changes.  *result_dev -- device memory, or host
+ * memory the device can write (hipHostMalloc) -- receives the value when `stream` gets there, with no host
+ * synchronisation; the scratch space is stream-ordered, as for dlesm_checksum_async_f64.  An empty box writes 0.0 and
+ * launches no sweep.  DLESM_EINVAL, before anything is launched: a box that does not fit with its one-cell ring,
+ * in == out, a null result_dev, a result_dev inside `in` or `out`, an unknown norm.  Combine across ranks with
+ * dlesm_global_max_f64 / dlesm_global_sum_f64.  Not callable under stream capture. */
+enum { DLESM_NORM_MAX = 0, DLESM_NORM_SUMSQ = 1 };
+int dlesm_stencil5_resid_f64(const double *in, double *out, int ld, int ny,
+                             int xstart, int xstop, int ystart, int ystop,
+                             int norm, double *result_dev, void *stream);
+
 /* Optional planning call for dlesm_stencil5_f64 (in the manner of an FFT plan): times about a dozen
  * launch shapes (waves per workgroup, tiles per row, rows per tile) on the caller's own arrays -- each
  * is the same valid step in -> out, the results do not depend on the shape -- and remembers the fastest
@@ -890,6 +905,10 @@ int dlesm_nemolite_step_dm(dlesm_halo_plan *plan, const dlesm_momentum_params *p
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);
+/* In-place max of one host double over all ranks (synchronous); a NaN on any rank gives NaN on every rank.  One rank: a
+ * no-op.  Mailbox mode: gathered over the board; RCCL: one double per rank all-gathered; either way the max is taken on
+ * the host in rank order (not ncclMax, whose NaN behaviour is unspecified). */
+int dlesm_global_max_f64(double *value);
 /* gather, parallel_utils_mod.f90:242-255: n doubles per rank (device memory)
  * -> n*nranks doubles on rank 0 (device memory). Synchronous. */
 int dlesm_gather_f64(const double *send, double *recv, int n);
