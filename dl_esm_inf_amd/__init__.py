@@ -11,7 +11,7 @@ Nothing here falls back to the CPU: without the built library the import fails, 
 every device entry point raises.
 """
 from . import _cabi
-from ._cabi import DlesmError, GoceanStop  # noqa: F401
+from ._cabi import DlesmError, GoceanStop, FieldStats  # noqa: F401
 
 _cabi.lib()  # fail loudly, at import time, if the HIP extension is missing
 
@@ -20,6 +20,6 @@ from .parallel_mod import (parallel_init, parallel_finalise, get_rank, get_num_r
 from .grid_mod import (grid_type, grid_init, GO_ARAKAWA_C, GO_ARAKAWA_B, GO_OFFSET_SW,  # noqa: E402,F401
                        GO_OFFSET_SE, GO_OFFSET_NW, GO_OFFSET_NE, GO_OFFSET_ANY,
                        GO_BC_PERIODIC, GO_BC_EXTERNAL, GO_BC_NONE)
-from .field_mod import (r2d_field, field_checksum, copy_field, set_field, free_field,  # noqa: E402,F401
+from .field_mod import (r2d_field, field_checksum, field_stats, field_locate, copy_field, set_field, free_field,  # noqa: E402,F401
                         GO_U_POINTS, GO_V_POINTS, GO_T_POINTS, GO_F_POINTS, GO_ALL_POINTS)
 from . import psy  # noqa: E402,F401

@@ -17,6 +17,8 @@ OK, EINVAL, ENODEV, EHIP, ERCCL, EABORT, ECOMMS = 0, -1, -2, -3, -4, -5, -12
 PEER_BLOB_BYTES = 1024
 DIRS_ALL, DIRS_NO_DIAGONALS = 0xF, 0x10
 NORM_MAX, NORM_SUMSQ = 0, 1           # dlesm_stencil5_resid_f64
+STATS_MAX_FIELDS = 8                  # dlesm_field_stats_async_f64
+LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
 
 
@@ -90,6 +92,19 @@ class SwParams(C.Structure):
 class MomentumParams(C.Structure):
     """dlesm_momentum_params"""
     _fields_ = [(n, C.c_double) for n in ("rdt", "cbfr", "visc", "g")]
+
+
+class FieldStats(C.Structure):
+    """dlesm_field_stats: what dlesm_field_stats_f64 says about one field"""
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("sum", C.c_double), ("sumsq", C.c_double),
+                ("count", C.c_int64), ("nonfinite", C.c_int64)]
+
+    def as6(self):
+        return (self.min, self.max, self.sum, self.sumsq, self.count, self.nonfinite)
+
+    def __repr__(self):
+        return (f"FieldStats(min={self.min!r}, max={self.max!r}, sum={self.sum!r}, sumsq={self.sumsq!r}, "
+                f"count={self.count}, nonfinite={self.nonfinite})")
 
 
 MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
@@ -175,6 +190,9 @@ PROTOTYPES = {
     "dlesm_fill_f64": (_i, [_vp, _i, _i, _i, _i, _i, _i, _d, _vp]),
     "dlesm_checksum_f64": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_d), _vp]),
     "dlesm_checksum_async_f64": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dlesm_field_stats_async_f64": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(Region), _i, _i, _i, _vp, _vp]),
+    "dlesm_field_stats_f64": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(Region), _i, _i, _i, C.POINTER(FieldStats), _vp]),
+    "dlesm_field_locate_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, C.POINTER(C.c_int64), _vp]),
     "dlesm_hash_init_f64": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.c_uint64, C.c_int64, C.c_int64, _vp]),
     "dlesm_set_tuning": (_i, [C.c_char_p, _i]),
     "dlesm_tuning_class": (_i, [C.c_char_p]),

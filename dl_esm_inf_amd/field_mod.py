@@ -137,6 +137,93 @@ def field_checksum(field, stream=None):
     return val.value
 
 
+def _mask_list(masks, n):
+    """masks of field_stats: None, one int32 device array for every field, or one entry (array or None) per field"""
+    if masks is None:
+        return [None] * n
+    if not isinstance(masks, (list, tuple)):
+        return [masks] * n
+    if len(masks) != n:
+        raise _cabi.DlesmError(_cabi.EINVAL, f"field_stats: {len(masks)} masks for {n} fields")
+    return list(masks)
+
+
+def _mask_ptr(mask, grid):
+    import torch
+    if mask is None:
+        return None
+    if mask.dtype != torch.int32 or tuple(mask.shape) != (grid.ny, grid.nx) or not mask.is_contiguous() or not mask.is_cuda:
+        raise _cabi.DlesmError(_cabi.EINVAL, "field_stats: a mask is a contiguous int32 device array of the field's shape "
+                                             "(grid.tmask_device)")
+    return mask.data_ptr()
+
+
+def field_stats(fields, masks=None, stream=None):
+    """min, max, SUM x, SUM x*x, the number of counted cells and how many of them are NaN or infinite, of 1 to 8 fields of
+    one grid, each over its `internal` region, in one sweep (dlesm_field_stats_async_f64) -> a list of
+    FieldStats, the same on every rank.  masks: None, one int32 device array in the field layout for all fields
+    (grid.tmask_device), or one entry per field (None: unmasked); only cells with mask > 0 are counted."""
+    import torch
+
+    from . import parallel_mod
+    fields = list(fields)
+    n = len(fields)
+    if not 1 <= n <= _cabi.STATS_MAX_FIELDS:
+        raise _cabi.DlesmError(_cabi.EINVAL, f"field_stats: {n} fields (1 to {_cabi.STATS_MAX_FIELDS})")
+    g = fields[0].grid
+    if any((f.grid.nx, f.grid.ny) != (g.nx, g.ny) for f in fields):
+        raise _cabi.DlesmError(_cabi.EINVAL, "field_stats: the fields are not of one array shape")
+    mlist = [_mask_ptr(m, g) for m in _mask_list(masks, n)]
+    fp = (C.c_void_p * n)(*[f.data.data_ptr() for f in fields])
+    mp = (C.c_void_p * n)(*mlist)
+    boxes = (Region * n)()
+    for k, f in enumerate(fields):
+        C.memmove(C.byref(boxes[k]), C.byref(f.internal), C.sizeof(Region))
+    L = _cabi.lib()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    # the numbers land in device memory allocated on the caller's stream and come back by a copy on it (see
+    # psy.invoke_jacobi5_residual for why torch's pinned host memory is not used)
+    with torch.cuda.stream(s):
+        res = torch.empty(6 * n, dtype=torch.float64, device=fields[0].data.device)
+        check(L.dlesm_field_stats_async_f64(fp, mp if any(m is not None for m in mlist) else None, boxes, n, g.nx, g.ny,
+                                            C.c_void_p(res.data_ptr()), _stream_ptr(s)))
+        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
+    out = (_cabi.FieldStats * n).from_buffer_copy(host.tobytes())
+    out = [out[k] for k in range(n)]
+    if parallel_mod.get_num_ranks() > 1:
+        def glob(fn, v):
+            val = C.c_double(v)
+            check(fn(C.byref(val)))
+            return val.value
+        for st in out:                                      # no NaN enters these collectives: see the definition of min .. sumsq
+            st.min = -glob(L.dlesm_global_max_f64, -st.min)
+            st.max = glob(L.dlesm_global_max_f64, st.max)
+            st.sum = glob(L.dlesm_global_sum_f64, st.sum)
+            st.sumsq = glob(L.dlesm_global_sum_f64, st.sumsq)
+            st.count = int(glob(L.dlesm_global_sum_f64, float(st.count)))          # exact below 2**53
+            st.nonfinite = int(glob(L.dlesm_global_sum_f64, float(st.nonfinite)))
+    return out
+
+
+def field_locate(field, what, value=None, mask=None, stream=None):
+    """where on THIS rank: the local 1-based (i, j) of the first cell (row by row) of field.internal, counted under `mask`
+    as in field_stats, that is NaN or infinite (what = "nonfinite") or that equals `value` (what = "equal": pass a min or
+    max of field_stats); None if there is none.  Synchronous; the rare path, after a check has tripped."""
+    codes = {"nonfinite": _cabi.LOCATE_NONFINITE, "equal": _cabi.LOCATE_EQUAL,
+             _cabi.LOCATE_NONFINITE: _cabi.LOCATE_NONFINITE, _cabi.LOCATE_EQUAL: _cabi.LOCATE_EQUAL}
+    if what not in codes:
+        raise ValueError(f"field_locate: what = {what!r} is not 'nonfinite' or 'equal'")
+    if codes[what] == _cabi.LOCATE_EQUAL and value is None:
+        raise ValueError("field_locate: 'equal' needs a value")
+    g, it = field.grid, field.internal
+    idx = C.c_int64(-1)
+    check(_cabi.lib().dlesm_field_locate_f64(field.device_ptr, _mask_ptr(mask, g), g.nx, g.ny, it.xstart, it.xstop, it.ystart,
+                                             it.ystop, codes[what], float(value or 0.0), C.byref(idx), _stream_ptr(stream)))
+    if idx.value < 0:
+        return None
+    return (idx.value % g.nx + 1, idx.value // g.nx + 1)
+
+
 def copy_field(field_in, field_out=None, src=None, dest=None, stream=None):
     """copy_field (field_mod.f90:1126-1187): whole-field copy, or patch copy src -> dest
     (Region objects) inside one field."""

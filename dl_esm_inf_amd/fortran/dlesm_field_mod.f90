@@ -107,6 +107,8 @@ module field_mod
   end interface
 
   public copy_field, set_field, field_checksum, free_field
+  ! what a time loop asks about a device-resident field every few steps (DESIGN.md section 5.5)
+  public :: field_stats, field_locate, field_stats_type, DLESM_LOCATE_NONFINITE, DLESM_LOCATE_EQUAL
 
   integer, public, parameter :: NBOUNDARY = 1
   logical, public, parameter :: TILED_FIELDS = .FALSE.
@@ -506,6 +508,82 @@ contains
       d => p%get_data()
     end subroutine sync_host
   end function fld_checksum
+
+  !> min, max, SUM x, SUM x*x over the finite cells of fld%internal, the number of cells counted and how many of them are
+  !! NaN or infinite -- over ALL ranks, as field_checksum is -- in one sweep on the device (dlesm_field_stats_f64).
+  !! mask: the grid's device tmask mirror (grid%tmask_device once grid_to_device has run); only cells with
+  !! tmask > 0 are then counted.
+  subroutine field_stats(fld, stats, mask)
+    type(r2d_field), intent(inout), target :: fld
+    type(field_stats_type), intent(out) :: stats
+    type(c_ptr), intent(in), optional :: mask
+    type(c_ptr), target :: fp(1), mp(1)
+    type(c_ptr) :: masks
+    type(c_region) :: box(1)
+    type(field_stats_type) :: res(1)
+    real(c_double) :: v
+    integer(c_int) :: rc
+    if (.not. fld%data_on_device) call field_to_device(fld)
+    if (.not. field_on_dlesm_device(fld)) call gocean_stop('field_stats: field lives on a foreign device')
+    fp(1) = field_device_data(fld)
+    masks = c_null_ptr
+    if (present(mask)) then
+       mp(1) = mask
+       masks = c_loc(mp)
+    end if
+    box(1) = c_region(int(fld%internal%nx, c_int), int(fld%internal%ny, c_int), &
+                      int(fld%internal%xstart, c_int), int(fld%internal%xstop, c_int), &
+                      int(fld%internal%ystart, c_int), int(fld%internal%ystop, c_int))
+    rc = dlesm_field_stats_f64(fp, masks, box, 1_c_int, int(size(fld%data, 1), c_int), int(size(fld%data, 2), c_int), &
+                               res, c_null_ptr)
+    if (rc /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
+    stats = res(1)
+    ! no NaN enters these collectives: min .. sumsq are over the finite cells; counts are exact as doubles below 2**53
+    v = -stats%min;  call gmax(v);  stats%min = -v
+    call gmax(stats%max)
+    call gsum(stats%sum)
+    call gsum(stats%sumsq)
+    v = real(stats%count, c_double);  call gsum(v);  stats%count = int(v, c_int64_t)
+    v = real(stats%nonfinite, c_double);  call gsum(v);  stats%nonfinite = int(v, c_int64_t)
+  contains
+    subroutine gsum(x)
+      real(c_double), intent(inout) :: x
+      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
+    end subroutine gsum
+    subroutine gmax(x)
+      real(c_double), intent(inout) :: x
+      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
+    end subroutine gmax
+  end subroutine field_stats
+
+  !> After a check has tripped: the local (i, j) of the first cell (row by row) of fld%internal ON THIS RANK, counted
+  !! under `mask` as in field_stats, that is NaN or infinite (what = DLESM_LOCATE_NONFINITE) or that equals `value`
+  !! (DLESM_LOCATE_EQUAL: pass stats%min or stats%max); i = j = 0 if there is none.
+  subroutine field_locate(fld, what, i, j, value, mask)
+    type(r2d_field), intent(inout), target :: fld
+    integer(c_int), intent(in) :: what
+    integer, intent(out) :: i, j
+    real(go_wp), intent(in), optional :: value
+    type(c_ptr), intent(in), optional :: mask
+    type(c_ptr) :: m
+    real(c_double) :: v
+    integer(c_int64_t) :: idx, ld
+    integer(c_int) :: rc
+    if (.not. fld%data_on_device) call field_to_device(fld)
+    if (.not. field_on_dlesm_device(fld)) call gocean_stop('field_locate: field lives on a foreign device')
+    m = c_null_ptr;  v = 0.0_c_double
+    if (present(mask)) m = mask
+    if (present(value)) v = value
+    rc = dlesm_field_locate_f64(field_device_data(fld), m, int(size(fld%data, 1), c_int), int(size(fld%data, 2), c_int), &
+                                int(fld%internal%xstart, c_int), int(fld%internal%xstop, c_int), &
+                                int(fld%internal%ystart, c_int), int(fld%internal%ystop, c_int), what, v, idx, c_null_ptr)
+    if (rc /= 0) call gocean_stop('field_locate: ' // dlesm_error_text())
+    i = 0;  j = 0
+    if (idx < 0) return
+    ld = size(fld%data, 1)
+    i = int(mod(idx, ld)) + 1
+    j = int(idx / ld) + 1
+  end subroutine field_locate
 
   function array_checksum(field, xstart, xstop, ystart, ystop) result(val)
     use parallel_comms_mod, only: global_sum

@@ -14,6 +14,9 @@ module dlesm_hip_mod
   integer(c_int), parameter :: DLESM_DIRS_ALL = 15_c_int, DLESM_DIRS_NO_DIAGONALS = 16_c_int
   !> norm values of dlesm_stencil5_resid_f64
   integer(c_int), parameter :: DLESM_NORM_MAX = 0_c_int, DLESM_NORM_SUMSQ = 1_c_int
+  !> `what` values of dlesm_field_locate_f64, and the most fields one dlesm_field_stats_f64 call takes
+  integer(c_int), parameter :: DLESM_LOCATE_NONFINITE = 0_c_int, DLESM_LOCATE_EQUAL = 1_c_int
+  integer(c_int), parameter :: DLESM_STATS_MAX_FIELDS = 8_c_int
 
   !> struct dlesm_region
   type, bind(C) :: c_region
@@ -52,6 +55,12 @@ module dlesm_hip_mod
   type, bind(C) :: c_momentum_grid
      type(c_ptr) :: tmask, dx_t, dy_t, dx_u, dy_u, dx_v, dy_v, area_u, area_v, fcor_u, fcor_v
   end type c_momentum_grid
+
+  !> struct dlesm_field_stats (DESIGN.md section 5.5): 48 bytes
+  type, bind(C) :: field_stats_type
+     real(c_double) :: min, max, sum, sumsq
+     integer(c_int64_t) :: count, nonfinite
+  end type field_stats_type
 
   interface
      ! ---- host-side index maps -------------------------------------------
@@ -533,6 +542,36 @@ module dlesm_hip_mod
        type(c_ptr), value :: f, stream
        integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
        real(c_double), intent(out) :: res
+       integer(c_int) :: rc
+     end function
+     function dlesm_field_stats_async_f64(fields, masks, boxes, nfields, ld, ny, result_dev, stream) &
+          bind(C, name="dlesm_field_stats_async_f64") result(rc)
+       import :: c_int, c_ptr, c_region
+       type(c_ptr), intent(in) :: fields(*)
+       type(c_ptr), value :: masks           ! NULL, or the address of nfields mask pointers
+       type(c_region), intent(in) :: boxes(*)
+       integer(c_int), value :: nfields, ld, ny
+       type(c_ptr), value :: result_dev, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_field_stats_f64(fields, masks, boxes, nfields, ld, ny, result_host, stream) &
+          bind(C, name="dlesm_field_stats_f64") result(rc)
+       import :: c_int, c_ptr, c_region, field_stats_type
+       type(c_ptr), intent(in) :: fields(*)
+       type(c_ptr), value :: masks
+       type(c_region), intent(in) :: boxes(*)
+       integer(c_int), value :: nfields, ld, ny
+       type(field_stats_type), intent(out) :: result_host(*)
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_field_locate_f64(f, mask, ld, ny, xstart, xstop, ystart, ystop, what, val, index_host, stream) &
+          bind(C, name="dlesm_field_locate_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_int64_t
+       type(c_ptr), value :: f, mask, stream
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop, what
+       real(c_double), value :: val
+       integer(c_int64_t), intent(out) :: index_host
        integer(c_int) :: rc
      end function
      function dlesm_hash_init_f64(f, ld, ny, xstart, xstop, ystart, ystop, seed, gx0, gy0, stream) &

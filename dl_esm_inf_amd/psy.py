@@ -345,6 +345,48 @@ def invoke_jacobi5_residual(out_fld, in_fld, norm="max", stream=None):
     return math.sqrt(val.value)
 
 
+def run_health(fields, names, masks=None, max_abs=None, stream=None):
+    """the check a time loop makes every few steps (NEMO's stp_ctl): ONE field_stats call over the fields' internal regions
+    (masks as in field_mod.field_stats); returns the list of FieldStats, the same on every rank.  Raises DlesmError -- on
+    every rank -- when a field holds a NaN or an infinity on any rank, or when max(|min|, |max|) of field k exceeds
+    max_abs[k] (max_abs: None, one bound for all fields, or one entry per field, None = no bound).  The message names the
+    field, the lowest rank (1-based, parallel_mod.get_rank) that holds an offending cell and the local 1-based (i, j) of
+    its first such cell."""
+    from . import field_mod, parallel_mod
+    fields, names = list(fields), list(names)
+    if len(names) != len(fields):
+        raise ValueError(f"run_health: {len(names)} names for {len(fields)} fields")
+    if max_abs is None or not isinstance(max_abs, (list, tuple)):
+        max_abs = [max_abs] * len(fields)
+    if len(max_abs) != len(fields):
+        raise ValueError(f"run_health: {len(max_abs)} bounds for {len(fields)} fields")
+    stats = field_mod.field_stats(fields, masks, stream)
+    mlist = field_mod._mask_list(masks, len(fields))
+    for k, (st, name) in enumerate(zip(stats, names)):
+        if st.nonfinite > 0:
+            what, value, why = "nonfinite", None, f"{st.nonfinite} cell(s) NaN or infinite"
+        elif max_abs[k] is not None and max(abs(st.min), abs(st.max)) > max_abs[k] and st.count > st.nonfinite:
+            value = st.max if abs(st.max) >= abs(st.min) else st.min
+            what, why = "equal", f"|{value!r}| exceeds {max_abs[k]!r}"
+        else:
+            continue
+        here = field_mod.field_locate(fields[k], what, value, mlist[k], stream)
+        rank, (i, j) = parallel_mod.get_rank(), here or (0, 0)
+        if parallel_mod.get_num_ranks() > 1:
+            L = _cabi.lib()
+
+            def glob(fn, v):
+                val = C.c_double(v)
+                check(fn(C.byref(val)))
+                return val.value
+            owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if here else -1.0e9))
+            i = int(glob(L.dlesm_global_sum_f64, float(i) if rank == owner else 0.0))
+            j = int(glob(L.dlesm_global_sum_f64, float(j) if rank == owner else 0.0))
+            rank = owner
+        raise _cabi.DlesmError(_cabi.EABORT, f"run_health: field {name}: {why}; first at local (i, j) = ({i}, {j}) on rank {rank}")
+    return stats
+
+
 def halo_connect_peers(grid, nfields=1):
     """collective: connect the grid's plan to the neighbours' mailboxes (grid_mod.connect_peers) -- the distributed
     Jacobi steps then exchange with stores over xGMI instead of an RCCL group"""

@@ -563,6 +563,43 @@ int dlesm_checksum_f64(const double *f, int ld, int ny, int xstart, int xstop,
  * full device-to-host copy of the field per call, :538); combine across ranks afterwards (dlesm_global_sum_f64). */
 int dlesm_checksum_async_f64(const double *f, int ld, int ny, int xstart, int xstop,
                              int ystart, int ystop, double *result_dev, void *stream);
+/* What a time loop asks about its fields every few steps: of 1 to DLESM_STATS_MAX_FIELDS fields of
+ * one array shape (ld, ny), each over its own 1-based inclusive box boxes[k] and, where masks != NULL and masks[k] != NULL,
+ * only where the int mask masks[k] (field layout) is > 0 -- the tmask convention of dlesm_stencil5_masked_f64:
+ *   min, max    over the counted FINITE cells, compared by value (the sign of a zero is unspecified); +inf / -inf when
+ *               there is none
+ *   sum, sumsq  SUM x and SUM x*x over the counted finite cells; IEEE overflow allowed
+ *   count       counted cells: inside the box, and mask > 0 where a mask is given
+ *   nonfinite   counted cells that are NaN or +-inf (left out of min, max, sum, sumsq)
+ * All fields are swept in ONE launch, every cell read once.  min, max, count and nonfinite are exact.  The bits of sum and
+ * sumsq of a field depend only on (ld, its box, whether its base is 16-byte aligned, whether it has a mask) and on the
+ * data: not on how many fields the call has or where the field stands in the list, not on the stream, repeats or what lies
+ * outside the box.  Any base (8-byte aligned) and pitch; boxes need no ring.
+ * result_dev[k] -- device memory, or host memory the device can write (hipHostMalloc) -- receives field k's numbers when
+ * `stream` gets there, with no host synchronisation; the scratch space is stream-ordered, as for
+ * dlesm_checksum_async_f64.  Nothing but result_dev[0..nfields) is written.  An empty box gives {+inf, -inf, 0, 0, 0, 0}
+ * and reads nothing.  DLESM_EINVAL, before anything is launched: nfields outside 1..DLESM_STATS_MAX_FIELDS, a null field,
+ * a box that does not fit the array, a null result_dev, a result_dev range that overlaps a field, a stream that is being
+ * captured.  Combine across ranks with dlesm_global_sum_f64 / dlesm_global_max_f64 (min as -max(-min)). */
+typedef struct dlesm_field_stats {   /* 48 bytes, no padding */
+    double min, max;
+    double sum, sumsq;
+    int64_t count;
+    int64_t nonfinite;
+} dlesm_field_stats;
+enum { DLESM_STATS_MAX_FIELDS = 8 };
+int dlesm_field_stats_async_f64(const double *const *fields, const int *const *masks, const dlesm_region *boxes,
+                                int nfields, int ld, int ny, dlesm_field_stats *result_dev, void *stream);
+/* The same, synchronous: result_host[0..nfields) (host memory) holds the numbers on return, bit for bit those of the
+ * asynchronous entry. */
+int dlesm_field_stats_f64(const double *const *fields, const int *const *masks, const dlesm_region *boxes,
+                          int nfields, int ld, int ny, dlesm_field_stats *result_host, void *stream);
+/* After a check has tripped: *index_host = the lowest 0-based linear index (j-1)*ld + (i-1) of a counted cell of the box
+ * (mask NULL, or mask > 0) that is NaN or +-inf (what = DLESM_LOCATE_NONFINITE; `value` unused) or that compares == value
+ * (DLESM_LOCATE_EQUAL; pass a min or max of dlesm_field_stats), -1 if there is none.  Synchronous; the rare path. */
+enum { DLESM_LOCATE_NONFINITE = 0, DLESM_LOCATE_EQUAL = 1 };
+int dlesm_field_locate_f64(const double *f, const int *mask, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                           int what, double value, int64_t *index_host, void *stream);
 /* synthetic initial condition of BASELINE.md: f(i,j) = u01(splitmix64(seed ^ (gi + gj<<32)))
  * on the box, gi = gx0+i-1, gj = gy0+j-1; cells outside the box are left alone. */
 int dlesm_hash_init_f64(double *f, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
