@@ -162,6 +162,11 @@ PROTOTYPES = {
     "dlesm_bc_open_f64": (_i, [_vp, C.POINTER(MomentumParams), _d] + [_vp] * 8 + [_vp]),
     "dlesm_nemolite_step_f64": (_i, [C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i, C.POINTER(Region),
                                      C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
+    "dlesm_wet_plan_create": (_i, [_vp, _i, _i, C.POINTER(Region), C.POINTER(_vp)]),
+    "dlesm_wet_plan_destroy": (_i, [_vp]),
+    "dlesm_wet_plan_counts": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "dlesm_nemolite_step_wet_f64": (_i, [_vp, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i, C.POINTER(Region),
+                                         C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
     "dlesm_stencil9_f64": (_i, [_vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil9_step_dm": (_i, [_vp, _vp, _vp, C.POINTER(_d), _i, _i, _i, _i, _i, _i, _vp]),
     "dlesm_stencil5_masked_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -244,6 +249,8 @@ PROTOTYPES = {
     "dlesm_shallow_step_smooth_x2_dm": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 12 + [_vp]),
     "dlesm_nemolite_step_dm": (_i, [_vp, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i, C.POINTER(Region),
                                     C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
+    "dlesm_nemolite_step_wet_dm": (_i, [_vp, _vp, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
+                                        C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 + [_vp]),
     "dlesm_shallow_step_smooth_dm_pipelined": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_global_sum_f64": (_i, [C.POINTER(_d)]),
     "dlesm_global_max_f64": (_i, [C.POINTER(_d)]),

@@ -1867,14 +1867,15 @@ __global__ __launch_bounds__(256) void nemolite_ssha_ring(RingRects r, double rd
     }
 }
 
-extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
-                                      const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
-                                      const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un,
-                                      const double *vn, const double *ht, const double *hu, const double *hv,
-                                      const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
-                                      double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+// dlesm_nemolite_step_dm (wet == NULL) and dlesm_nemolite_step_wet_dm: the wet plan only reaches step 2
+static int nemolite_step_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_wet_plan *wet,
+                                 const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, const double *area_t,
+                                 int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+                                 const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn, const double *ht,
+                                 const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                                 const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                                 void *stream)
 {
-    static const char *who = "dlesm_nemolite_step_dm";
     clear_error();
     DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
@@ -1882,10 +1883,11 @@ extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_p
     if (int rc = nemo::step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t,
                                   sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va))
         return rc;
+    if (int rc = nemo::wet_check(who, wet, ld, ny, tbox)) return rc;
     const bool comms = !p->sends.empty() || !p->recvs.empty();
-    auto step = [&] {
-        return dlesm_nemolite_step_f64(params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, sshn_t,
-                                       sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+    auto step = [&] {         // (wet == NULL: dlesm_nemolite_step_f64)
+        return dlesm_nemolite_step_wet_f64(wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv,
+                                           sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
     };
     if (!comms) return step();       // no neighbour: the single-domain entry, bit for bit
 
@@ -1942,6 +1944,29 @@ extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_p
     for (int k = 0; k < 5; k += turn)
         if (int rc = exchange_on(p, outs + k, std::min(turn, 5 - k), DLESM_DIRS_ALL, s)) return rc;
     return DLESM_OK;
+}
+
+extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                      const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                                      const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un,
+                                      const double *vn, const double *ht, const double *hu, const double *hv,
+                                      const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
+                                      double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+{
+    return nemolite_step_dm_impl("dlesm_nemolite_step_dm", p, nullptr, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc,
+                                 ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+}
+
+extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_plan *wet, const dlesm_momentum_params *params,
+                                          const dlesm_momentum_grid *grid, const double *area_t, int ld, int ny,
+                                          const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+                                          const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+                                          const double *ht, const double *hu, const double *hv, const double *sshn_t,
+                                          const double *sshn_u, const double *sshn_v, double *ssha, double *ssha_u,
+                                          double *ssha_v, double *ua, double *va, void *stream)
+{
+    return nemolite_step_dm_impl("dlesm_nemolite_step_wet_dm", p, wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc,
+                                 ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
 }
 
 extern "C" int dlesm_global_sum_f64(double *value)

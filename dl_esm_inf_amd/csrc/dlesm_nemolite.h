@@ -137,6 +137,9 @@ int step_check(const char *who, const dlesm_momentum_params *params, const dlesm
                const dlesm_obc *obc, const double *un, const double *vn, const double *ht, const double *hu,
                const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
                double *ssha_u, double *ssha_v, double *ua, double *va);
+// every refusal of a wet plan: other extents, a box other than tbox; a null plan is accepted.
+// Launches nothing (dlesm_nemolite_step.hip).
+int wet_check(const char *who, const dlesm_wet_plan *wet, int ld, int ny, const dlesm_region *tbox);
 
 } // namespace nemo
 

@@ -19,7 +19,28 @@
 // Everything else -- boxes that differ, odd leading dimensions, unaligned bases, the HOOK key nemo_step_kernel -- runs the
 // definition: the five entries in order on the caller's stream.  The open-boundary pass is always obc_apply's own launch
 // behind the sweep (O(perimeter) cells).
+//
+// Land: a wet plan (dlesm_wet_plan) marks the wave tiles in which the sweep would store nothing but
+// ssha on T == 0 cells; dlesm_nemolite_step_wet_f64 runs the same tile body on the others only -- one bit per tile read on a
+// wave-uniform address in today's launch, trimmed to the rows that hold an active tile (the flag map), or a grid of the
+// active tiles alone, each wave taking its tile from a row-major list (HOOK key nemo_wet_form = 1).  The plan and the
+// launcher take the tile geometry from step_tiles(), the one place it is written.
+#include <climits>
+#include <vector>
+
 #include "dlesm_nemolite.h"
+
+// the wet plan: which wave tiles of the sweep over `box` store anything but land ssha
+struct dlesm_wet_plan {
+    int ld, ny;
+    dlesm_region box;         // the box it was made for (1-based inclusive, as given)
+    int c_first, chunks, nxt; // the tile geometry it was made for (step_tiles)
+    long long tiles, active;
+    int row_lo, row_hi;       // the first and last row (0-based, relative to the box) that holds an active tile
+    unsigned *bits;           // HBM: one bit per tile, row-major, tile t in word t / 32; NULL when tiles == 0
+    int *list;                // HBM: the active tiles, row-major; NULL when active == 0
+};
+
 
 namespace dlesm {
 
@@ -29,6 +50,32 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
+
+// The wave tiles of the sweep over a box: TILE_CHUNKS chunks of 2 columns x 1 row, anchored on a 128-byte line of the row.
+// The kernel, its launcher and the wet plan all take the geometry from here.
+constexpr int TILE_CHUNKS = 63;
+struct StepTiles {
+    int x0, x1, y0, y1;       // the box, 0-based inclusive
+    int c_first, nxt;         // the first chunk of tile 0; tiles per row
+    long long tiles() const { return (long long)nxt * (y1 - y0 + 1); }
+};
+StepTiles step_tiles(const dlesm_region *box)
+{
+    StepTiles g{box->xstart - 1, box->xstop - 1, box->ystart - 1, box->ystop - 1, 0, 0};
+    g.c_first = (g.x0 / 2) & ~7;
+    g.nxt = (g.x1 / 2 - g.c_first + TILE_CHUNKS) / TILE_CHUNKS;
+    return g;
+}
+
+// how a launch finds its tiles: FULL = every tile of the box (today's sweep), FLAGS = every tile of rows y0 .. that has its
+// bit set, LIST = the tiles of a list
+enum { FULL = 0, FLAGS = 1, LIST = 2 };
+struct WetArgs {
+    const unsigned *bits;     // FLAGS: the plan's bit map; bit0 = the number of the first tile of row y0
+    const int *list;          // LIST: the plan's list of n tiles
+    long long bit0;
+    int nxt, n;
+};
 
 enum { AT = NF, NS };   // area_t: the one operand the step reads beyond momentum's
 
@@ -51,17 +98,31 @@ __device__ __forceinline__ void store_pair(double *p, double x0, double x1, bool
     }
 }
 
-// (x0:x1, y0:y1) = the box B (0-based)
+// (x0:x1, y0:y1) = the box B (0-based).  WET = FLAGS: y0 is the first row of the launch, a tile whose bit is clear returns;
+// WET = LIST: wave w takes tile wa.list[w], rows counted from y0.  The tile's coordinates are wave-uniform, so the look-up is
+// a scalar load.
+template <int WET>
 __global__ __launch_bounds__(256) void nemolite_step_tile(StepArgs s, int ld, int x0, int x1, int y0, int y1, int c_first,
-                                                          int nxw)
+                                                          int nxw, WetArgs wa)
 {
     const MomArgs &a = s.m;
     const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    int w;
+    if constexpr (WET == FULL) w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    else w = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (WET == LIST) {
+        if (w >= wa.n) return;
+        w = wa.list[w];
+        nxw = wa.nxt;
+    }
     const int xw = w % nxw, j = y0 + w / nxw;
     if (j > y1) return;
-    const int c = c_first + xw * 63 + lane;              // this lane's chunk (2 columns); lane 63 = the next wave's lane 0
+    const int c = c_first + xw * TILE_CHUNKS + lane;     // this lane's chunk (2 columns); lane 63 = the next wave's lane 0
     if (c - lane > x1 / 2) return;                       // idle padding tile
+    if constexpr (WET == FLAGS) {
+        const long long t = wa.bit0 + (long long)(w / nxw) * wa.nxt + xw;
+        if (!((wa.bits[t >> 5] >> (t & 31)) & 1u)) return;   // nothing but land ssha would be stored here
+    }
     const int c_ld = ld / 2 - 1, cl = c < c_ld ? c : c_ld;
     const bool own = lane != 63;                         // lane 63 only loads: its chunk is the east column of lane 62
     const bool m0 = own && c * 2 >= x0 && c * 2 <= x1, m1 = own && c * 2 + 1 >= x0 && c * 2 + 1 <= x1;
@@ -189,22 +250,43 @@ int nemo::step_check(const char *who, const dlesm_momentum_params *params, const
     return DLESM_OK;
 }
 
+// the refusals of a wet plan: made for other extents, for a box other than tbox, or for another
+// tile geometry than the sweep's.  A null plan is no plan.
+int nemo::wet_check(const char *who, const dlesm_wet_plan *wet, int ld, int ny, const dlesm_region *tbox)
+{
+    if (!wet) return DLESM_OK;
+    DLESM_REQUIRE(tbox, "%s: null region pointer", who);
+    DLESM_REQUIRE(wet->ld == ld && wet->ny == ny, "%s: the wet plan was made for %dx%d arrays, not %dx%d", who, wet->ld,
+                  wet->ny, ld, ny);
+    DLESM_REQUIRE(same_box(&wet->box, tbox), "%s: the wet plan was made for the box (%d:%d,%d:%d), not tbox (%d:%d,%d:%d)", who,
+                  wet->box.xstart, wet->box.xstop, wet->box.ystart, wet->box.ystop, tbox->xstart, tbox->xstop, tbox->ystart,
+                  tbox->ystop);
+    if (!empty(tbox)) {
+        const StepTiles g = step_tiles(tbox);
+        DLESM_REQUIRE(wet->c_first == g.c_first && wet->chunks == TILE_CHUNKS && wet->nxt == g.nxt && wet->tiles == g.tiles(),
+                      "%s: the wet plan was made for another tile geometry", who);
+    }
+    return DLESM_OK;
+}
+
 } // namespace dlesm
 
 using namespace dlesm;
 
-extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
-                                       const double *area_t, int ld, int ny, const dlesm_region *tbox,
-                                       const dlesm_region *ubox, const dlesm_region *vbox, const dlesm_obc *obc,
-                                       double ssh_bc, const double *un, const double *vn, const double *ht, const double *hu,
-                                       const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v,
-                                       double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+namespace {
+
+// dlesm_nemolite_step_f64 (wet == NULL) and dlesm_nemolite_step_wet_f64
+int step_impl(const char *who, const dlesm_wet_plan *wet, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+              const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+              const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+              const double *ht, const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+              const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
 {
-    static const char *who = "dlesm_nemolite_step_f64";
     if (int rc = ensure_device()) return rc;
     if (int rc = step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t, sshn_u,
                             sshn_v, ssha, ssha_u, ssha_v, ua, va))
         return rc;
+    if (int rc = wet_check(who, wet, ld, ny, tbox)) return rc;
     const double *const ins[19] = {un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, area_t, grid->dx_t, grid->dy_t, grid->dx_u,
                                    grid->dy_u, grid->dx_v, grid->dy_v, grid->area_u, grid->area_v, grid->fcor_u,
                                    grid->fcor_v};
@@ -226,13 +308,26 @@ extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, cons
             s.m.rdt = params->rdt, s.m.visc = params->visc, s.m.g = params->g;
             s.m.den = 1.0 + params->cbfr * params->rdt;
             s.area_t = area_t, s.ssha = ssha, s.ssha_u = ssha_u, s.ssha_v = ssha_v;
-            const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
-            const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;  // tiles anchored on 128-byte lines of the row
-            int nxw = (c_last - c_first + 63) / 63, tpb = 4;   // 63 chunks per wave
+            const StepTiles g = step_tiles(tbox);               // tiles anchored on 128-byte lines of the row
+            int nxw = g.nxt, tpb = 4;
             choose_block_shape(&nxw, &tpb, 4);
             if (tpb > 4) tpb = 4;                               // __launch_bounds__(256)
-            const unsigned nblk = (unsigned)(((long)nxw * (y1 - y0 + 1) + tpb - 1) / tpb);
-            hipLaunchKernelGGL(nemolite_step_tile, dim3(nblk), dim3(64 * tpb), 0, st, s, ld, x0, x1, y0, y1, c_first, nxw);
+            if (!wet || wet->active == wet->tiles) {            // every tile: today's kernel, today's launch shape
+                const unsigned nblk = (unsigned)(((long)nxw * (g.y1 - g.y0 + 1) + tpb - 1) / tpb);
+                hipLaunchKernelGGL(nemolite_step_tile<FULL>, dim3(nblk), dim3(64 * tpb), 0, st, s, ld, g.x0, g.x1, g.y0,
+                                   g.y1, g.c_first, nxw, WetArgs{});
+            } else if (wet->active == 0) {                      // all land: nothing to sweep
+            } else if (tuning("nemo_wet_form", 0) == 1) {       // the compacted list: one wave per active tile
+                const WetArgs wa{nullptr, wet->list, 0, g.nxt, (int)wet->active};
+                const unsigned nblk = (unsigned)((wet->active + 3) / 4);
+                hipLaunchKernelGGL(nemolite_step_tile<LIST>, dim3(nblk), dim3(256), 0, st, s, ld, g.x0, g.x1, g.y0, g.y1,
+                                   g.c_first, g.nxt, wa);
+            } else {                                            // the flag map: today's shape over the rows row_lo .. row_hi
+                const WetArgs wa{wet->bits, nullptr, (long long)wet->row_lo * g.nxt, g.nxt, 0};
+                const unsigned nblk = (unsigned)(((long)nxw * (wet->row_hi - wet->row_lo + 1) + tpb - 1) / tpb);
+                hipLaunchKernelGGL(nemolite_step_tile<FLAGS>, dim3(nblk), dim3(64 * tpb), 0, st, s, ld, g.x0, g.x1,
+                                   g.y0 + wet->row_lo, g.y1, g.c_first, nxw, wa);
+            }
             DLESM_HIP_TRY(hipGetLastError());
         }
     } else {
@@ -252,4 +347,113 @@ extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, cons
     }
     if (obc) return dlesm_bc_open_f64(obc, params, ssh_bc, hu, sshn_u, hv, sshn_v, sshn_t, ssha, ua, va, stream);
     return DLESM_OK;
+}
+
+} // namespace
+
+extern "C" int dlesm_wet_plan_create(const int *tmask_host, int ld, int ny, const dlesm_region *box, dlesm_wet_plan **out)
+{
+    static const char *who = "dlesm_wet_plan_create";
+    DLESM_REQUIRE(out, "%s: null output pointer", who);
+    *out = nullptr;
+    DLESM_REQUIRE(tmask_host && box, "%s: null mask or region", who);
+    DLESM_REQUIRE(ld >= 1 && ny >= 1, "%s: array extents %dx%d", who, ld, ny);
+    dlesm_wet_plan *p = new dlesm_wet_plan{ld, ny, *box, 0, TILE_CHUNKS, 0, 0, 0, 0, -1, nullptr, nullptr};
+    std::vector<unsigned> bits;
+    std::vector<int> list;
+    if (!empty(box)) {
+        // the step's own condition on its boxes: a one-cell ring, so that T(i+1, j) and T(i, j+1) are inside the array
+        if (int rc = check_box(who, ld, ny, box->xstart, box->xstop, box->ystart, box->ystop, 1)) {
+            delete p;
+            return rc;
+        }
+        const StepTiles g = step_tiles(box);
+        if (g.tiles() > INT_MAX) {
+            delete p;
+            return fail(DLESM_EINVAL, "%s: %lld tiles do not fit the plan's int32 tile index", who, g.tiles());
+        }
+        p->c_first = g.c_first, p->nxt = g.nxt, p->tiles = g.tiles();
+        bits.assign((size_t)((p->tiles + 31) / 32), 0u);
+        // One pass over the mask per tile row.  A tile is inactive only if the sweep would store nothing but ssha on T == 0
+        // cells in it: no owned cell of the box has T(i,j) != 0, T(i+1,j) > 0 (its ssha_u is written) or T(i,j+1) > 0 (its
+        // ssha_v is written).
+        for (int j = g.y0; j <= g.y1; j++) {
+            const int *t = tmask_host + (size_t)j * ld, *tn = t + ld;
+            for (int xw = 0; xw < g.nxt; xw++) {
+                const int lo = (g.c_first + xw * TILE_CHUNKS) * 2, hi = lo + 2 * TILE_CHUNKS - 1;
+                bool on = false;
+                for (int i = lo < g.x0 ? g.x0 : lo; i <= (hi > g.x1 ? g.x1 : hi) && !on; i++)
+                    on = t[i] != 0 || t[i + 1] > 0 || tn[i] > 0;
+                if (!on) continue;
+                const long long k = (long long)(j - g.y0) * g.nxt + xw;
+                bits[(size_t)(k >> 5)] |= 1u << (k & 31);
+                list.push_back((int)k);
+                if (p->row_hi < 0) p->row_lo = j - g.y0;
+                p->row_hi = j - g.y0;
+            }
+        }
+        p->active = (long long)list.size();
+    }
+    if (!bits.empty()) {
+        int rc = ensure_device();
+        const size_t nb = bits.size() * sizeof(unsigned), nl = list.size() * sizeof(int);
+        if (rc == DLESM_OK && hipMalloc((void **)&p->bits, nb) != hipSuccess) {
+            p->bits = nullptr;
+            rc = fail(DLESM_EHIP, "%s: hipMalloc of %zu bytes failed", who, nb);
+        }
+        if (rc == DLESM_OK && nl && hipMalloc((void **)&p->list, nl) != hipSuccess) {
+            p->list = nullptr;
+            rc = fail(DLESM_EHIP, "%s: hipMalloc of %zu bytes failed", who, nl);
+        }
+        if (rc == DLESM_OK && (hipMemcpy(p->bits, bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+                               (nl && hipMemcpy(p->list, list.data(), nl, hipMemcpyHostToDevice) != hipSuccess)))
+            rc = fail(DLESM_EHIP, "%s: upload of the tile map failed", who);
+        if (rc != DLESM_OK) {
+            if (p->bits) (void)hipFree(p->bits);
+            if (p->list) (void)hipFree(p->list);
+            delete p;
+            return rc;
+        }
+    }
+    *out = p;
+    return DLESM_OK;
+}
+
+extern "C" int dlesm_wet_plan_destroy(dlesm_wet_plan *plan)
+{
+    if (!plan) return DLESM_OK;
+    if (plan->bits) DLESM_HIP_TRY(hipFree(plan->bits));
+    if (plan->list) DLESM_HIP_TRY(hipFree(plan->list));
+    delete plan;
+    return DLESM_OK;
+}
+
+extern "C" int dlesm_wet_plan_counts(const dlesm_wet_plan *plan, long long *tiles, long long *active)
+{
+    DLESM_REQUIRE(plan && tiles && active, "dlesm_wet_plan_counts: null pointer");
+    *tiles = plan->tiles, *active = plan->active;
+    return DLESM_OK;
+}
+
+extern "C" int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                       const double *area_t, int ld, int ny, const dlesm_region *tbox,
+                                       const dlesm_region *ubox, const dlesm_region *vbox, const dlesm_obc *obc,
+                                       double ssh_bc, const double *un, const double *vn, const double *ht, const double *hu,
+                                       const double *hv, const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                                       double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
+{
+    return step_impl("dlesm_nemolite_step_f64", nullptr, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn,
+                     ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+}
+
+extern "C" int dlesm_nemolite_step_wet_f64(const dlesm_wet_plan *wet, const dlesm_momentum_params *params,
+                                           const dlesm_momentum_grid *grid, const double *area_t, int ld, int ny,
+                                           const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+                                           const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+                                           const double *ht, const double *hu, const double *hv, const double *sshn_t,
+                                           const double *sshn_u, const double *sshn_v, double *ssha, double *ssha_u,
+                                           double *ssha_v, double *ua, double *va, void *stream)
+{
+    return step_impl("dlesm_nemolite_step_wet_f64", wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn,
+                     ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
 }

@@ -54,6 +54,8 @@ module grid_mod
      type(c_ptr) :: fcor_u_device, fcor_v_device
      !> the open-boundary plan (dlesm_obc, DESIGN.md section 6.6): made by open_boundary (dlesm_psy_mod) once per grid
      type(c_ptr) :: obc
+     !> the wet plan (dlesm_wet_plan, DESIGN.md section 6.9): made by wet_plan (dlesm_psy_mod) once per grid
+     type(c_ptr) :: wet
      real(go_wp), allocatable :: xt(:,:), yt(:,:)
      type(c_ptr) :: xt_device, yt_device
    contains
@@ -121,6 +123,7 @@ contains
     self%gphif_device = c_null_ptr
     self%fcor_u_device = c_null_ptr;  self%fcor_v_device = c_null_ptr
     self%obc = c_null_ptr
+    self%wet = c_null_ptr
     self%xt_device = c_null_ptr;  self%yt_device = c_null_ptr
   end function grid_constructor
 

@@ -319,6 +319,41 @@ module dlesm_hip_mod
        type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream
        integer(c_int) :: rc
      end function
+     ! ---- land: the wet plan and the step that takes one (DESIGN.md section 6.9)
+     function dlesm_wet_plan_create(tmask_host, ld, ny, box, plan) bind(C, name="dlesm_wet_plan_create") result(rc)
+       import :: c_int, c_ptr, c_region
+       type(c_ptr), value :: tmask_host
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: box
+       type(c_ptr), intent(out) :: plan
+       integer(c_int) :: rc
+     end function
+     function dlesm_wet_plan_destroy(plan) bind(C, name="dlesm_wet_plan_destroy") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+       integer(c_int) :: rc
+     end function
+     function dlesm_wet_plan_counts(plan, tiles, active) bind(C, name="dlesm_wet_plan_counts") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       type(c_ptr), value :: plan
+       integer(c_long_long), intent(out) :: tiles, active
+       integer(c_int) :: rc
+     end function
+     function dlesm_nemolite_step_wet_f64(wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, &
+          hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream) bind(C, name="dlesm_nemolite_step_wet_f64") &
+          result(rc)
+       import :: c_int, c_ptr, c_double, c_momentum_params, c_momentum_grid, c_region
+       type(c_ptr), value :: wet
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       type(c_ptr), value :: area_t
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: tbox, ubox, vbox
+       type(c_ptr), value :: obc
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream
+       integer(c_int) :: rc
+     end function
      function dlesm_stencil5_masked_f64(in, out, tmask, ld, ny, xstart, xstop, ystart, ystop, stream) &
           bind(C, name="dlesm_stencil5_masked_f64") result(rc)
        import :: c_int, c_ptr
@@ -741,6 +776,21 @@ module dlesm_hip_mod
           sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream) bind(C, name="dlesm_nemolite_step_dm") result(rc)
        import :: c_int, c_ptr, c_double, c_momentum_params, c_momentum_grid, c_region
        type(c_ptr), value :: plan
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       type(c_ptr), value :: area_t
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: tbox, ubox, vbox
+       type(c_ptr), value :: obc
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_nemolite_step_wet_dm(plan, wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, &
+          hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream) bind(C, name="dlesm_nemolite_step_wet_dm") &
+          result(rc)
+       import :: c_int, c_ptr, c_double, c_momentum_params, c_momentum_grid, c_region
+       type(c_ptr), value :: plan, wet
        type(c_momentum_params), intent(in) :: params
        type(c_momentum_grid), intent(in) :: grid
        type(c_ptr), value :: area_t

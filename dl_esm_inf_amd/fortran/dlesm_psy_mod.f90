@@ -54,7 +54,7 @@ module dlesm_psy_mod
   public :: momentum_params, c_momentum_params, momentum_coriolis, invoke_momentum_u, invoke_momentum_v, invoke_momentum
   public :: invoke_next_sshu, invoke_next_sshv
   public :: open_boundary, tide_ssh, invoke_bc_ssh, invoke_bc_flather_u, invoke_bc_flather_v, invoke_bc_open
-  public :: invoke_nemolite_step, invoke_nemolite_step_dm
+  public :: invoke_nemolite_step, invoke_nemolite_step_dm, wet_plan
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -344,6 +344,28 @@ contains
     plan = grid%obc
   end function open_boundary
 
+  !> The wet plan of a grid (DESIGN.md section 6.9), made once from the host tmask -- the mask grid_to_device mirrors -- and the
+  !! T-point internal region: which wave tiles of the one-sweep step store anything but land ssha.
+  function wet_plan(grid) result(plan)
+    type(grid_type), intent(inout), target :: grid
+    type(c_ptr) :: plan
+    type(c_region) :: sub, box, whole
+    integer(c_int) :: rc
+    if (.not. c_associated(grid%wet)) then
+       if (.not. allocated(grid%tmask)) call gocean_stop('wet_plan: grid_init has not been called for this grid')
+       associate (s => grid%subdomain%internal)
+         sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+       end associate
+       rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(grid%offset, c_int), int(grid%boundary_conditions(1), c_int), &
+                               int(grid%boundary_conditions(2), c_int), sub, int(grid%nx, c_int), int(grid%ny, c_int), &
+                               box, whole)
+       if (rc /= 0) call gocean_stop('wet_plan: ' // dlesm_error_text())
+       rc = dlesm_wet_plan_create(c_loc(grid%tmask), int(grid%nx, c_int), int(grid%ny, c_int), box, grid%wet)
+       if (rc /= 0) call gocean_stop('wet_plan: ' // dlesm_error_text())
+    end if
+    plan = grid%wet
+  end function wet_plan
+
   !> The boundary sea-surface height of bc_ssh, amp*sin(omega*t), with the host's sin (DESIGN.md section 6.6)
   function tide_ssh(amp, omega, t) result(ssh_bc)
     real(go_wp), intent(in) :: amp, omega, t
@@ -403,13 +425,18 @@ contains
   !! open_boundary plan (absent: a closed basin, no boundary pass).  ssha is in/out: the faces at the east and north edge of
   !! the box read ssha in the ring.  Stops without momentum_coriolis, and on a decomposed grid (the sequence needs an ssha
   !! halo exchange between continuity and next_ssh*: use the separate wrappers there).
-  subroutine invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc)
+  !! skip_land present and true: the sweep leaves out the wave tiles of the grid's wet_plan that hold nothing but land (DESIGN.md
+  !! section 6.9): ssha_u, ssha_v, ua and va as without it in every cell, ssha in every cell with tmask /= 0; a land cell of
+  !! ssha may keep its content.
+  subroutine invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc, &
+                                  skip_land)
     type(c_momentum_params), intent(in) :: params
     type(r2d_field), intent(inout), target :: ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
     real(go_wp), intent(in), optional :: ssh_bc
+    logical, intent(in), optional :: skip_land
     type(c_momentum_grid) :: mg
     type(c_region) :: tbox, ubox, vbox
-    type(c_ptr) :: plan
+    type(c_ptr) :: plan, wet
     real(c_double) :: bc
     integer(c_int) :: rc
     if (ssha%grid%decomp%ndomains > 1) &
@@ -431,12 +458,25 @@ contains
        plan = open_boundary(ssha%grid)
        bc = real(ssh_bc, c_double)
     end if
-    rc = dlesm_nemolite_step_f64(params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
-                                 tbox, ubox, vbox, plan, bc, field_device_data(un), field_device_data(vn), &
-                                 field_device_data(ht), field_device_data(hu), field_device_data(hv), &
-                                 field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
-                                 field_device_data(ssha), field_device_data(ssha_u), field_device_data(ssha_v), &
-                                 field_device_data(ua), field_device_data(va), c_null_ptr)
+    wet = c_null_ptr
+    if (present(skip_land)) then
+       if (skip_land) wet = wet_plan(ssha%grid)
+    end if
+    if (c_associated(wet)) then
+       rc = dlesm_nemolite_step_wet_f64(wet, params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), &
+                                        int(ssha%grid%ny, c_int), tbox, ubox, vbox, plan, bc, field_device_data(un), &
+                                        field_device_data(vn), field_device_data(ht), field_device_data(hu), &
+                                        field_device_data(hv), field_device_data(sshn_t), field_device_data(sshn_u), &
+                                        field_device_data(sshn_v), field_device_data(ssha), field_device_data(ssha_u), &
+                                        field_device_data(ssha_v), field_device_data(ua), field_device_data(va), c_null_ptr)
+    else
+       rc = dlesm_nemolite_step_f64(params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
+                                    tbox, ubox, vbox, plan, bc, field_device_data(un), field_device_data(vn), &
+                                    field_device_data(ht), field_device_data(hu), field_device_data(hv), &
+                                    field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                    field_device_data(ssha), field_device_data(ssha_u), field_device_data(ssha_v), &
+                                    field_device_data(ua), field_device_data(va), c_null_ptr)
+    end if
     if (rc /= 0) call gocean_stop('invoke_nemolite_step: ' // dlesm_error_text())
   end subroutine invoke_nemolite_step
 
@@ -446,15 +486,18 @@ contains
   !! inputs need valid depth-1 halos, corners included; the outputs leave with them.  Collective.  The grid must have been
   !! decomposed with halo_width = 1 (without distributed memory the plan has no messages: invoke_nemolite_step, bit for bit).
   !! Stops on another halo width and without momentum_coriolis.
-  subroutine invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc)
+  !! skip_land present and true: as invoke_nemolite_step, with this rank's wet_plan (dlesm_nemolite_step_wet_dm, section 6.9).
+  subroutine invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc, &
+                                     skip_land)
     use parallel_comms_mod, only: halo_plan_for, serial_plan_for
     use parallel_utils_mod, only: DIST_MEM_ENABLED
     type(c_momentum_params), intent(in) :: params
     type(r2d_field), intent(inout), target :: ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
     real(go_wp), intent(in), optional :: ssh_bc
+    logical, intent(in), optional :: skip_land
     type(c_momentum_grid) :: mg
     type(c_region) :: tbox, ubox, vbox
-    type(c_ptr) :: plan, obc
+    type(c_ptr) :: plan, obc, wet
     real(c_double) :: bc
     integer(c_int) :: rc
     if (ssha%grid%subdomain%internal%xstart - 1 /= 1 .or. ssha%grid%subdomain%internal%ystart - 1 /= 1) &
@@ -480,12 +523,17 @@ contains
     else
        plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
     end if
-    rc = dlesm_nemolite_step_dm(plan, params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), &
-                                int(ssha%grid%ny, c_int), tbox, ubox, vbox, obc, bc, field_device_data(un), &
-                                field_device_data(vn), field_device_data(ht), field_device_data(hu), field_device_data(hv), &
-                                field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
-                                field_device_data(ssha), field_device_data(ssha_u), field_device_data(ssha_v), &
-                                field_device_data(ua), field_device_data(va), c_null_ptr)
+    wet = c_null_ptr
+    if (present(skip_land)) then
+       if (skip_land) wet = wet_plan(ssha%grid)
+    end if
+    ! (a null wet plan: dlesm_nemolite_step_dm)
+    rc = dlesm_nemolite_step_wet_dm(plan, wet, params, mg, ssha%grid%area_t_device, int(ssha%grid%nx, c_int), &
+                                    int(ssha%grid%ny, c_int), tbox, ubox, vbox, obc, bc, field_device_data(un), &
+                                    field_device_data(vn), field_device_data(ht), field_device_data(hu), &
+                                    field_device_data(hv), field_device_data(sshn_t), field_device_data(sshn_u), &
+                                    field_device_data(sshn_v), field_device_data(ssha), field_device_data(ssha_u), &
+                                    field_device_data(ssha_v), field_device_data(ua), field_device_data(va), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_nemolite_step_dm: ' // dlesm_error_text())
   end subroutine invoke_nemolite_step_dm
 

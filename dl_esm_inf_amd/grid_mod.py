@@ -43,6 +43,7 @@ class grid_type:
         self.gphiu = self.gphiv = None # host latitudes of u and v points (grid_mod.f90:512-523)
         self.fcor = None               # (omega, d2r, fcor_u, fcor_v device tensors): psy.coriolis, once per grid
         self._obc = None               # the open-boundary plan (dlesm_obc): psy.open_boundary, once per grid
+        self._wet = None               # the wet plan (dlesm_wet_plan): psy.wet_plan, once per grid
 
     @property
     def tmask_device(self):
@@ -127,6 +128,9 @@ def grid_init(grid, dxarg, dyarg, tmask=None):
     if grid._obc is not None:                              # made from the previous mask
         check(L.dlesm_obc_destroy(grid._obc.handle))
         grid._obc = None
+    if grid._wet is not None:
+        check(L.dlesm_wet_plan_destroy(grid._wet.handle))
+        grid._wet = None
     if nranks > 1:
         if periodic:                                       # grid_mod.f90:559-564
             raise _cabi.GoceanStop(_cabi.EABORT, "map_comms call needs to be implemented for "

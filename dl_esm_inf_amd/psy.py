@@ -161,6 +161,37 @@ def open_boundary(grid):
     return grid._obc
 
 
+class WetPlan:
+    """the wet plan of a grid (dlesm_wet_plan): which wave tiles of the one-sweep step over the T
+    internal region store anything but land ssha.  Made by wet_plan(grid); grid_init releases it."""
+
+    def __init__(self, handle, tiles, active):
+        self.handle, self.tiles, self.active = handle, tiles, active
+
+    def __repr__(self):
+        return f"WetPlan(tiles {self.tiles}, active {self.active})"
+
+
+def wet_plan(grid):
+    """the grid's wet plan, built once per grid from its host tmask (the mask its device mirror holds) and the T internal
+    region"""
+    if grid._wet is None:
+        from .field_mod import GO_T_POINTS, field_bounds
+        if grid.tmask is None:
+            raise _cabi.GoceanStop(_cabi.EABORT, "wet_plan: grid%tmask requested before grid_init")
+        import numpy as np
+        tm = np.ascontiguousarray(grid.tmask, dtype=np.int32)
+        box = field_bounds(grid, GO_T_POINTS)[0]
+        h = C.c_void_p()
+        rc = _cabi.lib().dlesm_wet_plan_create(tm.ctypes.data, grid.nx, grid.ny, C.byref(box), C.byref(h))
+        if rc != 0:
+            raise _cabi.GoceanStop(_cabi.EABORT, "wet_plan: " + _cabi.lib().dlesm_last_error().decode())
+        n = [C.c_longlong() for _ in range(2)]
+        check(_cabi.lib().dlesm_wet_plan_counts(h, *[C.byref(x) for x in n]))
+        grid._wet = WetPlan(h, *[x.value for x in n])
+    return grid._wet
+
+
 def tide_ssh(amp, omega, t):
     """the boundary sea-surface height of bc_ssh, amp*sin(omega*t), with the host's sin"""
     return float(amp) * math.sin(float(omega) * float(t))
@@ -191,11 +222,14 @@ def invoke_bc_open(params, ssh_bc, ssha, ua, va, hu, sshn_u, hv, sshn_v, sshn_t,
 
 
 def invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc=None,
-                         stream=None):
+                         stream=None, skip_land=False):
     """one NEMOLite2D-class time step in one call, bit for bit invoke_continuity (rdt = params.rdt)
     -> invoke_next_sshu / invoke_next_sshv on ssha -> invoke_momentum -> invoke_bc_open on the grid's open_boundary plan.
     ssh_bc=None: a closed basin, no boundary pass.  ssha is in/out (the ring cells east and north of the box are read).
-    Single domain: stops on a decomposed grid, and when the grid's Coriolis parameter was never set."""
+    Single domain: stops on a decomposed grid, and when the grid's Coriolis parameter was never set.
+    skip_land=True: the sweep leaves out the wave tiles of the grid's wet_plan that hold nothing but land (DESIGN.md section
+    6.9) -- ssha_u, ssha_v, ua and va as without it in every cell, ssha in every cell with tmask != 0; a land cell of ssha
+    may keep its content."""
     g = ssha.grid
     if g.decomp is not None and g.decomp.ndomains > 1:
         raise _cabi.GoceanStop(_cabi.EABORT, "invoke_nemolite_step: the grid is decomposed (%d subdomains): the step needs an "
@@ -203,21 +237,24 @@ def invoke_nemolite_step(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, h
                                              "hold; use the separate wrappers" % g.decomp.ndomains)
     mg = _momentum_grid(g, "invoke_nemolite_step")
     plan = None if ssh_bc is None else open_boundary(g).handle
-    check(_cabi.lib().dlesm_nemolite_step_f64(C.byref(params), C.byref(mg), C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny,
-                                              C.byref(ssha.internal), C.byref(ua.internal), C.byref(va.internal), plan,
-                                              0.0 if ssh_bc is None else float(ssh_bc),
-                                              *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u,
-                                                                       ssha_v, ua, va)],
-                                              _stream_ptr(stream)))
+    args = (C.byref(params), C.byref(mg), C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal),
+            C.byref(ua.internal), C.byref(va.internal), plan, 0.0 if ssh_bc is None else float(ssh_bc),
+            *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va)],
+            _stream_ptr(stream))
+    if skip_land:
+        check(_cabi.lib().dlesm_nemolite_step_wet_f64(wet_plan(g).handle, *args))
+    else:
+        check(_cabi.lib().dlesm_nemolite_step_f64(*args))
 
 
 def invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssh_bc=None,
-                            stream=None):
+                            stream=None, skip_land=False):
     """one NEMOLite2D-class time step and ONE exchange of its five outputs on a decomposed grid, bit for
     bit invoke_continuity -> ssha.halo_exchange(1) -> invoke_next_sshu / invoke_next_sshv -> invoke_momentum ->
     invoke_bc_open on this rank's open_boundary plan (ssh_bc=None: none) -> halo_exchange_multi of ssha, ssha_u, ssha_v, ua,
     va.  The inputs need valid depth-1 halos, corners included; the outputs leave with them.  Collective.  Stops on a grid
-    with halo_width other than 1, and when the grid's Coriolis parameter was never set."""
+    with halo_width other than 1, and when the grid's Coriolis parameter was never set.  skip_land=True: as
+    invoke_nemolite_step, with this rank's wet_plan (dlesm_nemolite_step_wet_dm)."""
     g = ssha.grid
     hw = getattr(g, "halo_width", 1)
     if hw != 1:
@@ -228,13 +265,14 @@ def invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu
         raise _cabi.DlesmError(_cabi.EINVAL, "invoke_nemolite_step_dm: the grid has no message tables (grid_init after "
                                              "decompose)")
     obc = None if ssh_bc is None else open_boundary(g).handle
-    check(_cabi.lib().dlesm_nemolite_step_dm(grid_mod.halo_plan(g), C.byref(params), C.byref(mg),
-                                             C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal),
-                                             C.byref(ua.internal), C.byref(va.internal), obc,
-                                             0.0 if ssh_bc is None else float(ssh_bc),
-                                             *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u,
-                                                                      ssha_v, ua, va)],
-                                             _stream_ptr(stream)))
+    args = (C.byref(params), C.byref(mg), C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal),
+            C.byref(ua.internal), C.byref(va.internal), obc, 0.0 if ssh_bc is None else float(ssh_bc),
+            *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va)],
+            _stream_ptr(stream))
+    if skip_land:
+        check(_cabi.lib().dlesm_nemolite_step_wet_dm(grid_mod.halo_plan(g), wet_plan(g).handle, *args))
+    else:
+        check(_cabi.lib().dlesm_nemolite_step_dm(grid_mod.halo_plan(g), *args))
 
 
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):

@@ -383,6 +383,33 @@ int dlesm_nemolite_step_f64(const dlesm_momentum_params *params, const dlesm_mom
                             const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
                             void *stream);
 
+/* Land: a wet plan marks the wave tiles of the one-sweep step over `box` in which the sweep would
+ * store nothing but ssha on T == 0 cells -- no cell (i,j) of the tile inside the box has T(i,j) != 0, T(i+1,j) > 0 or
+ * T(i,j+1) > 0 -- and dlesm_nemolite_step_wet_f64 leaves those tiles out.  The plan is made once from the HOST mask, which must
+ * be the mask grid->tmask holds on the device when the plan is used: that is the caller's responsibility, the library
+ * cannot check it.  box is the T box the step will be called with (1-based, inclusive, a one-cell ring inside the array; an
+ * empty box gives a plan of no tiles).  The tile geometry is internal; dlesm_wet_plan_counts shows the number of tiles of the
+ * box and how many of them are active.  DLESM_EINVAL: null pointers, a box that does not fit, more tiles than an int32 holds. */
+typedef struct dlesm_wet_plan dlesm_wet_plan;
+int dlesm_wet_plan_create(const int *tmask_host, int ld, int ny, const dlesm_region *box, dlesm_wet_plan **plan);
+int dlesm_wet_plan_destroy(dlesm_wet_plan *plan);
+int dlesm_wet_plan_counts(const dlesm_wet_plan *plan, long long *tiles, long long *active);
+/* dlesm_nemolite_step_f64 that skips land.  wet == NULL: dlesm_nemolite_step_f64, bit for bit in every cell.  Otherwise, after
+ * the call ssha_u, ssha_v, ua and va hold in EVERY cell what dlesm_nemolite_step_f64 leaves; ssha does so in every cell with
+ * T != 0 and in every cell outside tbox; a T == 0 cell of tbox holds either that value or its content from before the call.
+ * Stale land values of ssha are never read by a written cell, in this step or after the caller rotates ssha into sshn_t
+ * (section 6.9).  With every tile active the call launches exactly the kernel and shape of dlesm_nemolite_step_f64; with none,
+ * nothing but bc_open.  The definition path (unequal boxes, an odd ld, unaligned bases, the HOOK key nemo_step_kernel) ignores
+ * the plan.  DLESM_EINVAL before anything is launched: a plan made for other (ld, ny) or for a box other than tbox, and
+ * every refusal of dlesm_nemolite_step_f64. */
+int dlesm_nemolite_step_wet_f64(const dlesm_wet_plan *wet, const dlesm_momentum_params *params,
+                                const dlesm_momentum_grid *grid, const double *area_t, int ld, int ny,
+                                const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
+                                const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn, const double *ht,
+                                const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                                const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                                void *stream);
+
 /* Shallow-water u/v/h update: reads u,v,p (3x3 footprint)
  * and uold,vold,pold, writes unew,vnew,pnew on the box. */
 typedef struct dlesm_sw_params {
@@ -934,6 +961,17 @@ int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *plan, const dlesm_sw_params
  * the same order. */
 int dlesm_nemolite_step_dm(dlesm_halo_plan *plan, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
                            const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                           const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+                           const double *ht, const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                           const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                           void *stream);
+/* dlesm_nemolite_step_dm that skips land: step 2 is dlesm_nemolite_step_wet_f64 with this rank's wet
+ * plan (rank-local, as obc is; NULL: dlesm_nemolite_step_dm, bit for bit); the ring ssha and the exchange of the five outputs
+ * are unchanged, every rank performs the same number of mailbox operations whatever its plan, and stale land ssha travels in
+ * the exchange.  The contract of dlesm_nemolite_step_wet_f64 holds against dlesm_nemolite_step_dm, halos included.
+ * DLESM_EINVAL before anything is launched or exchanged: the refusals of both entries. */
+int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *plan, const dlesm_wet_plan *wet, const dlesm_momentum_params *params,
+                           const dlesm_momentum_grid *grid, const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
                            const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
                            const double *ht, const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
                            const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
