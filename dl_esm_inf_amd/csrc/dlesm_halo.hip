@@ -1969,6 +1969,52 @@ extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_pl
                                  ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
 }
 
+// Tracer transport on a decomposed grid: the single-domain sweep, then ONE exchange of the new
+// tracers -- dlesm_tracer_step_f64 followed by dlesm_halo_exchange_multi_f64, with dlesm_nemolite_step_dm's guards and its
+// rule for the mailbox turns.
+extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
+                                    int ystop, const int *tmask, const double *area_t, const double *un, const double *vn,
+                                    const double *hu, const double *hv, const double *ht, const double *sshn_t,
+                                    const double *sshn_u, const double *sshn_v, const double *ssha,
+                                    const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+{
+    static const char *who = "dlesm_tracer_step_dm";
+    clear_error();
+    DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
+    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
+    if (int rc = ensure_device()) return rc;
+    const nemo::TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
+    if (int rc = nemo::tracer_check(who, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers)) return rc;
+    auto step = [&] {
+        return dlesm_tracer_step_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t,
+                                     sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
+    };
+    if (p->sends.empty() && p->recvs.empty()) return step();     // no neighbour: the single-domain entry, bit for bit
+
+    // ---- every refusal of a plan with messages, before anything is launched or exchanged
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
+    for (const Msg &m : p->recvs) {
+        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
+        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
+        if (!xdir && !ydir) continue;
+        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 1, "%s: the plan exchanges depth-%d halos, the step needs depth 1 "
+                      "(a grid decomposed with halo_width = 1)", who, xdir ? m.nx : m.ny);
+    }
+    DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
+    hipStream_t s = (hipStream_t)stream;
+    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil(ntracers / peer_fcap) mailbox
+    // operations per call on every rank, whatever the box
+    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
+    const int turn = mailbox ? p->peer_fcap : ntracers;
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
+    if (int rc = join_pending(p, s)) return rc;
+    if (int rc = step()) return rc;
+    for (int k = 0; k < ntracers; k += turn)
+        if (int rc = exchange_on(p, c_out + k, std::min(turn, ntracers - k), DLESM_DIRS_ALL, s)) return rc;
+    return DLESM_OK;
+}
+
 extern "C" int dlesm_global_sum_f64(double *value)
 {
     DLESM_REQUIRE(value != nullptr, "null pointer");

@@ -1,8 +1,8 @@
 // The point expressions of the NEMOLite2D-class kernels (DESIGN.md sections 5.10 and 6.5), shared by every entry that
-// evaluates them -- continuity (dlesm_continuity.hip), momentum and next_ssh* (dlesm_momentum.hip) and the one-sweep time
-// step (dlesm_nemolite_step.hip) -- so that the entries cannot drift apart.  Every operation is rounded in double precision
-// in the order the parentheses give: the sources that include this header are built with -ffp-contract=off and no
-// expression here replaces a division by a reciprocal.
+// evaluates them -- continuity (dlesm_continuity.hip), momentum and next_ssh* (dlesm_momentum.hip), the one-sweep time
+// step (dlesm_nemolite_step.hip) and tracer transport (dlesm_tracer.hip) -- so that the entries cannot drift apart.  Every
+// operation is rounded in double precision in the order the parentheses give: the sources that include this header are
+// built with -ffp-contract=off and no expression here replaces a division by a reciprocal.
 #pragma once
 
 #include "dlesm_internal.h"
@@ -36,6 +36,34 @@ __device__ __forceinline__ double cont_point(double rdt, double st, double su, d
     const double r1 = (su + hu) * un, r2 = (su_w + hu_w) * un_w;
     const double r3 = (sv + hv) * vn, r4 = (sv_s + hv_s) * vn_s;
     return st + (((r2 - r1) + r4) - r3) * rdt / area;
+}
+
+// Tracer transport.  What a T cell's update takes from the flow, the same for every tracer: the
+// face transports r1..r4 with continuity's expression tree (east, west, north, south), whether each face's far cell is
+// anything but land, q = rdt / area_t and the old and new water column.  _w operands at (i-1, j), _s operands at (i, j-1);
+// t_e .. t_s = tmask at (i+1, j), (i-1, j), (i, j+1), (i, j-1).
+struct TracerFlow {
+    double r1, r2, r3, r4, q, h_old, h_new;
+    bool e, w, n, s;
+};
+__device__ __forceinline__ TracerFlow tracer_flow(double rdt, double su, double su_w, double sv, double sv_s, double hu,
+                                                  double hu_w, double hv, double hv_s, double un, double un_w, double vn,
+                                                  double vn_s, double area, double ht, double st, double sa, int t_e,
+                                                  int t_w, int t_n, int t_s)
+{
+    return TracerFlow{(su + hu) * un, (su_w + hu_w) * un_w, (sv + hv) * vn, (sv_s + hv_s) * vn_s, rdt / area, ht + st,
+                      ht + sa, t_e != 0, t_w != 0, t_n != 0, t_s != 0};
+}
+// c_out(i,j) of a wet cell: first-order upwind fluxes through the four faces; c = the tracer at (i, j), c_e .. c_s at
+// (i+1, j), (i-1, j), (i, j+1), (i, j-1).  The upwind choice and the land switch are selects, never blends: what a land
+// cell or a face that touches land holds (a NaN included) does not reach the result.
+__device__ __forceinline__ double tracer_point(const TracerFlow &f, double c, double c_e, double c_w, double c_n, double c_s)
+{
+    const double F1 = f.e ? f.r1 * (f.r1 >= 0.0 ? c : c_e) : 0.0;
+    const double F2 = f.w ? f.r2 * (f.r2 >= 0.0 ? c_w : c) : 0.0;
+    const double F3 = f.n ? f.r3 * (f.r3 >= 0.0 ? c : c_n) : 0.0;
+    const double F4 = f.s ? f.r4 * (f.r4 >= 0.0 ? c_s : c) : 0.0;
+    return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
 }
 
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,
@@ -140,6 +168,17 @@ int step_check(const char *who, const dlesm_momentum_params *params, const dlesm
 // every refusal of a wet plan: other extents, a box other than tbox; a null plan is accepted.
 // Launches nothing (dlesm_nemolite_step.hip).
 int wet_check(const char *who, const dlesm_wet_plan *wet, int ld, int ny, const dlesm_region *tbox);
+
+// the flow a tracer step reads, in the order of the C entry's arguments
+struct TracerFields {
+    const int *tmask;
+    const double *area_t, *un, *vn, *hu, *hv, *ht, *sshn_t, *sshn_u, *sshn_v, *ssha;
+};
+// every refusal of DESIGN.md section 6.10 (the tracer count, null pointers, a box without its ring, a c_out that overlaps
+// an input, a c_in or another c_out), messages prefixed with `who`; DLESM_OK or DLESM_EINVAL.  Launches nothing
+// (dlesm_tracer.hip).
+int tracer_check(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, const TracerFields &f,
+                 const double *const *c_in, double *const *c_out, int ntracers);
 
 } // namespace nemo
 

@@ -12,6 +12,7 @@ module dlesm_hip_mod
   integer, parameter :: DLESM_UNIQUE_ID_BYTES = 128
   !> dirs_mask values of dlesm_halo_exchange_f64 (include/dlesm_hip.h)
   integer(c_int), parameter :: DLESM_DIRS_ALL = 15_c_int, DLESM_DIRS_NO_DIAGONALS = 16_c_int
+  integer, parameter :: DLESM_TRACER_MAX = 8           ! dlesm_tracer_step_f64
   !> norm values of dlesm_stencil5_resid_f64
   integer(c_int), parameter :: DLESM_NORM_MAX = 0_c_int, DLESM_NORM_SUMSQ = 1_c_int
   !> `what` values of dlesm_field_locate_f64, and the most fields one dlesm_field_stats_f64 call takes
@@ -799,6 +800,30 @@ module dlesm_hip_mod
        type(c_ptr), value :: obc
        real(c_double), value :: ssh_bc
        type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream
+       integer(c_int) :: rc
+     end function
+     ! ---- tracer transport (DESIGN.md section 6.10): c_in, c_out = host arrays of ntracers device pointers
+     function dlesm_tracer_step_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, &
+          sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream) bind(C, name="dlesm_tracer_step_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha
+       type(c_ptr), intent(in) :: c_in(*), c_out(*)
+       integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_tracer_step_dm(plan, rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, &
+          sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream) bind(C, name="dlesm_tracer_step_dm") result(rc)
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: plan
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha
+       type(c_ptr), intent(in) :: c_in(*), c_out(*)
+       integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
        integer(c_int) :: rc
      end function
      function dlesm_shallow_step_x2_dm(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, &

@@ -55,6 +55,7 @@ module dlesm_psy_mod
   public :: invoke_next_sshu, invoke_next_sshv
   public :: open_boundary, tide_ssh, invoke_bc_ssh, invoke_bc_flather_u, invoke_bc_flather_v, invoke_bc_open
   public :: invoke_nemolite_step, invoke_nemolite_step_dm, wet_plan
+  public :: invoke_tracer_step, invoke_tracer_step_dm
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -536,6 +537,85 @@ contains
                                     field_device_data(ssha_v), field_device_data(ua), field_device_data(va), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_nemolite_step_dm: ' // dlesm_error_text())
   end subroutine invoke_nemolite_step_dm
+
+  !> Upwind transport of up to DLESM_TRACER_MAX T-point tracers in one sweep (DESIGN.md section 6.10): c_out(k) <- c_in(k)
+  !! carried by continuity's face transports of level n (un, vn, hu, hv, sshn_u, sshn_v), from the water column ht + sshn_t to
+  !! ht + ssha, over the T internal region, on wet cells only.  ssha is what the time step made from the same level-n inputs.
+  !! Single domain: stops on a decomposed grid (use invoke_tracer_step_dm), and when c_out and c_in differ in size.
+  subroutine invoke_tracer_step(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    if (ssha%grid%decomp%ndomains > 1) &
+         call gocean_stop('invoke_tracer_step: the grid is decomposed: the new tracers need a halo exchange; use ' // &
+                          'invoke_tracer_step_dm')
+    call tracer_step_call('invoke_tracer_step', c_null_ptr, .false., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, &
+                          sshn_u, sshn_v)
+  end subroutine invoke_tracer_step
+
+  !> invoke_tracer_step and ONE exchange of the new tracers on a decomposed grid (dlesm_tracer_step_dm, DESIGN.md section
+  !! 6.10): bit for bit invoke_tracer_step, then the halo exchange of c_out.  The flow fields and c_in need valid depth-1 halos;
+  !! c_out leaves with them.  Collective.  The grid must have been decomposed with halo_width = 1 (without distributed memory
+  !! the plan has no messages: invoke_tracer_step, bit for bit).
+  subroutine invoke_tracer_step_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    type(c_ptr) :: plan
+    if (ssha%grid%subdomain%internal%xstart - 1 /= 1 .or. ssha%grid%subdomain%internal%ystart - 1 /= 1) &
+         call gocean_stop('invoke_tracer_step_dm: the grid must be decomposed with halo_width = 1')
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(ssha%grid%nx, ssha%grid%ny)
+    else
+       plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
+    end if
+    call tracer_step_call('invoke_tracer_step_dm', plan, .true., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, &
+                          sshn_v)
+  end subroutine invoke_tracer_step_dm
+
+  ! the call both tracer wrappers make (dm: dlesm_tracer_step_dm with `plan`)
+  subroutine tracer_step_call(who, plan, dm, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+    character(len=*), intent(in) :: who
+    type(c_ptr), intent(in) :: plan
+    logical, intent(in) :: dm
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    type(c_ptr) :: pin(DLESM_TRACER_MAX), pout(DLESM_TRACER_MAX)
+    integer :: k, n
+    integer(c_int) :: rc
+    n = size(c_in)
+    if (size(c_out) /= n) call gocean_stop(who // ': c_out and c_in differ in size')
+    if (n < 1 .or. n > DLESM_TRACER_MAX) call gocean_stop(who // ': the number of tracers must be 1..8')
+    call need_device(ssha);  call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(hu)
+    call need_device(hv);  call need_device(sshn_t);  call need_device(sshn_u);  call need_device(sshn_v)
+    pin = c_null_ptr;  pout = c_null_ptr
+    do k = 1, n
+       call need_device(c_in(k));  call need_device(c_out(k))
+       pin(k) = field_device_data(c_in(k));  pout(k) = field_device_data(c_out(k))
+    end do
+    call grid_to_device(ssha%grid)
+    if (dm) then
+       rc = dlesm_tracer_step_dm(plan, real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
+                                 int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
+                                 int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &
+                                 ssha%grid%tmask_device, ssha%grid%area_t_device, field_device_data(un), &
+                                 field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
+                                 field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                 field_device_data(ssha), pin, pout, int(n, c_int), c_null_ptr)
+    else
+       rc = dlesm_tracer_step_f64(real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
+                                  int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
+                                  int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &
+                                  ssha%grid%tmask_device, ssha%grid%area_t_device, field_device_data(un), &
+                                  field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
+                                  field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                  field_device_data(ssha), pin, pout, int(n, c_int), c_null_ptr)
+    end if
+    if (rc /= 0) call gocean_stop(who // ': ' // dlesm_error_text())
+  end subroutine tracer_step_call
 
   !> Optional planning call (once per field geometry, outside the time loop): lets the library time
   !! its launch shapes for invoke_jacobi5 / invoke_jacobi5_dm on these fields and keep the fastest.

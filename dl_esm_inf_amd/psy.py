@@ -275,6 +275,48 @@ def invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu
         check(_cabi.lib().dlesm_nemolite_step_dm(grid_mod.halo_plan(g), *args))
 
 
+def _tracer_args(who, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream):
+    c_out, c_in = list(c_out), list(c_in)
+    if len(c_out) != len(c_in):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: %d output fields for %d tracers" % (who, len(c_out), len(c_in)))
+    g, it = ssha.grid, ssha.internal
+    n = len(c_in)
+    pin, pout = (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_in]), (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_out])
+    return (float(rdt), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+            C.c_void_p(g.area_t_device.data_ptr()), *[f.device_ptr for f in (un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha)],
+            pin, pout, n, _stream_ptr(stream))
+
+
+def invoke_tracer_step(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """upwind transport of up to TRACER_MAX T-point tracers in one sweep: c_out[k] <- c_in[k] carried by
+    continuity's face transports of level n (un, vn, hu, hv, sshn_u, sshn_v), from the water column ht + sshn_t to ht + ssha,
+    over the T internal region, on wet cells only.  c_out and c_in are lists of T-point fields; ssha is what the time step
+    made from the same level-n inputs.  Single domain: stops on a decomposed grid."""
+    g = ssha.grid
+    if g.decomp is not None and g.decomp.ndomains > 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step: the grid is decomposed (%d subdomains): the new tracers "
+                                             "need a halo exchange; use invoke_tracer_step_dm" % g.decomp.ndomains)
+    check(_cabi.lib().dlesm_tracer_step_f64(*_tracer_args("invoke_tracer_step", rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
+                                                          sshn_t, sshn_u, sshn_v, stream)))
+
+
+def invoke_tracer_step_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """invoke_tracer_step and ONE exchange of the new tracers on a decomposed grid (dlesm_tracer_step_dm, DESIGN.md section
+    6.10), bit for bit invoke_tracer_step -> halo_exchange_multi(c_out).  The flow fields and c_in need valid depth-1 halos;
+    c_out leaves with them.  Collective.  Stops on a grid with halo_width other than 1."""
+    g = ssha.grid
+    hw = getattr(g, "halo_width", 1)
+    if hw != 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_dm: the grid has halo_width %d; the step exchanges depth-1 "
+                                             "halos: decompose the grid with halo_width = 1" % hw)
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_dm: the grid has no message tables (grid_init after "
+                                             "decompose)")
+    check(_cabi.lib().dlesm_tracer_step_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_dm", rdt, c_out, c_in, ssha,
+                                                                                 un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v,
+                                                                                 stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

@@ -977,6 +977,39 @@ int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *plan, const dlesm_wet_plan *wet,
                            const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
                            void *stream);
 
+/* Tracer transport: first-order upwind advection of ntracers (1..DLESM_TRACER_MAX) T-point tracers
+ * with continuity's own face transports, in one sweep that loads the flow once.  For every T cell (i,j) of the box (1-based,
+ * inclusive, a one-cell ring inside the array) with tmask(i,j) > 0 and every tracer c = c_in[k]:
+ *     r1..r4 = continuity's (east, west, north, south face)
+ *     F1 = tmask(i+1,j) != 0 ? r1 * (r1 >= 0 ? c(i,j)   : c(i+1,j)) : 0      F2 = tmask(i-1,j) != 0 ? r2 * (r2 >= 0 ? c(i-1,j) : c(i,j)) : 0
+ *     F3 = tmask(i,j+1) != 0 ? r3 * (r3 >= 0 ? c(i,j)   : c(i,j+1)) : 0      F4 = tmask(i,j-1) != 0 ? r4 * (r4 >= 0 ? c(i,j-1) : c(i,j)) : 0
+ *     c_out[k](i,j) = ((ht + sshn_t) * c + (((F2 - F1) + F4) - F3) * (rdt / area_t)) / (ht + ssha)
+ * every operation rounded in double precision in that order.  Cells with tmask <= 0 (land, open) and cells outside the box
+ * are not written; what land cells of c or faces that touch land hold never reaches a written cell.  ssha is the array the
+ * time step produced from the same level-n inputs; an open cell's c is the boundary value, kept by the caller in both buffers.
+ * c_in and c_out are HOST arrays of ntracers device pointers.  Asynchronous on `stream`, may be captured.  Any 8-byte-aligned
+ * bases and any ld give the same bits (an even ld and 16-byte bases take the wave-tile sweep; the HOOK key tracer_kernel = 1
+ * forces the general path).  An empty box launches nothing.  DLESM_EINVAL before anything is launched: ntracers outside
+ * 1..DLESM_TRACER_MAX, a null pointer, a box that does not fit with its ring, a c_out[k] that overlaps an input, a c_in or
+ * another c_out. */
+enum { DLESM_TRACER_MAX = 8 };
+int dlesm_tracer_step_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                          const int *tmask, const double *area_t, const double *un, const double *vn,
+                          const double *hu, const double *hv, const double *ht,
+                          const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                          const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+/* The distributed form: bit for bit in every cell, dlesm_tracer_step_f64 followed by dlesm_halo_exchange_multi_f64(plan, c_out,
+ * ntracers, DLESM_DIRS_ALL).  In: the flow arrays, tmask and c_in with valid depth-1 halos towards every neighbour.  Out: c_out
+ * with valid depth-1 halos; a time loop only rotates the pointers.  A plan without messages: dlesm_tracer_step_f64.  A plan
+ * with messages must be a depth-1 plan for ld x ny (DLESM_EINVAL otherwise, as for a null plan and every refusal above, before
+ * anything is launched or exchanged).  Over connected mailboxes the exchange runs in ceil(ntracers / mailbox fields) turns on
+ * every rank, whatever the box.  Collective: every rank calls it, in the same order. */
+int dlesm_tracer_step_dm(dlesm_halo_plan *plan, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                         const int *tmask, const double *area_t, const double *un, const double *vn,
+                         const double *hu, const double *hv, const double *ht,
+                         const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                         const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);
