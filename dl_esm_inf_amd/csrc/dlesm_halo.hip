@@ -1969,16 +1969,18 @@ extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_pl
                                  ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
 }
 
-// Tracer transport on a decomposed grid: the single-domain sweep, then ONE exchange of the new
-// tracers -- dlesm_tracer_step_f64 followed by dlesm_halo_exchange_multi_f64, with dlesm_nemolite_step_dm's guards and its
-// rule for the mailbox turns.
-extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
-                                    int ystop, const int *tmask, const double *area_t, const double *un, const double *vn,
-                                    const double *hu, const double *hv, const double *ht, const double *sshn_t,
-                                    const double *sshn_u, const double *sshn_v, const double *ssha,
-                                    const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+// Tracer transport on a decomposed grid (DESIGN.md sections 6.10 and 6.11): the single-domain sweep, then ONE exchange of the
+// new tracers -- `entry` followed by dlesm_halo_exchange_multi_f64, with dlesm_nemolite_step_dm's guards and its rule for the
+// mailbox turns.  `depth` is the halo depth a plan with messages must exchange: 1 for the upwind sweep, 2 for the limited one.
+typedef int (*tracer_entry)(double, int, int, int, int, int, int, const int *, const double *, const double *, const double *,
+                            const double *, const double *, const double *, const double *, const double *, const double *,
+                            const double *, const double *const *, double *const *, int, void *);
+static int tracer_step_dm_impl(const char *who, tracer_entry entry, int depth, dlesm_halo_plan *p, double rdt, int ld, int ny,
+                               int xstart, int xstop, int ystart, int ystop, const int *tmask, const double *area_t,
+                               const double *un, const double *vn, const double *hu, const double *hv, const double *ht,
+                               const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                               const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
-    static const char *who = "dlesm_tracer_step_dm";
     clear_error();
     DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
@@ -1986,8 +1988,8 @@ extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int 
     const nemo::TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
     if (int rc = nemo::tracer_check(who, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers)) return rc;
     auto step = [&] {
-        return dlesm_tracer_step_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t,
-                                     sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
+        return entry(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha,
+                     c_in, c_out, ntracers, stream);
     };
     if (p->sends.empty() && p->recvs.empty()) return step();     // no neighbour: the single-domain entry, bit for bit
 
@@ -1998,8 +2000,8 @@ extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int 
         const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
         const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
         if (!xdir && !ydir) continue;
-        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 1, "%s: the plan exchanges depth-%d halos, the step needs depth 1 "
-                      "(a grid decomposed with halo_width = 1)", who, xdir ? m.nx : m.ny);
+        DLESM_REQUIRE((xdir ? m.nx : m.ny) == depth, "%s: the plan exchanges depth-%d halos, the step needs depth %d "
+                      "(a grid decomposed with halo_width = %d)", who, xdir ? m.nx : m.ny, depth, depth);
     }
     DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
     hipStream_t s = (hipStream_t)stream;
@@ -2013,6 +2015,28 @@ extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int 
     for (int k = 0; k < ntracers; k += turn)
         if (int rc = exchange_on(p, c_out + k, std::min(turn, ntracers - k), DLESM_DIRS_ALL, s)) return rc;
     return DLESM_OK;
+}
+
+extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
+                                    int ystop, const int *tmask, const double *area_t, const double *un, const double *vn,
+                                    const double *hu, const double *hv, const double *ht, const double *sshn_t,
+                                    const double *sshn_u, const double *sshn_v, const double *ssha,
+                                    const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+{
+    return tracer_step_dm_impl("dlesm_tracer_step_dm", dlesm_tracer_step_f64, 1, p, rdt, ld, ny, xstart, xstop, ystart, ystop,
+                               tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
+}
+
+extern "C" int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
+                                          int ystop, const int *tmask, const double *area_t, const double *un,
+                                          const double *vn, const double *hu, const double *hv, const double *ht,
+                                          const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                                          const double *ssha, const double *const *c_in, double *const *c_out, int ntracers,
+                                          void *stream)
+{
+    return tracer_step_dm_impl("dlesm_tracer_step_muscl_dm", dlesm_tracer_step_muscl_f64, 2, p, rdt, ld, ny, xstart, xstop,
+                               ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
+                               ntracers, stream);
 }
 
 extern "C" int dlesm_global_sum_f64(double *value)

@@ -66,6 +66,37 @@ __device__ __forceinline__ double tracer_point(const TracerFlow &f, double c, do
     return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
 }
 
+// Second-order limited tracer transport: the monotonised-central slope of c at a cell from the
+// differences to its two neighbours along one axis (c_m, c, c_p), or 0.0 where `on` is false -- `on` is "the cell is wet and
+// neither neighbour is land", T outside the array counting as land.  Compare-and-select, never fmin / fmax (a NaN difference
+// gives 0.0), and no division.
+__device__ __forceinline__ double muscl_slope(bool on, double c_m, double c, double c_p)
+{
+    const double a = c - c_m, b = c_p - c;
+    const double a2 = 2.0 * fabs(a), b2 = 2.0 * fabs(b), m = 0.5 * fabs(a + b);
+    double lo = a2 < b2 ? a2 : b2;
+    lo = m < lo ? m : lo;
+    const double mc = (a > 0.0 && b > 0.0) ? lo : ((a < 0.0 && b < 0.0) ? -lo : 0.0);
+    return on ? mc : 0.0;
+}
+// c_out(i,j) of a wet cell with the face values reconstructed from the upwind cell's slope: sx, sy = the slopes at (i, j),
+// sx_e, sx_w at (i+1, j), (i-1, j), sy_n, sy_s at (i, j+1), (i, j-1); everything else as tracer_point.  A zero slope gives
+// tracer_point's face value (c + 0.0, c - 0.0), so coasts, open boundaries and a constant tracer fall back to section 6.10.
+__device__ __forceinline__ double tracer_point_muscl(const TracerFlow &f, double c, double c_e, double c_w, double c_n,
+                                                     double c_s, double sx, double sx_e, double sx_w, double sy, double sy_n,
+                                                     double sy_s)
+{
+    const double ce = f.r1 >= 0.0 ? c + 0.5 * sx : c_e - 0.5 * sx_e;
+    const double cw = f.r2 >= 0.0 ? c_w + 0.5 * sx_w : c - 0.5 * sx;
+    const double cn = f.r3 >= 0.0 ? c + 0.5 * sy : c_n - 0.5 * sy_n;
+    const double cs = f.r4 >= 0.0 ? c_s + 0.5 * sy_s : c - 0.5 * sy;
+    const double F1 = f.e ? f.r1 * ce : 0.0;
+    const double F2 = f.w ? f.r2 * cw : 0.0;
+    const double F3 = f.n ? f.r3 * cn : 0.0;
+    const double F4 = f.s ? f.r4 * cs : 0.0;
+    return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
+}
+
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,
 // 1 = the one east (north) of it; ax = area_u (area_v) of the face
 __device__ __forceinline__ double ssh_point(long long t0, long long t1, double a0, double a1, double s0, double s1, double ax)

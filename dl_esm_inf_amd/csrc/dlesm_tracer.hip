@@ -14,6 +14,18 @@
 // beyond, against 100 K for K single-tracer sweeps.
 //
 // tracer_direct<NT>: one cell per thread -- odd leading dimensions, unaligned bases and the HOOK key tracer_kernel = 1.
+//
+// Second-order limited transport (dlesm_tracer_step_muscl_f64): the same sweep with the value a face
+// carries rebuilt from the upwind cell's monotonised-central slope (muscl_slope / tracer_point_muscl, dlesm_nemolite.h).  The
+// stencil reaches two cells.  tracer_muscl_tile<NT> keeps the shape above and feeds the wave's two ends with two load-only
+// lanes: lanes 1..62 own a chunk, lanes 0 and 63 load the chunk west / east of them, waves step by 62 chunks.  Every lane
+// computes the x slopes of its own two columns from its neighbours' near columns (one DPP shift each way) and hands them on by
+// a second shift, so both columns of lanes c-1 and c+1 reach lane c with four shifts of doubles per tracer and no lane
+// evaluates a slope twice; the alternative, 63 owned chunks and extra edge loads, needs two scalar loads per row, array and
+// tracer at each end and a second evaluation of the end slopes behind a lane test.  Rows j-2 .. j+2 of the lane's own columns
+// are loaded for c and for the mask.  A chunk or a row outside the array is loaded clamped and its mask forced to 0 by a
+// select, which zeroes every slope that would have read it.  tracer_muscl_direct<NT>: one cell per thread, HOOK key
+// tracer_muscl_kernel = 1.
 #include "dlesm_nemolite.h"
 
 namespace dlesm {
@@ -137,9 +149,137 @@ __global__ __launch_bounds__(256) void tracer_direct(TracerArgs<NT> a, int ld, i
     }
 }
 
+// ---- second-order limited transport ----------------------------------------------------------
+
+constexpr int MUSCL_CHUNKS = 62;      // chunks a wave owns; lanes 0 and 63 only load
+
+// what one tracer's update reads: rows j-2 .. j+2 of the lane's two columns
+struct MusclRows {
+    d2 ss, s, m, n, nn;
+};
+__device__ __forceinline__ MusclRows load_muscl_rows(const double *c, size_t oss, size_t os, size_t o, size_t on, size_t onn)
+{
+    return MusclRows{*(const d2 *)(c + oss), *(const d2 *)(c + os), *(const d2 *)(c + o), *(const d2 *)(c + on),
+                     *(const d2 *)(c + onn)};
+}
+
+// (x0:x1, y0:y1) = the box (0-based); nxw tiles per row, lane 1 of tile 0 holds chunk c_first
+template <int NT>
+__global__ __launch_bounds__(256) void tracer_muscl_tile(TracerArgs<NT> a, int ld, int ny, int x0, int x1, int y0, int y1,
+                                                         int c_first, int nxw)
+{
+    const TracerFields &f = a.f;
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int xw = w % nxw, j = y0 + w / nxw;
+    if (j > y1) return;
+    const int c = c_first + xw * MUSCL_CHUNKS + lane - 1;  // this lane's chunk (2 columns); lane 0: the one west of the tile
+    if (c - lane + 1 > x1 / 2) return;                     // idle padding tile
+    const int c_ld = ld / 2 - 1, cl = c < 0 ? 0 : (c < c_ld ? c : c_ld);
+    const bool in = c == cl;                               // the chunk lies in the array: otherwise loaded clamped, mask 0
+    const bool own = lane != 0 && lane != 63;
+    const bool m0 = own && c * 2 >= x0 && c * 2 <= x1, m1 = own && c * 2 + 1 >= x0 && c * 2 + 1 <= x1;
+    const size_t col = (size_t)cl * 2, row = (size_t)j * ld, o = row + col;
+
+    // the land exit: the mask of the row first; a wave that owns no wet cell of the box stores nothing
+    i2 t = *(const i2 *)(f.tmask + o);
+    const bool wet0 = m0 && t.x > 0, wet1 = m1 && t.y > 0;
+    if (__ballot(wet0 || wet1) == 0) return;
+
+    // rows j-1 and j+1 lie in the array (the box has its ring); rows j-2 and j+2 may not: clamped, mask 0
+    const bool in_ss = j >= 2, in_nn = j + 2 < ny;
+    const size_t os = o - ld, on = o + ld, oss = (size_t)(in_ss ? j - 2 : 0) * ld + col,
+                 onn = (size_t)(in_nn ? j + 2 : ny - 1) * ld + col;
+    MusclRows cur = load_muscl_rows(a.c_in[0], oss, os, o, on, onn);     // the first tracer's loads go out with the flow's
+
+    i2 ts = *(const i2 *)(f.tmask + os), tn = *(const i2 *)(f.tmask + on);
+    i2 tss = *(const i2 *)(f.tmask + oss), tnn = *(const i2 *)(f.tmask + onn);
+    const d2 su = *(const d2 *)(f.sshn_u + o), hu = *(const d2 *)(f.hu + o), un = *(const d2 *)(f.un + o);
+    const d2 sv = *(const d2 *)(f.sshn_v + o), hv = *(const d2 *)(f.hv + o), vn = *(const d2 *)(f.vn + o);
+    const d2 sv_s = *(const d2 *)(f.sshn_v + os), hv_s = *(const d2 *)(f.hv + os), vn_s = *(const d2 *)(f.vn + os);
+    const d2 ht = *(const d2 *)(f.ht + o), st = *(const d2 *)(f.sshn_t + o), sa = *(const d2 *)(f.ssha + o);
+    const d2 ar = *(const d2 *)(f.area_t + o);
+
+    if (!in) t = i2{0, 0}, ts = i2{0, 0}, tn = i2{0, 0};
+    if (!in || !in_ss) tss = i2{0, 0};
+    if (!in || !in_nn) tnn = i2{0, 0};
+
+    const double su_w = from_lower<true>(su.y), hu_w = from_lower<true>(hu.y), un_w = from_lower<true>(un.y);
+    const int tw = __builtin_amdgcn_mov_dpp(t.y, 0x138, 0xf, 0xf, true);      // (lane 0: 0, never used)
+    const int te = __builtin_amdgcn_mov_dpp(t.x, 0x130, 0xf, 0xf, true);      // (lane 63: 0, never used)
+    const TracerFlow f0 = tracer_flow(a.rdt, su.x, su_w, sv.x, sv_s.x, hu.x, hu_w, hv.x, hv_s.x, un.x, un_w, vn.x, vn_s.x,
+                                      ar.x, ht.x, st.x, sa.x, t.y, tw, tn.x, ts.x);
+    const TracerFlow f1 = tracer_flow(a.rdt, su.y, su.x, sv.y, sv_s.y, hu.y, hu.x, hv.y, hv_s.y, un.y, un.x, vn.y, vn_s.y,
+                                      ar.y, ht.y, st.y, sa.y, te, t.x, tn.y, ts.y);
+    // where a slope is taken: a wet cell between two cells that are not land.  x: the lane's two columns (lane 0's west
+    // column and lane 63's east column get none, and nothing asks for them); y: rows j-1, j, j+1 of both columns
+    const bool x_0 = t.x > 0 && tw != 0 && t.y != 0, x_1 = t.y > 0 && t.x != 0 && te != 0;
+    const bool ys_0 = ts.x > 0 && tss.x != 0 && t.x != 0, ys_1 = ts.y > 0 && tss.y != 0 && t.y != 0;
+    const bool ym_0 = t.x > 0 && ts.x != 0 && tn.x != 0, ym_1 = t.y > 0 && ts.y != 0 && tn.y != 0;
+    const bool yn_0 = tn.x > 0 && t.x != 0 && tnn.x != 0, yn_1 = tn.y > 0 && t.y != 0 && tnn.y != 0;
+
+    const size_t oc = row + (size_t)c * 2;
+#pragma unroll
+    for (int k = 0; k < NT; k++) {
+        MusclRows nxt = cur;
+        if (k + 1 < NT) nxt = load_muscl_rows(a.c_in[k + 1], oss, os, o, on, onn);
+        const double c_w = from_lower<true>(cur.m.y), c_e = from_upper<true>(cur.m.x);
+        const double sx0 = muscl_slope(x_0, c_w, cur.m.x, cur.m.y), sx1 = muscl_slope(x_1, cur.m.x, cur.m.y, c_e);
+        const double sx_w = from_lower<true>(sx1), sx_e = from_upper<true>(sx0);
+        const double o0 = tracer_point_muscl(f0, cur.m.x, cur.m.y, c_w, cur.n.x, cur.s.x, sx0, sx1, sx_w,
+                                             muscl_slope(ym_0, cur.s.x, cur.m.x, cur.n.x),
+                                             muscl_slope(yn_0, cur.m.x, cur.n.x, cur.nn.x),
+                                             muscl_slope(ys_0, cur.ss.x, cur.s.x, cur.m.x));
+        const double o1 = tracer_point_muscl(f1, cur.m.y, c_e, cur.m.x, cur.n.y, cur.s.y, sx1, sx_e, sx0,
+                                             muscl_slope(ym_1, cur.s.y, cur.m.y, cur.n.y),
+                                             muscl_slope(yn_1, cur.m.y, cur.n.y, cur.nn.y),
+                                             muscl_slope(ys_1, cur.ss.y, cur.s.y, cur.m.y));
+        store_pair(a.c_out[k] + oc, o0, o1, wet0, wet1);
+        cur = nxt;
+    }
+}
+
+// one cell per thread: odd leading dimensions, unaligned bases, the HOOK key tracer_muscl_kernel
+template <int NT>
+__global__ __launch_bounds__(256) void tracer_muscl_direct(TracerArgs<NT> a, int ld, int ny, int x0, int x1, int y0, int y1)
+{
+    const TracerFields &f = a.f;
+    const int i = x0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > x1) return;
+    // columns i-1, i+1 and rows j-1, j+1 lie in the array (the box has its ring); i-2, i+2, j-2, j+2 may not: clamped, mask 0
+    const bool in_ww = i >= 2, in_ee = i + 2 < ld;
+    const int iww = in_ww ? i - 2 : 0, iee = in_ee ? i + 2 : ld - 1;
+    for (int j = y0 + blockIdx.y; j <= y1; j += gridDim.y) {
+        const size_t o = (size_t)j * ld + i;
+        const int t = f.tmask[o];
+        if (t <= 0) continue;
+        const bool in_ss = j >= 2, in_nn = j + 2 < ny;
+        const size_t oww = (size_t)j * ld + iww, oee = (size_t)j * ld + iee;
+        const size_t oss = (size_t)(in_ss ? j - 2 : 0) * ld + i, onn = (size_t)(in_nn ? j + 2 : ny - 1) * ld + i;
+        const int t_e = f.tmask[o + 1], t_w = f.tmask[o - 1], t_n = f.tmask[o + ld], t_s = f.tmask[o - ld];
+        const int l_ee = f.tmask[oee], l_ww = f.tmask[oww], l_nn = f.tmask[onn], l_ss = f.tmask[oss];
+        const int t_ee = in_ee ? l_ee : 0, t_ww = in_ww ? l_ww : 0, t_nn = in_nn ? l_nn : 0, t_ss = in_ss ? l_ss : 0;
+        const TracerFlow fl = tracer_flow(a.rdt, f.sshn_u[o], f.sshn_u[o - 1], f.sshn_v[o], f.sshn_v[o - ld], f.hu[o],
+                                          f.hu[o - 1], f.hv[o], f.hv[o - ld], f.un[o], f.un[o - 1], f.vn[o], f.vn[o - ld],
+                                          f.area_t[o], f.ht[o], f.sshn_t[o], f.ssha[o], t_e, t_w, t_n, t_s);
+        const bool x_m = t_e != 0 && t_w != 0, y_m = t_n != 0 && t_s != 0;           // (t > 0 here)
+        const bool x_e = t_e > 0 && t_ee != 0, x_w = t_w > 0 && t_ww != 0;            // (t != 0 here)
+        const bool y_n = t_n > 0 && t_nn != 0, y_s = t_s > 0 && t_ss != 0;
+#pragma unroll
+        for (int k = 0; k < NT; k++) {
+            const double *c = a.c_in[k];
+            const double cm = c[o], ce = c[o + 1], cw = c[o - 1], cn = c[o + ld], cs = c[o - ld];
+            a.c_out[k][o] = tracer_point_muscl(fl, cm, ce, cw, cn, cs, muscl_slope(x_m, cw, cm, ce),
+                                               muscl_slope(x_e, cm, ce, c[oee]), muscl_slope(x_w, c[oww], cw, cm),
+                                               muscl_slope(y_m, cs, cm, cn), muscl_slope(y_n, cm, cn, c[onn]),
+                                               muscl_slope(y_s, c[oss], cs, cm));
+        }
+    }
+}
+
 struct Launch {
-    bool tile;
-    int ld, x0, x1, y0, y1, c_first, nxw, tpb;
+    bool tile, muscl;
+    int ld, ny, x0, x1, y0, y1, c_first, nxw, tpb;
     hipStream_t st;
 };
 
@@ -150,7 +290,16 @@ void launch(const Launch &l, double rdt, const TracerFields &f, const double *co
     a.f = f, a.rdt = rdt;
     for (int k = 0; k < NT; k++) a.c_in[k] = c_in[k], a.c_out[k] = c_out[k];
     const int h = l.y1 - l.y0 + 1;
-    if (l.tile) {
+    if (l.muscl) {
+        if (l.tile) {
+            const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
+            hipLaunchKernelGGL(tracer_muscl_tile<NT>, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1,
+                               l.c_first, l.nxw);
+        } else {
+            hipLaunchKernelGGL(tracer_muscl_direct<NT>, dim3((l.x1 - l.x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, l.st,
+                               a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1);
+        }
+    } else if (l.tile) {
         const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
         hipLaunchKernelGGL(tracer_tile<NT>, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.x0, l.x1, l.y0, l.y1, l.c_first,
                            l.nxw);
@@ -162,7 +311,7 @@ void launch(const Launch &l, double rdt, const TracerFields &f, const double *co
 
 } // namespace
 
-// every refusal of DESIGN.md section 6.10, before anything is launched (dlesm_tracer_step_f64, dlesm_tracer_step_dm)
+// every refusal of DESIGN.md section 6.10, before anything is launched (the four tracer entries)
 int nemo::tracer_check(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, const TracerFields &f,
                        const double *const *c_in, double *const *c_out, int ntracers)
 {
@@ -193,29 +342,30 @@ int nemo::tracer_check(const char *who, int ld, int ny, int xstart, int xstop, i
 
 using namespace dlesm;
 
-extern "C" int dlesm_tracer_step_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                                     const int *tmask, const double *area_t, const double *un, const double *vn,
-                                     const double *hu, const double *hv, const double *ht, const double *sshn_t,
-                                     const double *sshn_u, const double *sshn_v, const double *ssha,
-                                     const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+namespace {
+
+// the body of both single-domain entries: the refusals, the path, at most NT_MAX tracers per launch
+int tracer_step(const char *who, bool muscl, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                const TracerFields &f, const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
-    static const char *who = "dlesm_tracer_step_f64";
     if (int rc = ensure_device()) return rc;
-    const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
     if (int rc = tracer_check(who, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers)) return rc;
     if (xstop < xstart || ystop < ystart) return DLESM_OK;   // empty box: a zero-trip loop nest
 
-    bool aligned = ld % 2 == 0 && (uintptr_t)tmask % 8 == 0;
-    for (const double *p : {area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha}) aligned = aligned && (uintptr_t)p % 16 == 0;
+    bool aligned = ld % 2 == 0 && (uintptr_t)f.tmask % 8 == 0;
+    for (const double *p : {f.area_t, f.un, f.vn, f.hu, f.hv, f.ht, f.sshn_t, f.sshn_u, f.sshn_v, f.ssha})
+        aligned = aligned && (uintptr_t)p % 16 == 0;
     for (int k = 0; k < ntracers; k++) aligned = aligned && (uintptr_t)c_in[k] % 16 == 0 && (uintptr_t)c_out[k] % 16 == 0;
 
     Launch l{};
-    l.tile = aligned && tuning("tracer_kernel", 0) == 0;
-    l.ld = ld, l.x0 = xstart - 1, l.x1 = xstop - 1, l.y0 = ystart - 1, l.y1 = ystop - 1;
+    l.muscl = muscl;
+    l.tile = aligned && (muscl ? tuning("tracer_muscl_kernel", 0) : tuning("tracer_kernel", 0)) == 0;
+    l.ld = ld, l.ny = ny, l.x0 = xstart - 1, l.x1 = xstop - 1, l.y0 = ystart - 1, l.y1 = ystop - 1;
     l.st = (hipStream_t)stream;
     if (l.tile) {
+        const int chunks = muscl ? MUSCL_CHUNKS : TILE_CHUNKS;
         l.c_first = (l.x0 / 2) & ~7;                     // tiles anchored on a 128-byte line of the row
-        l.nxw = (l.x1 / 2 - l.c_first + TILE_CHUNKS) / TILE_CHUNKS, l.tpb = 4;
+        l.nxw = (l.x1 / 2 - l.c_first + chunks) / chunks, l.tpb = 4;
         choose_block_shape(&l.nxw, &l.tpb, 4);
         if (l.tpb > 4) l.tpb = 4;                        // __launch_bounds__(256)
     }
@@ -230,4 +380,28 @@ extern "C" int dlesm_tracer_step_f64(double rdt, int ld, int ny, int xstart, int
         DLESM_HIP_TRY(hipGetLastError());
     }
     return DLESM_OK;
+}
+
+} // namespace
+
+extern "C" int dlesm_tracer_step_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                     const int *tmask, const double *area_t, const double *un, const double *vn,
+                                     const double *hu, const double *hv, const double *ht, const double *sshn_t,
+                                     const double *sshn_u, const double *sshn_v, const double *ssha,
+                                     const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+{
+    const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
+    return tracer_step("dlesm_tracer_step_f64", false, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers,
+                       stream);
+}
+
+extern "C" int dlesm_tracer_step_muscl_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                           const int *tmask, const double *area_t, const double *un, const double *vn,
+                                           const double *hu, const double *hv, const double *ht, const double *sshn_t,
+                                           const double *sshn_u, const double *sshn_v, const double *ssha,
+                                           const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+{
+    const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
+    return tracer_step("dlesm_tracer_step_muscl_f64", true, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers,
+                       stream);
 }

@@ -317,6 +317,37 @@ def invoke_tracer_step_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, ss
                                                                                  stream)))
 
 
+def invoke_tracer_step_muscl(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """invoke_tracer_step with second-order limited face values (dlesm_tracer_step_muscl_f64): the
+    upwind cell's monotonised-central slope rebuilds what a face carries; land, open cells and cells next to land keep the
+    upwind value.  Same arguments and rules.  Single domain: stops on a decomposed grid."""
+    g = ssha.grid
+    if g.decomp is not None and g.decomp.ndomains > 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_muscl: the grid is decomposed (%d subdomains): the new "
+                                             "tracers need a halo exchange; use invoke_tracer_step_muscl_dm"
+                               % g.decomp.ndomains)
+    check(_cabi.lib().dlesm_tracer_step_muscl_f64(*_tracer_args("invoke_tracer_step_muscl", rdt, c_out, c_in, ssha, un, vn, ht,
+                                                                hu, hv, sshn_t, sshn_u, sshn_v, stream)))
+
+
+def invoke_tracer_step_muscl_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """invoke_tracer_step_muscl and ONE depth-2 exchange of the new tracers on a decomposed grid (dlesm_tracer_step_muscl_dm,
+    DESIGN.md section 6.11), bit for bit invoke_tracer_step_muscl -> halo_exchange_multi(c_out).  The grid's mask and c_in
+    need valid depth-2 halos, the flow fields depth-1 halos; c_out leaves with depth-2 halos.  Collective.  Stops on a grid
+    with halo_width other than 2."""
+    g = ssha.grid
+    hw = getattr(g, "halo_width", 1)
+    if hw != 2:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_muscl_dm: the grid has halo_width %d; the step reads two "
+                                             "cells and exchanges depth-2 halos: decompose the grid with halo_width = 2" % hw)
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_muscl_dm: the grid has no message tables (grid_init after "
+                                             "decompose)")
+    check(_cabi.lib().dlesm_tracer_step_muscl_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_muscl_dm", rdt, c_out,
+                                                                                       c_in, ssha, un, vn, ht, hu, hv, sshn_t,
+                                                                                       sshn_u, sshn_v, stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

@@ -1010,6 +1010,38 @@ int dlesm_tracer_step_dm(dlesm_halo_plan *plan, double rdt, int ld, int ny, int 
                          const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
                          const double *const *c_in, double *const *c_out, int ntracers, void *stream);
 
+/* Second-order limited tracer transport: dlesm_tracer_step_f64 with the value a face carries rebuilt
+ * from the upwind cell's monotonised-central slope.  T(i,j) = tmask(i,j) inside the array and 0 outside it:
+ *     MC(a, b): a2 = 2*|a|; b2 = 2*|b|; m = 0.5*|a + b|; lo = a2 < b2 ? a2 : b2; lo = m < lo ? m : lo
+ *               MC = (a > 0 && b > 0) ? lo : ((a < 0 && b < 0) ? -lo : 0)
+ *     sx(i,j) = (T(i,j) > 0 && T(i-1,j) != 0 && T(i+1,j) != 0) ? MC(c(i,j) - c(i-1,j), c(i+1,j) - c(i,j)) : 0
+ *     sy(i,j) = (T(i,j) > 0 && T(i,j-1) != 0 && T(i,j+1) != 0) ? MC(c(i,j) - c(i,j-1), c(i,j+1) - c(i,j)) : 0
+ *     ce = r1 >= 0 ? c(i,j)   + 0.5*sx(i,j)   : c(i+1,j) - 0.5*sx(i+1,j)      cw = r2 >= 0 ? c(i-1,j) + 0.5*sx(i-1,j) : c(i,j) - 0.5*sx(i,j)
+ *     cn = r3 >= 0 ? c(i,j)   + 0.5*sy(i,j)   : c(i,j+1) - 0.5*sy(i,j+1)      cs = r4 >= 0 ? c(i,j-1) + 0.5*sy(i,j-1) : c(i,j) - 0.5*sy(i,j)
+ *     F1 = T(i+1,j) != 0 ? r1*ce : 0    F2 = T(i-1,j) != 0 ? r2*cw : 0    F3 = T(i,j+1) != 0 ? r3*cn : 0    F4 = T(i,j-1) != 0 ? r4*cs : 0
+ * and c_out[k](i,j) as above.  Compare-and-select throughout, no division but the rule's own; land, open cells and cells next
+ * to land have slope zero, so coasts and open boundaries carry the upwind value, a NaN on land (two cells away included) never
+ * reaches a written cell, and a constant nonzero tracer gets dlesm_tracer_step_f64's bits.  Nothing outside the array is read:
+ * the box needs only its one-cell ring.  Arguments, aliasing rules, refusals and the asynchronous contract are those of
+ * dlesm_tracer_step_f64; the HOOK key tracer_muscl_kernel = 1 forces the general path.  Keeps a profile's range while
+ * |r| * rdt / (area_t * (ht + ssha)) <= 1/2. */
+int dlesm_tracer_step_muscl_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                const int *tmask, const double *area_t, const double *un, const double *vn,
+                                const double *hu, const double *hv, const double *ht,
+                                const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                                const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+/* The distributed form: bit for bit in every cell, dlesm_tracer_step_muscl_f64 followed by dlesm_halo_exchange_multi_f64(plan,
+ * c_out, ntracers, DLESM_DIRS_ALL).  In: tmask and c_in with valid depth-2 halos towards every neighbour, the flow arrays with
+ * depth-1 halos.  Out: c_out with valid depth-2 halos.  A plan without messages: dlesm_tracer_step_muscl_f64.  A plan with
+ * messages must be a depth-2 plan for ld x ny, from a grid decomposed with halo_width = 2 (DLESM_EINVAL otherwise, as for a null
+ * plan and every refusal above, before anything is launched or exchanged).  Guards, mailbox turns and the collective contract
+ * are dlesm_tracer_step_dm's. */
+int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *plan, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                               const int *tmask, const double *area_t, const double *un, const double *vn,
+                               const double *hu, const double *hv, const double *ht,
+                               const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                               const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);

@@ -5,6 +5,10 @@ of section 6.10 -- 84 B/cell of flow per launch (two launches beyond four tracer
 library's copy ceiling measured in the same run on the same arrays (dlesm_lab_stream_copy_f64, 8 arrays read + 1 written).
 The byte model counts the bytes the algorithm needs, not the traffic the sweep causes (it re-reads the rows above and below,
 mostly from cache).  Writes profiles/r10_tracer.json and prints the LAB_NOTES table.
+The second-order limited entry (dlesm_tracer_step_muscl_f64) is timed beside it in the same windows,
+one call with K tracers: its compulsory bytes are the same 84 + 16 K B/cell (rows j-2 and j+2 are re-reads), so it is given
+under the same byte model and as a ratio to the same-run upwind call.  Those rows go to profiles/r13_tracer_muscl.json
+(TRACER_PROBE_MUSCL_OUT names another file).
     python scripts/tracer_probe.py [OUT.json] [WINDOWS] [N ...]"""
 import ctypes as C
 import json
@@ -19,6 +23,7 @@ import torch  # noqa: E402
 import dl_esm_inf_amd as D  # noqa: E402
 
 out_path = sys.argv[1] if len(sys.argv) > 1 else "profiles/r10_tracer.json"
+muscl_path = os.environ.get("TRACER_PROBE_MUSCL_OUT", "profiles/r13_tracer_muscl.json")
 windows = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 sizes = [int(a) for a in sys.argv[3:]] or [4096, 8192]
 KS = (1, 2, 4, 8)
@@ -32,6 +37,10 @@ result = {"what": "ms per K tracers, medians of interleaved windows (device even
                   "dlesm_tracer_step_f64 call with K tracers, split = K calls with one tracer each; GB/s under the byte model "
                   "(84 B/cell of flow per launch + 16 B/cell per tracer); copy = dlesm_lab_stream_copy_f64, 8 read + 1 written",
           "windows": windows, "device": torch.cuda.get_device_name(0), "sizes": {}}
+muscl_result = {"what": "ms per K tracers, medians of the same interleaved windows: muscl = one dlesm_tracer_step_muscl_f64 "
+                        "call with K tracers, upwind = one dlesm_tracer_step_f64 call with K tracers; GB/s under the same "
+                        "byte model (rows j-2 and j+2 are re-reads); muscl_over_upwind = the ratio of the two times",
+                "windows": windows, "device": result["device"], "sizes": {}}
 
 
 def model_bytes(k, launches):
@@ -67,6 +76,9 @@ for n in sizes:
     def one(k):
         return lambda: D.psy.invoke_tracer_step(20.0, Co[:k], Ci[:k], *flow, stream=s)
 
+    def muscl(k):
+        return lambda: D.psy.invoke_tracer_step_muscl(20.0, Co[:k], Ci[:k], *flow, stream=s)
+
     def split(k):
         def fn():
             for m in range(k):
@@ -77,6 +89,7 @@ for n in sizes:
     for k in KS:
         variants["one_%d" % k] = one(k)
         variants["split_%d" % k] = split(k)
+        variants["muscl_%d" % k] = muscl(k)
     launches = 10
     times = {k: [] for k in variants}
     torch.cuda.synchronize()
@@ -108,6 +121,16 @@ for n in sizes:
         print("| %d | %.4f | %.0f (%d) | %.4f | %.0f (%d) | %.3f | %.0f |" % (k, med["one_%d" % k], g1, b1, med["split_%d" % k],
                                                                               gk, bk, ratio, copy_gbs), flush=True)
     result["sizes"][str(n)] = r
+    rm = {"extents": [g.nx, g.ny], "cells": cells, "copy_gbs": copy_gbs, "rows": []}
+    print("| K | limited, ms | GB/s (model B/cell) | upwind, ms | limited / upwind |")
+    print("|---|---|---|---|---|")
+    for k in KS:
+        b1 = model_bytes(k, 1 if k <= 4 else 2)
+        tm_, tu = med["muscl_%d" % k], med["one_%d" % k]
+        rm["rows"].append({"k": k, "muscl_ms": tm_, "model_bytes": b1, "muscl_gbs": b1 * cells / tm_ / 1e6, "upwind_ms": tu,
+                           "muscl_over_upwind": tm_ / tu})
+        print("| %d | %.4f | %.0f (%d) | %.4f | %.3f |" % (k, tm_, b1 * cells / tm_ / 1e6, b1, tu, tm_ / tu), flush=True)
+    muscl_result["sizes"][str(n)] = rm
     del F, Ci, Co, flow, g, variants
     torch.cuda.empty_cache()
 
@@ -115,3 +138,7 @@ os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
 with open(out_path, "w") as f:
     json.dump(result, f, indent=1)
 print("wrote", out_path)
+os.makedirs(os.path.dirname(muscl_path) or ".", exist_ok=True)
+with open(muscl_path, "w") as f:
+    json.dump(muscl_result, f, indent=1)
+print("wrote", muscl_path)
