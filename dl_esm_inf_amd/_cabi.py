@@ -256,6 +256,8 @@ PROTOTYPES = {
     "dlesm_tracer_step_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_muscl_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_muscl_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_tracer_step_hancock_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_tracer_step_hancock_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_shallow_step_smooth_dm_pipelined": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_global_sum_f64": (_i, [C.POINTER(_d)]),
     "dlesm_global_max_f64": (_i, [C.POINTER(_d)]),

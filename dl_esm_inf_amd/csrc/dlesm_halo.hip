@@ -1969,9 +1969,9 @@ extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_pl
                                  ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
 }
 
-// Tracer transport on a decomposed grid (DESIGN.md sections 6.10 and 6.11): the single-domain sweep, then ONE exchange of the
+// Tracer transport on a decomposed grid (DESIGN.md sections 6.10, 6.11 and 6.12): the single-domain sweep, then ONE exchange of the
 // new tracers -- `entry` followed by dlesm_halo_exchange_multi_f64, with dlesm_nemolite_step_dm's guards and its rule for the
-// mailbox turns.  `depth` is the halo depth a plan with messages must exchange: 1 for the upwind sweep, 2 for the limited one.
+// mailbox turns.  `depth` is the halo depth a plan with messages must exchange: 1 for the upwind sweep, 2 for the two limited ones.
 typedef int (*tracer_entry)(double, int, int, int, int, int, int, const int *, const double *, const double *, const double *,
                             const double *, const double *, const double *, const double *, const double *, const double *,
                             const double *, const double *const *, double *const *, int, void *);
@@ -2035,6 +2035,18 @@ extern "C" int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *p, double rdt, int ld
                                           void *stream)
 {
     return tracer_step_dm_impl("dlesm_tracer_step_muscl_dm", dlesm_tracer_step_muscl_f64, 2, p, rdt, ld, ny, xstart, xstop,
+                               ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
+                               ntracers, stream);
+}
+
+extern "C" int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
+                                            int ystop, const int *tmask, const double *area_t, const double *un,
+                                            const double *vn, const double *hu, const double *hv, const double *ht,
+                                            const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                                            const double *ssha, const double *const *c_in, double *const *c_out,
+                                            int ntracers, void *stream)
+{
+    return tracer_step_dm_impl("dlesm_tracer_step_hancock_dm", dlesm_tracer_step_hancock_f64, 2, p, rdt, ld, ny, xstart, xstop,
                                ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
                                ntracers, stream);
 }

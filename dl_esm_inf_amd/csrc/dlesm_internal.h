@@ -35,6 +35,9 @@ namespace dlesm {
 
 // true once a device has been bound (dlesm_init, or lazily on first device call)
 int ensure_device();
+// hipMallocAsync for a reduction's intermediate records (give them back with hipFreeAsync): stream-ordered as ever, from a
+// pool of the library's own on the bound device that keeps its freed blocks (dlesm_runtime.hip)
+hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s);
 hipStream_t side_stream();     // created by ensure_device()
 hipStream_t transfer_stream(); // for the non-blocking sync callbacks
 int tuning(const char *key, int fallback);

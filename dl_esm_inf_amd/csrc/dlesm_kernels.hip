@@ -2132,7 +2132,7 @@ extern "C" int dlesm_checksum_async_f64(const double *f, int ld, int ny, int xst
     if (int rc = check_box("dlesm_checksum_async_f64", ld, ny, xstart, xstop, ystart, ystop, 0)) return rc;
     const int nx = xstop - xstart + 1, nyb = ystop - ystart + 1;
     double *scratch = nullptr;
-    DLESM_HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)checksum_scratch_doubles(nx, nyb) * sizeof(double), s));
+    DLESM_HIP_TRY(scratch_alloc_async((void **)&scratch, (size_t)checksum_scratch_doubles(nx, nyb) * sizeof(double), s));
     const int rc = enqueue_checksum(f, ld, xstart - 1, ystart - 1, nx, nyb, scratch, result_dev, s);
     DLESM_HIP_TRY(hipFreeAsync(scratch, s));
     return rc;
@@ -2191,7 +2191,7 @@ extern "C" int dlesm_stencil5_resid_f64(const double *in, double *out, int ld, i
     int R = tuning("j5_tile_rows", 0);
     if (R < 1) R = vec2 ? 2 : 4;
     double *scratch = nullptr;
-    DLESM_HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)(np + resid_tree_doubles(np)) * sizeof(double), s));
+    DLESM_HIP_TRY(scratch_alloc_async((void **)&scratch, (size_t)(np + resid_tree_doubles(np)) * sizeof(double), s));
     if (norm == DLESM_NORM_MAX) {
         if (vec2) launch_tile<2, false, 1 + DLESM_NORM_MAX>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);
         else launch_tile<1, false, 1 + DLESM_NORM_MAX>(in, out, ld, x0, x1, y0, y1, R, 0, s, nullptr, nullptr, scratch);

@@ -97,6 +97,46 @@ __device__ __forceinline__ double tracer_point_muscl(const TracerFlow &f, double
     return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
 }
 
+// Time-centred (Hancock) limited tracer transport: the factor that replaces section 6.11's constant
+// 0.5 on each face, the same for every tracer.  w = tracer_weight of the cell, w_e .. w_s of its four neighbours; a face's
+// Courant number n is taken in the face's upwind cell, and g = 0.5 * (1 - n) for 0 <= n < 1, else 0.0 -- a NaN, an infinite
+// or a negative n fails the two comparisons, so g is always finite and what land holds in area_t, ht, sshn_t reaches no
+// written cell.
+struct TracerCourant {
+    double g1, g2, g3, g4;
+};
+__device__ __forceinline__ double tracer_weight(double rdt, double area, double ht, double st)
+{
+    return rdt / (area * (ht + st));
+}
+__device__ __forceinline__ double hancock_factor(double n)
+{
+    return (n >= 0.0 && n < 1.0) ? 0.5 * (1.0 - n) : 0.0;
+}
+__device__ __forceinline__ TracerCourant tracer_courant(const TracerFlow &f, double w, double w_e, double w_w, double w_n,
+                                                        double w_s)
+{
+    return TracerCourant{hancock_factor(fabs(f.r1) * (f.r1 >= 0.0 ? w : w_e)),
+                         hancock_factor(fabs(f.r2) * (f.r2 >= 0.0 ? w_w : w)),
+                         hancock_factor(fabs(f.r3) * (f.r3 >= 0.0 ? w : w_n)),
+                         hancock_factor(fabs(f.r4) * (f.r4 >= 0.0 ? w_s : w))};
+}
+// tracer_point_muscl with the face factors g1..g4 in the place of 0.5.  g = 0.0 gives tracer_point's face value.
+__device__ __forceinline__ double tracer_point_hancock(const TracerFlow &f, const TracerCourant &g, double c, double c_e,
+                                                       double c_w, double c_n, double c_s, double sx, double sx_e, double sx_w,
+                                                       double sy, double sy_n, double sy_s)
+{
+    const double ce = f.r1 >= 0.0 ? c + g.g1 * sx : c_e - g.g1 * sx_e;
+    const double cw = f.r2 >= 0.0 ? c_w + g.g2 * sx_w : c - g.g2 * sx;
+    const double cn = f.r3 >= 0.0 ? c + g.g3 * sy : c_n - g.g3 * sy_n;
+    const double cs = f.r4 >= 0.0 ? c_s + g.g4 * sy_s : c - g.g4 * sy;
+    const double F1 = f.e ? f.r1 * ce : 0.0;
+    const double F2 = f.w ? f.r2 * cw : 0.0;
+    const double F3 = f.n ? f.r3 * cn : 0.0;
+    const double F4 = f.s ? f.r4 * cs : 0.0;
+    return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
+}
+
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,
 // 1 = the one east (north) of it; ax = area_u (area_v) of the face
 __device__ __forceinline__ double ssh_point(long long t0, long long t1, double a0, double a1, double s0, double s1, double ax)

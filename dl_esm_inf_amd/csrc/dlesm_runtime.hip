@@ -59,7 +59,7 @@ static const struct { const char *key; int cls; } kKeys[] = {
     {"cont_nt", KEY_HOOK}, {"sw_smooth_ntl", KEY_HOOK},
     // ---- HOOK: fall-back kernels (unaligned bases, odd pitches, thin boxes) and the forms DLESM_DM_SAFE / a capture select
     {"j5_variant", KEY_HOOK}, {"sw_kernel", KEY_HOOK}, {"swk_kernel", KEY_HOOK}, {"s9_kernel", KEY_HOOK}, {"j5m_kernel", KEY_HOOK},
-    {"cont_kernel", KEY_HOOK}, {"mom_kernel", KEY_HOOK}, {"nemo_step_kernel", KEY_HOOK}, {"nemo_wet_form", KEY_HOOK}, {"tracer_kernel", KEY_HOOK}, {"tracer_muscl_kernel", KEY_HOOK}, {"sw_wrap_fused", KEY_HOOK}, {"sw_smooth_fused", KEY_HOOK},
+    {"cont_kernel", KEY_HOOK}, {"mom_kernel", KEY_HOOK}, {"nemo_step_kernel", KEY_HOOK}, {"nemo_wet_form", KEY_HOOK}, {"tracer_kernel", KEY_HOOK}, {"tracer_muscl_kernel", KEY_HOOK}, {"tracer_hancock_kernel", KEY_HOOK}, {"sw_wrap_fused", KEY_HOOK}, {"sw_smooth_fused", KEY_HOOK},
     {"sw_x2_fused", KEY_HOOK}, {"sw_x2_dm_overlap", KEY_HOOK},
     {"util_rowseg", KEY_HOOK}, {"util_rowlinear", KEY_HOOK}, {"util_gather_linear", KEY_HOOK},
     {"j5_dm_fused", KEY_HOOK}, {"sw_dm_fused", KEY_HOOK}, {"s9_dm_fused", KEY_HOOK}, {"j5_dm_chain", KEY_HOOK}, {"sw_dm_chain", KEY_HOOK},
@@ -96,6 +96,19 @@ static int tuning_nolock(const char *key, int fallback)
 // every later device entry point fails loudly (ensure_device) until the host program acknowledges it.
 static int *g_wait_timed_out = nullptr;
 
+// The pool the reductions' stream-ordered scratch comes from (scratch_alloc_async): the bound device's, and one that keeps
+// its freed blocks.  The device's default pool gives freed blocks back to the driver at every synchronisation, so in a
+// process that synchronises after each reduction every call works in memory fresh from the driver; results read back as
+// zeros now and then where a kernel had written (LAB_NOTES.md section 5.21).  A few records per call: kilobytes.
+static hipMemPool_t g_scratch_pool = nullptr;
+static int g_scratch_pool_device = -1;
+
+static void drop_scratch_pool()
+{
+    if (g_scratch_pool) (void)hipMemPoolDestroy(g_scratch_pool);   // (blocks still in use go when they are freed)
+    g_scratch_pool = nullptr, g_scratch_pool_device = -1;
+}
+
 static int bind_device(int device)
 {
     int n = 0;
@@ -118,6 +131,22 @@ static int bind_device(int device)
     if (!g_wait_timed_out) {
         DLESM_HIP_TRY(hipHostMalloc((void **)&g_wait_timed_out, sizeof(int), hipHostMallocMapped));
         *g_wait_timed_out = 0;
+    }
+    if (g_scratch_pool_device != device) {
+        drop_scratch_pool();
+        hipMemPoolProps props{};
+        props.allocType = hipMemAllocationTypePinned;
+        props.handleTypes = hipMemHandleTypeNone;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = device;
+        uint64_t keep = UINT64_MAX;
+        if (hipMemPoolCreate(&g_scratch_pool, &props) == hipSuccess &&
+            hipMemPoolSetAttribute(g_scratch_pool, hipMemPoolAttrReleaseThreshold, &keep) == hipSuccess) {
+            g_scratch_pool_device = device;
+        } else {                                         // no such pool here: the device's default one, as before
+            (void)hipGetLastError();
+            drop_scratch_pool();
+        }
     }
     g_device = device;
     g_ready = true;
@@ -143,6 +172,11 @@ int ensure_device()
         cur = 0;
     }
     return bind_device(cur);
+}
+
+hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s)
+{
+    return g_scratch_pool ? hipMallocFromPoolAsync(p, bytes, g_scratch_pool, s) : hipMallocAsync(p, bytes, s);
 }
 
 int *wait_timed_out_word() { return g_wait_timed_out; }
@@ -202,6 +236,7 @@ extern "C" int dlesm_finalize(void)
     // word is cleared so that a re-initialised library starts clean.
     if (g_wait_timed_out) *(volatile int *)g_wait_timed_out = 0;
     invalidate_concurrency_probe();
+    drop_scratch_pool();
     if (g_side) (void)hipStreamDestroy(g_side);
     if (g_xfer) (void)hipStreamDestroy(g_xfer);
     g_side = g_xfer = nullptr;

@@ -346,7 +346,7 @@ static int field_stats_run(const char *who, const double *const *fields, const i
     job.n = nfields, job.ld = ld;
 
     dlesm_field_stats *scratch = nullptr;
-    DLESM_HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)(total + above + nfields) * sizeof(dlesm_field_stats), s));
+    DLESM_HIP_TRY(scratch_alloc_async((void **)&scratch, (size_t)(total + above + nfields) * sizeof(dlesm_field_stats), s));
     if (!result_dev) result_dev = scratch + total + above;
     job.rec = scratch;
     if (total > 0) hipLaunchKernelGGL(field_stats_sweep, dim3((unsigned)total), dim3(256), 0, s, job);
@@ -417,7 +417,7 @@ extern "C" int dlesm_field_locate_f64(const double *f, const int *mask, int ld, 
     if (int rc = check_box("dlesm_field_locate_f64", ld, ny, xstart, xstop, ystart, ystop, 0)) return rc;
     const int nx = xstop - xstart + 1, nyb = ystop - ystart + 1;
     unsigned long long *best = nullptr, got = 0;
-    DLESM_HIP_TRY(hipMallocAsync((void **)&best, sizeof *best, s));
+    DLESM_HIP_TRY(scratch_alloc_async((void **)&best, sizeof *best, s));
     hipError_t err = hipMemsetAsync(best, 0xff, sizeof *best, s);
     if (err == hipSuccess) {
         hipLaunchKernelGGL(field_locate_k, dim3((unsigned)((nx + 255) / 256), (unsigned)(nyb < 4096 ? nyb : 4096)), dim3(256), 0, s,

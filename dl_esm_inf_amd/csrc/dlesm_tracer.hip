@@ -26,6 +26,14 @@
 // are loaded for c and for the mask.  A chunk or a row outside the array is loaded clamped and its mask forced to 0 by a
 // select, which zeroes every slope that would have read it.  tracer_muscl_direct<NT>: one cell per thread, HOOK key
 // tracer_muscl_kernel = 1.
+//
+// Time-centred limited transport (dlesm_tracer_step_hancock_f64): the two kernels above with a second
+// template parameter, <NT, true>; <NT, false> is section 6.11's sweep.  The constant 0.5 in front of a slope becomes a factor
+// per face, 0.5 * (1 - n) with n the face's Courant number in its upwind cell (tracer_courant / tracer_point_hancock,
+// dlesm_nemolite.h).  The factors depend on the flow only: every lane computes w = rdt / (area_t * (ht + sshn_t)) of its own
+// two columns on rows j-1, j, j+1 (six divisions and six more 16-byte loads a lane and tile, re-reads), takes w of columns
+// i-1 and i+1 from its neighbours by the DPP shifts of the flow stage -- the load-only lanes supply the tile's ends -- and
+// keeps g1..g4 of its two cells in registers for the unrolled tracer loop.  HOOK key tracer_hancock_kernel = 1.
 #include "dlesm_nemolite.h"
 
 namespace dlesm {
@@ -163,8 +171,9 @@ __device__ __forceinline__ MusclRows load_muscl_rows(const double *c, size_t oss
                      *(const d2 *)(c + onn)};
 }
 
-// (x0:x1, y0:y1) = the box (0-based); nxw tiles per row, lane 1 of tile 0 holds chunk c_first
-template <int NT>
+// (x0:x1, y0:y1) = the box (0-based); nxw tiles per row, lane 1 of tile 0 holds chunk c_first.  HANCOCK: section 6.12's
+// face factors in the place of 0.5; <NT, false> compiles to the code the kernel had before it had the parameter
+template <int NT, bool HANCOCK = false>
 __global__ __launch_bounds__(256) void tracer_muscl_tile(TracerArgs<NT> a, int ld, int ny, int x0, int x1, int y0, int y1,
                                                          int c_first, int nxw)
 {
@@ -190,6 +199,16 @@ __global__ __launch_bounds__(256) void tracer_muscl_tile(TracerArgs<NT> a, int l
     const bool in_ss = j >= 2, in_nn = j + 2 < ny;
     const size_t os = o - ld, on = o + ld, oss = (size_t)(in_ss ? j - 2 : 0) * ld + col,
                  onn = (size_t)(in_nn ? j + 2 : ny - 1) * ld + col;
+    // section 6.12: w of the lane's two columns on rows j-1 and j+1 (with row j's, six divisions a lane and tile, none per
+    // tracer), asked for in front of everything else: the six row pairs are then dead before the tracers' rows arrive, and
+    // every instantiation stays at four waves per SIMD (LAB_NOTES.md section 5.21)
+    d2 ws{}, wn{};
+    if constexpr (HANCOCK) {
+        const d2 ar_s = *(const d2 *)(f.area_t + os), ht_s = *(const d2 *)(f.ht + os), st_s = *(const d2 *)(f.sshn_t + os);
+        const d2 ar_n = *(const d2 *)(f.area_t + on), ht_n = *(const d2 *)(f.ht + on), st_n = *(const d2 *)(f.sshn_t + on);
+        ws = d2{tracer_weight(a.rdt, ar_s.x, ht_s.x, st_s.x), tracer_weight(a.rdt, ar_s.y, ht_s.y, st_s.y)};
+        wn = d2{tracer_weight(a.rdt, ar_n.x, ht_n.x, st_n.x), tracer_weight(a.rdt, ar_n.y, ht_n.y, st_n.y)};
+    }
     MusclRows cur = load_muscl_rows(a.c_in[0], oss, os, o, on, onn);     // the first tracer's loads go out with the flow's
 
     i2 ts = *(const i2 *)(f.tmask + os), tn = *(const i2 *)(f.tmask + on);
@@ -211,6 +230,16 @@ __global__ __launch_bounds__(256) void tracer_muscl_tile(TracerArgs<NT> a, int l
                                       ar.x, ht.x, st.x, sa.x, t.y, tw, tn.x, ts.x);
     const TracerFlow f1 = tracer_flow(a.rdt, su.y, su.x, sv.y, sv_s.y, hu.y, hu.x, hv.y, hv_s.y, un.y, un.x, vn.y, vn_s.y,
                                       ar.y, ht.y, st.y, sa.y, te, t.x, tn.y, ts.y);
+    // section 6.12: w of the lane's own row; w of columns i-1 and i+1 from the neighbouring lanes, the load-only lanes
+    // supplying the tile's ends.  A clamped chunk's w belongs to another cell: it reaches only the factor of a face whose flux
+    // the forced mask switches off.
+    TracerCourant g0{}, g1{};
+    if constexpr (HANCOCK) {
+        const double w0 = tracer_weight(a.rdt, ar.x, ht.x, st.x), w1 = tracer_weight(a.rdt, ar.y, ht.y, st.y);
+        const double w_w = from_lower<true>(w1), w_e = from_upper<true>(w0);
+        g0 = tracer_courant(f0, w0, w1, w_w, wn.x, ws.x);
+        g1 = tracer_courant(f1, w1, w_e, w0, wn.y, ws.y);
+    }
     // where a slope is taken: a wet cell between two cells that are not land.  x: the lane's two columns (lane 0's west
     // column and lane 63's east column get none, and nothing asks for them); y: rows j-1, j, j+1 of both columns
     const bool x_0 = t.x > 0 && tw != 0 && t.y != 0, x_1 = t.y > 0 && t.x != 0 && te != 0;
@@ -226,21 +255,33 @@ __global__ __launch_bounds__(256) void tracer_muscl_tile(TracerArgs<NT> a, int l
         const double c_w = from_lower<true>(cur.m.y), c_e = from_upper<true>(cur.m.x);
         const double sx0 = muscl_slope(x_0, c_w, cur.m.x, cur.m.y), sx1 = muscl_slope(x_1, cur.m.x, cur.m.y, c_e);
         const double sx_w = from_lower<true>(sx1), sx_e = from_upper<true>(sx0);
-        const double o0 = tracer_point_muscl(f0, cur.m.x, cur.m.y, c_w, cur.n.x, cur.s.x, sx0, sx1, sx_w,
-                                             muscl_slope(ym_0, cur.s.x, cur.m.x, cur.n.x),
-                                             muscl_slope(yn_0, cur.m.x, cur.n.x, cur.nn.x),
-                                             muscl_slope(ys_0, cur.ss.x, cur.s.x, cur.m.x));
-        const double o1 = tracer_point_muscl(f1, cur.m.y, c_e, cur.m.x, cur.n.y, cur.s.y, sx1, sx_e, sx0,
-                                             muscl_slope(ym_1, cur.s.y, cur.m.y, cur.n.y),
-                                             muscl_slope(yn_1, cur.m.y, cur.n.y, cur.nn.y),
-                                             muscl_slope(ys_1, cur.ss.y, cur.s.y, cur.m.y));
+        double o0, o1;
+        if constexpr (HANCOCK) {
+            o0 = tracer_point_hancock(f0, g0, cur.m.x, cur.m.y, c_w, cur.n.x, cur.s.x, sx0, sx1, sx_w,
+                                      muscl_slope(ym_0, cur.s.x, cur.m.x, cur.n.x),
+                                      muscl_slope(yn_0, cur.m.x, cur.n.x, cur.nn.x),
+                                      muscl_slope(ys_0, cur.ss.x, cur.s.x, cur.m.x));
+            o1 = tracer_point_hancock(f1, g1, cur.m.y, c_e, cur.m.x, cur.n.y, cur.s.y, sx1, sx_e, sx0,
+                                      muscl_slope(ym_1, cur.s.y, cur.m.y, cur.n.y),
+                                      muscl_slope(yn_1, cur.m.y, cur.n.y, cur.nn.y),
+                                      muscl_slope(ys_1, cur.ss.y, cur.s.y, cur.m.y));
+        } else {
+            o0 = tracer_point_muscl(f0, cur.m.x, cur.m.y, c_w, cur.n.x, cur.s.x, sx0, sx1, sx_w,
+                                    muscl_slope(ym_0, cur.s.x, cur.m.x, cur.n.x),
+                                    muscl_slope(yn_0, cur.m.x, cur.n.x, cur.nn.x),
+                                    muscl_slope(ys_0, cur.ss.x, cur.s.x, cur.m.x));
+            o1 = tracer_point_muscl(f1, cur.m.y, c_e, cur.m.x, cur.n.y, cur.s.y, sx1, sx_e, sx0,
+                                    muscl_slope(ym_1, cur.s.y, cur.m.y, cur.n.y),
+                                    muscl_slope(yn_1, cur.m.y, cur.n.y, cur.nn.y),
+                                    muscl_slope(ys_1, cur.ss.y, cur.s.y, cur.m.y));
+        }
         store_pair(a.c_out[k] + oc, o0, o1, wet0, wet1);
         cur = nxt;
     }
 }
 
-// one cell per thread: odd leading dimensions, unaligned bases, the HOOK key tracer_muscl_kernel
-template <int NT>
+// one cell per thread: odd leading dimensions, unaligned bases, the HOOK keys tracer_muscl_kernel / tracer_hancock_kernel
+template <int NT, bool HANCOCK = false>
 __global__ __launch_bounds__(256) void tracer_muscl_direct(TracerArgs<NT> a, int ld, int ny, int x0, int x1, int y0, int y1)
 {
     const TracerFields &f = a.f;
@@ -265,20 +306,34 @@ __global__ __launch_bounds__(256) void tracer_muscl_direct(TracerArgs<NT> a, int
         const bool x_m = t_e != 0 && t_w != 0, y_m = t_n != 0 && t_s != 0;           // (t > 0 here)
         const bool x_e = t_e > 0 && t_ee != 0, x_w = t_w > 0 && t_ww != 0;            // (t != 0 here)
         const bool y_n = t_n > 0 && t_nn != 0, y_s = t_s > 0 && t_ss != 0;
+        TracerCourant g{};
+        if constexpr (HANCOCK) {
+            auto W = [&](size_t p) { return tracer_weight(a.rdt, f.area_t[p], f.ht[p], f.sshn_t[p]); };
+            g = tracer_courant(fl, W(o), W(o + 1), W(o - 1), W(o + ld), W(o - ld));
+        }
 #pragma unroll
         for (int k = 0; k < NT; k++) {
             const double *c = a.c_in[k];
             const double cm = c[o], ce = c[o + 1], cw = c[o - 1], cn = c[o + ld], cs = c[o - ld];
-            a.c_out[k][o] = tracer_point_muscl(fl, cm, ce, cw, cn, cs, muscl_slope(x_m, cw, cm, ce),
-                                               muscl_slope(x_e, cm, ce, c[oee]), muscl_slope(x_w, c[oww], cw, cm),
-                                               muscl_slope(y_m, cs, cm, cn), muscl_slope(y_n, cm, cn, c[onn]),
-                                               muscl_slope(y_s, c[oss], cs, cm));
+            if constexpr (HANCOCK)
+                a.c_out[k][o] = tracer_point_hancock(fl, g, cm, ce, cw, cn, cs, muscl_slope(x_m, cw, cm, ce),
+                                                     muscl_slope(x_e, cm, ce, c[oee]), muscl_slope(x_w, c[oww], cw, cm),
+                                                     muscl_slope(y_m, cs, cm, cn), muscl_slope(y_n, cm, cn, c[onn]),
+                                                     muscl_slope(y_s, c[oss], cs, cm));
+            else
+                a.c_out[k][o] = tracer_point_muscl(fl, cm, ce, cw, cn, cs, muscl_slope(x_m, cw, cm, ce),
+                                                   muscl_slope(x_e, cm, ce, c[oee]), muscl_slope(x_w, c[oww], cw, cm),
+                                                   muscl_slope(y_m, cs, cm, cn), muscl_slope(y_n, cm, cn, c[onn]),
+                                                   muscl_slope(y_s, c[oss], cs, cm));
         }
     }
 }
 
+enum Scheme { SCHEME_UPWIND = 0, SCHEME_MUSCL = 1, SCHEME_HANCOCK = 2 };    // sections 6.10, 6.11, 6.12
+
 struct Launch {
-    bool tile, muscl;
+    bool tile;
+    Scheme scheme;
     int ld, ny, x0, x1, y0, y1, c_first, nxw, tpb;
     hipStream_t st;
 };
@@ -290,14 +345,16 @@ void launch(const Launch &l, double rdt, const TracerFields &f, const double *co
     a.f = f, a.rdt = rdt;
     for (int k = 0; k < NT; k++) a.c_in[k] = c_in[k], a.c_out[k] = c_out[k];
     const int h = l.y1 - l.y0 + 1;
-    if (l.muscl) {
+    if (l.scheme != SCHEME_UPWIND) {
         if (l.tile) {
             const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
-            hipLaunchKernelGGL(tracer_muscl_tile<NT>, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1,
-                               l.c_first, l.nxw);
+            const auto tile = l.scheme == SCHEME_HANCOCK ? tracer_muscl_tile<NT, true> : tracer_muscl_tile<NT, false>;
+            hipLaunchKernelGGL(tile, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1, l.c_first,
+                               l.nxw);
         } else {
-            hipLaunchKernelGGL(tracer_muscl_direct<NT>, dim3((l.x1 - l.x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, l.st,
-                               a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1);
+            const auto direct = l.scheme == SCHEME_HANCOCK ? tracer_muscl_direct<NT, true> : tracer_muscl_direct<NT, false>;
+            hipLaunchKernelGGL(direct, dim3((l.x1 - l.x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, l.st, a, l.ld, l.ny,
+                               l.x0, l.x1, l.y0, l.y1);
         }
     } else if (l.tile) {
         const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
@@ -344,8 +401,8 @@ using namespace dlesm;
 
 namespace {
 
-// the body of both single-domain entries: the refusals, the path, at most NT_MAX tracers per launch
-int tracer_step(const char *who, bool muscl, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+// the body of the three single-domain entries: the refusals, the path, at most NT_MAX tracers per launch
+int tracer_step(const char *who, Scheme scheme, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
                 const TracerFields &f, const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
     if (int rc = ensure_device()) return rc;
@@ -358,12 +415,13 @@ int tracer_step(const char *who, bool muscl, double rdt, int ld, int ny, int xst
     for (int k = 0; k < ntracers; k++) aligned = aligned && (uintptr_t)c_in[k] % 16 == 0 && (uintptr_t)c_out[k] % 16 == 0;
 
     Launch l{};
-    l.muscl = muscl;
-    l.tile = aligned && (muscl ? tuning("tracer_muscl_kernel", 0) : tuning("tracer_kernel", 0)) == 0;
+    static const char *const hook[3] = {"tracer_kernel", "tracer_muscl_kernel", "tracer_hancock_kernel"};
+    l.scheme = scheme;
+    l.tile = aligned && tuning(hook[scheme], 0) == 0;
     l.ld = ld, l.ny = ny, l.x0 = xstart - 1, l.x1 = xstop - 1, l.y0 = ystart - 1, l.y1 = ystop - 1;
     l.st = (hipStream_t)stream;
     if (l.tile) {
-        const int chunks = muscl ? MUSCL_CHUNKS : TILE_CHUNKS;
+        const int chunks = scheme != SCHEME_UPWIND ? MUSCL_CHUNKS : TILE_CHUNKS;
         l.c_first = (l.x0 / 2) & ~7;                     // tiles anchored on a 128-byte line of the row
         l.nxw = (l.x1 / 2 - l.c_first + chunks) / chunks, l.tpb = 4;
         choose_block_shape(&l.nxw, &l.tpb, 4);
@@ -391,8 +449,8 @@ extern "C" int dlesm_tracer_step_f64(double rdt, int ld, int ny, int xstart, int
                                      const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
     const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
-    return tracer_step("dlesm_tracer_step_f64", false, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers,
-                       stream);
+    return tracer_step("dlesm_tracer_step_f64", SCHEME_UPWIND, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out,
+                       ntracers, stream);
 }
 
 extern "C" int dlesm_tracer_step_muscl_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
@@ -402,6 +460,17 @@ extern "C" int dlesm_tracer_step_muscl_f64(double rdt, int ld, int ny, int xstar
                                            const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
     const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
-    return tracer_step("dlesm_tracer_step_muscl_f64", true, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers,
-                       stream);
+    return tracer_step("dlesm_tracer_step_muscl_f64", SCHEME_MUSCL, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out,
+                       ntracers, stream);
+}
+
+extern "C" int dlesm_tracer_step_hancock_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                             const int *tmask, const double *area_t, const double *un, const double *vn,
+                                             const double *hu, const double *hv, const double *ht, const double *sshn_t,
+                                             const double *sshn_u, const double *sshn_v, const double *ssha,
+                                             const double *const *c_in, double *const *c_out, int ntracers, void *stream)
+{
+    const TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
+    return tracer_step("dlesm_tracer_step_hancock_f64", SCHEME_HANCOCK, rdt, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out,
+                       ntracers, stream);
 }

@@ -850,6 +850,30 @@ module dlesm_hip_mod
        type(c_ptr), value :: stream
        integer(c_int) :: rc
      end function
+     ! ---- time-centred limited tracer transport (DESIGN.md section 6.12): the same argument lists
+     function dlesm_tracer_step_hancock_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, &
+          sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream) bind(C, name="dlesm_tracer_step_hancock_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha
+       type(c_ptr), intent(in) :: c_in(*), c_out(*)
+       integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_tracer_step_hancock_dm(plan, rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, &
+          sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream) bind(C, name="dlesm_tracer_step_hancock_dm") result(rc)
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: plan
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha
+       type(c_ptr), intent(in) :: c_in(*), c_out(*)
+       integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
      function dlesm_shallow_step_x2_dm(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, &
           unew, vnew, pnew, unew2, vnew2, pnew2, stream) bind(C, name="dlesm_shallow_step_x2_dm") result(rc)
        import :: c_int, c_ptr, c_sw_params

@@ -56,6 +56,7 @@ module dlesm_psy_mod
   public :: open_boundary, tide_ssh, invoke_bc_ssh, invoke_bc_flather_u, invoke_bc_flather_v, invoke_bc_open
   public :: invoke_nemolite_step, invoke_nemolite_step_dm, wet_plan
   public :: invoke_tracer_step, invoke_tracer_step_dm, invoke_tracer_step_muscl, invoke_tracer_step_muscl_dm
+  public :: invoke_tracer_step_hancock, invoke_tracer_step_hancock_dm
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -549,7 +550,7 @@ contains
     if (ssha%grid%decomp%ndomains > 1) &
          call gocean_stop('invoke_tracer_step: the grid is decomposed: the new tracers need a halo exchange; use ' // &
                           'invoke_tracer_step_dm')
-    call tracer_step_call('invoke_tracer_step', c_null_ptr, .false., .false., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, &
+    call tracer_step_call('invoke_tracer_step', c_null_ptr, .false., 0, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, &
                           sshn_u, sshn_v)
   end subroutine invoke_tracer_step
 
@@ -571,7 +572,7 @@ contains
     else
        plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
     end if
-    call tracer_step_call('invoke_tracer_step_dm', plan, .true., .false., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, &
+    call tracer_step_call('invoke_tracer_step_dm', plan, .true., 0, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, &
                           sshn_v)
   end subroutine invoke_tracer_step_dm
 
@@ -585,7 +586,7 @@ contains
     if (ssha%grid%decomp%ndomains > 1) &
          call gocean_stop('invoke_tracer_step_muscl: the grid is decomposed: the new tracers need a halo exchange; use ' // &
                           'invoke_tracer_step_muscl_dm')
-    call tracer_step_call('invoke_tracer_step_muscl', c_null_ptr, .false., .true., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
+    call tracer_step_call('invoke_tracer_step_muscl', c_null_ptr, .false., 1, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
                           sshn_t, sshn_u, sshn_v)
   end subroutine invoke_tracer_step_muscl
 
@@ -607,15 +608,53 @@ contains
     else
        plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
     end if
-    call tracer_step_call('invoke_tracer_step_muscl_dm', plan, .true., .true., rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
+    call tracer_step_call('invoke_tracer_step_muscl_dm', plan, .true., 1, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
                           sshn_t, sshn_u, sshn_v)
   end subroutine invoke_tracer_step_muscl_dm
 
-  ! the call the four tracer wrappers make (dm: the distributed entry with `plan`; muscl: the limited scheme's entries)
-  subroutine tracer_step_call(who, plan, dm, muscl, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+  !> invoke_tracer_step_muscl with time-centred face values (dlesm_tracer_step_hancock_f64, DESIGN.md section 6.12): the slope's
+  !! factor 0.5 becomes 0.5 * (1 - n), n the face's Courant number in its upwind cell, 0 where n is not in [0, 1).  Same
+  !! arguments and rules.  Single domain: stops on a decomposed grid (use invoke_tracer_step_hancock_dm).
+  subroutine invoke_tracer_step_hancock(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    if (ssha%grid%decomp%ndomains > 1) &
+         call gocean_stop('invoke_tracer_step_hancock: the grid is decomposed: the new tracers need a halo exchange; use ' // &
+                          'invoke_tracer_step_hancock_dm')
+    call tracer_step_call('invoke_tracer_step_hancock', c_null_ptr, .false., 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
+                          sshn_t, sshn_u, sshn_v)
+  end subroutine invoke_tracer_step_hancock
+
+  !> invoke_tracer_step_hancock and ONE depth-2 exchange of the new tracers on a decomposed grid (dlesm_tracer_step_hancock_dm,
+  !! DESIGN.md section 6.12).  The grid's mask and c_in need valid depth-2 halos, the flow fields depth-1 halos; c_out leaves
+  !! with depth-2 halos.  Collective.  The grid must have been decomposed with halo_width = 2 (without distributed memory the
+  !! plan has no messages: invoke_tracer_step_hancock, bit for bit).
+  subroutine invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    type(c_ptr) :: plan
+    if (ssha%grid%subdomain%internal%xstart - 1 /= 2 .or. ssha%grid%subdomain%internal%ystart - 1 /= 2) &
+         call gocean_stop('invoke_tracer_step_hancock_dm: the grid must be decomposed with halo_width = 2')
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(ssha%grid%nx, ssha%grid%ny)
+    else
+       plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
+    end if
+    call tracer_step_call('invoke_tracer_step_hancock_dm', plan, .true., 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
+                          sshn_t, sshn_u, sshn_v)
+  end subroutine invoke_tracer_step_hancock_dm
+
+  ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
+  ! scheme's, 2 the time-centred limited scheme's)
+  subroutine tracer_step_call(who, plan, dm, scheme, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v)
     character(len=*), intent(in) :: who
     type(c_ptr), intent(in) :: plan
-    logical, intent(in) :: dm, muscl
+    logical, intent(in) :: dm
+    integer, intent(in) :: scheme
     real(go_wp), intent(in) :: rdt
     type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
     type(r2d_field), intent(inout), target :: ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
@@ -633,7 +672,15 @@ contains
        pin(k) = field_device_data(c_in(k));  pout(k) = field_device_data(c_out(k))
     end do
     call grid_to_device(ssha%grid)
-    if (dm .and. muscl) then
+    if (dm .and. scheme == 2) then
+       rc = dlesm_tracer_step_hancock_dm(plan, real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
+                                         int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
+                                         int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &
+                                         ssha%grid%tmask_device, ssha%grid%area_t_device, field_device_data(un), &
+                                         field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
+                                         field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                         field_device_data(ssha), pin, pout, int(n, c_int), c_null_ptr)
+    else if (dm .and. scheme == 1) then
        rc = dlesm_tracer_step_muscl_dm(plan, real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
                                        int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
                                        int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &
@@ -649,7 +696,15 @@ contains
                                  field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
                                  field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
                                  field_device_data(ssha), pin, pout, int(n, c_int), c_null_ptr)
-    else if (muscl) then
+    else if (scheme == 2) then
+       rc = dlesm_tracer_step_hancock_f64(real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
+                                          int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
+                                          int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &
+                                          ssha%grid%tmask_device, ssha%grid%area_t_device, field_device_data(un), &
+                                          field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
+                                          field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), &
+                                          field_device_data(ssha), pin, pout, int(n, c_int), c_null_ptr)
+    else if (scheme == 1) then
        rc = dlesm_tracer_step_muscl_f64(real(rdt, c_double), int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), &
                                         int(ssha%internal%xstart, c_int), int(ssha%internal%xstop, c_int), &
                                         int(ssha%internal%ystart, c_int), int(ssha%internal%ystop, c_int), &

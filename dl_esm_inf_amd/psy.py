@@ -348,6 +348,38 @@ def invoke_tracer_step_muscl_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn
                                                                                        sshn_u, sshn_v, stream)))
 
 
+def invoke_tracer_step_hancock(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """invoke_tracer_step_muscl with time-centred face values (dlesm_tracer_step_hancock_f64): the
+    slope's factor 0.5 becomes 0.5 * (1 - n), n the face's Courant number in its upwind cell, 0 where n is not in [0, 1).
+    Same arguments and rules.  Single domain: stops on a decomposed grid."""
+    g = ssha.grid
+    if g.decomp is not None and g.decomp.ndomains > 1:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_hancock: the grid is decomposed (%d subdomains): the new "
+                                             "tracers need a halo exchange; use invoke_tracer_step_hancock_dm"
+                               % g.decomp.ndomains)
+    check(_cabi.lib().dlesm_tracer_step_hancock_f64(*_tracer_args("invoke_tracer_step_hancock", rdt, c_out, c_in, ssha, un, vn,
+                                                                  ht, hu, hv, sshn_t, sshn_u, sshn_v, stream)))
+
+
+def invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
+    """invoke_tracer_step_hancock and ONE depth-2 exchange of the new tracers on a decomposed grid
+    (dlesm_tracer_step_hancock_dm), bit for bit invoke_tracer_step_hancock ->
+    halo_exchange_multi(c_out).  The grid's mask and c_in need valid depth-2 halos, the flow fields depth-1 halos (area_t, ht
+    and sshn_t among them: w of the cell beyond the box is built from them); c_out leaves with depth-2 halos.  Collective.
+    Stops on a grid with halo_width other than 2."""
+    g = ssha.grid
+    hw = getattr(g, "halo_width", 1)
+    if hw != 2:
+        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_hancock_dm: the grid has halo_width %d; the step reads two "
+                                             "cells and exchanges depth-2 halos: decompose the grid with halo_width = 2" % hw)
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_hancock_dm: the grid has no message tables (grid_init after "
+                                             "decompose)")
+    check(_cabi.lib().dlesm_tracer_step_hancock_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_hancock_dm", rdt,
+                                                                                         c_out, c_in, ssha, un, vn, ht, hu, hv,
+                                                                                         sshn_t, sshn_u, sshn_v, stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

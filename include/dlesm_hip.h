@@ -1042,6 +1042,35 @@ int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *plan, double rdt, int ld, int ny
                                const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
                                const double *const *c_in, double *const *c_out, int ntracers, void *stream);
 
+/* Time-centred (Hancock) limited tracer transport: dlesm_tracer_step_muscl_f64 with the constant 0.5
+ * in front of a slope replaced, face by face, by half of one minus the face's Courant number, taken in the face's upwind cell:
+ *     w(i,j) = rdt / (area_t(i,j) * (ht(i,j) + sshn_t(i,j)))
+ *     n1 = |r1| * (r1 >= 0 ? w(i,j)   : w(i+1,j))      n2 = |r2| * (r2 >= 0 ? w(i-1,j) : w(i,j))
+ *     n3 = |r3| * (r3 >= 0 ? w(i,j)   : w(i,j+1))      n4 = |r4| * (r4 >= 0 ? w(i,j-1) : w(i,j))
+ *     gk = (nk >= 0 && nk < 1) ? 0.5 * (1 - nk) : 0                                                          k = 1..4
+ *     ce = r1 >= 0 ? c(i,j)   + g1*sx(i,j)   : c(i+1,j) - g1*sx(i+1,j)      cw = r2 >= 0 ? c(i-1,j) + g2*sx(i-1,j) : c(i,j) - g2*sx(i,j)
+ *     cn = r3 >= 0 ? c(i,j)   + g3*sy(i,j)   : c(i,j+1) - g3*sy(i,j+1)      cs = r4 >= 0 ? c(i,j-1) + g4*sy(i,j-1) : c(i,j) - g4*sy(i,j)
+ * with sx, sy, F1..F4 and c_out as above.  g is always finite: a NaN, an infinite or a negative n fails the two comparisons and
+ * gives 0, so what land holds in area_t, ht and sshn_t never reaches a written cell, a face with n >= 1 carries the upwind
+ * value, and coasts, open cells and a constant nonzero tracer keep dlesm_tracer_step_f64's bits.  A face carries one flux: the
+ * upwind cell is the same from both sides.  w is read in the four neighbours, inside the box's ring: nothing is read further
+ * out than by dlesm_tracer_step_muscl_f64.  Arguments, aliasing rules, refusals and the asynchronous contract are those of
+ * dlesm_tracer_step_f64; the HOOK key tracer_hancock_kernel = 1 forces the general path.  In one dimension a profile's range is
+ * kept while n <= 1/2. */
+int dlesm_tracer_step_hancock_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                  const int *tmask, const double *area_t, const double *un, const double *vn,
+                                  const double *hu, const double *hv, const double *ht,
+                                  const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                                  const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+/* The distributed form: bit for bit in every cell, dlesm_tracer_step_hancock_f64 followed by dlesm_halo_exchange_multi_f64(plan,
+ * c_out, ntracers, DLESM_DIRS_ALL).  Halos, the depth-2 plan, refusals, guards, mailbox turns and the collective contract are
+ * dlesm_tracer_step_muscl_dm's; w of the cell beyond the box comes from the depth-1 halos of area_t, ht and sshn_t. */
+int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *plan, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                 const int *tmask, const double *area_t, const double *un, const double *vn,
+                                 const double *hu, const double *hv, const double *ht,
+                                 const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
+                                 const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);

@@ -9,6 +9,10 @@ The second-order limited entry (dlesm_tracer_step_muscl_f64, DESIGN.md section 6
 one call with K tracers: its compulsory bytes are the same 84 + 16 K B/cell (rows j-2 and j+2 are re-reads), so it is given
 under the same byte model and as a ratio to the same-run upwind call.  Those rows go to profiles/r13_tracer_muscl.json
 (TRACER_PROBE_MUSCL_OUT names another file).
+The time-centred limited entry (dlesm_tracer_step_hancock_f64) is timed in the same windows too, under
+the same byte model (its six extra rows of area_t, ht, sshn_t are re-reads) and as a ratio to the same-run limited call, whose
+code it shares but for the face factors.  Those rows, with the same run's upwind and limited times beside them, go to
+profiles/r14_tracer_hancock.json (TRACER_PROBE_HANCOCK_OUT names another file).
     python scripts/tracer_probe.py [OUT.json] [WINDOWS] [N ...]"""
 import ctypes as C
 import json
@@ -24,6 +28,7 @@ import dl_esm_inf_amd as D  # noqa: E402
 
 out_path = sys.argv[1] if len(sys.argv) > 1 else "profiles/r10_tracer.json"
 muscl_path = os.environ.get("TRACER_PROBE_MUSCL_OUT", "profiles/r13_tracer_muscl.json")
+hancock_path = os.environ.get("TRACER_PROBE_HANCOCK_OUT", "profiles/r14_tracer_hancock.json")
 windows = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 sizes = [int(a) for a in sys.argv[3:]] or [4096, 8192]
 KS = (1, 2, 4, 8)
@@ -41,6 +46,11 @@ muscl_result = {"what": "ms per K tracers, medians of the same interleaved windo
                         "call with K tracers, upwind = one dlesm_tracer_step_f64 call with K tracers; GB/s under the same "
                         "byte model (rows j-2 and j+2 are re-reads); muscl_over_upwind = the ratio of the two times",
                 "windows": windows, "device": result["device"], "sizes": {}}
+hancock_result = {"what": "ms per K tracers, medians of the same interleaved windows: hancock = one "
+                          "dlesm_tracer_step_hancock_f64 call with K tracers, muscl = one dlesm_tracer_step_muscl_f64 call, "
+                          "upwind = one dlesm_tracer_step_f64 call; GB/s under the same byte model (the rows j-1 and j+1 of "
+                          "area_t, ht, sshn_t are re-reads); hancock_over_muscl, muscl_over_upwind = ratios of the times",
+                  "windows": windows, "device": result["device"], "sizes": {}}
 
 
 def model_bytes(k, launches):
@@ -79,6 +89,9 @@ for n in sizes:
     def muscl(k):
         return lambda: D.psy.invoke_tracer_step_muscl(20.0, Co[:k], Ci[:k], *flow, stream=s)
 
+    def hancock(k):
+        return lambda: D.psy.invoke_tracer_step_hancock(20.0, Co[:k], Ci[:k], *flow, stream=s)
+
     def split(k):
         def fn():
             for m in range(k):
@@ -90,6 +103,7 @@ for n in sizes:
         variants["one_%d" % k] = one(k)
         variants["split_%d" % k] = split(k)
         variants["muscl_%d" % k] = muscl(k)
+        variants["hancock_%d" % k] = hancock(k)
     launches = 10
     times = {k: [] for k in variants}
     torch.cuda.synchronize()
@@ -131,6 +145,18 @@ for n in sizes:
                            "muscl_over_upwind": tm_ / tu})
         print("| %d | %.4f | %.0f (%d) | %.4f | %.3f |" % (k, tm_, b1 * cells / tm_ / 1e6, b1, tu, tm_ / tu), flush=True)
     muscl_result["sizes"][str(n)] = rm
+    rh = {"extents": [g.nx, g.ny], "cells": cells, "copy_gbs": copy_gbs, "rows": [],
+          "ms_all_windows": {k: v for k, v in times.items() if k.split("_")[0] in ("hancock", "muscl", "one")}}
+    print("| K | time-centred, ms | GB/s (model B/cell) | limited, ms | upwind, ms | time-centred / limited | limited / upwind |")
+    print("|---|---|---|---|---|---|---|")
+    for k in KS:
+        b1 = model_bytes(k, 1 if k <= 4 else 2)
+        th, tm_, tu = med["hancock_%d" % k], med["muscl_%d" % k], med["one_%d" % k]
+        rh["rows"].append({"k": k, "hancock_ms": th, "model_bytes": b1, "hancock_gbs": b1 * cells / th / 1e6, "muscl_ms": tm_,
+                           "upwind_ms": tu, "hancock_over_muscl": th / tm_, "muscl_over_upwind": tm_ / tu})
+        print("| %d | %.4f | %.0f (%d) | %.4f | %.4f | %.3f | %.3f |" % (k, th, b1 * cells / th / 1e6, b1, tm_, tu, th / tm_,
+                                                                        tm_ / tu), flush=True)
+    hancock_result["sizes"][str(n)] = rh
     del F, Ci, Co, flow, g, variants
     torch.cuda.empty_cache()
 
@@ -142,3 +168,7 @@ os.makedirs(os.path.dirname(muscl_path) or ".", exist_ok=True)
 with open(muscl_path, "w") as f:
     json.dump(muscl_result, f, indent=1)
 print("wrote", muscl_path)
+os.makedirs(os.path.dirname(hancock_path) or ".", exist_ok=True)
+with open(hancock_path, "w") as f:
+    json.dump(hancock_result, f, indent=1)
+print("wrote", hancock_path)
