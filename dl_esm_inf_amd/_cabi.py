@@ -19,6 +19,7 @@ DIRS_ALL, DIRS_NO_DIAGONALS = 0xF, 0x10
 NORM_MAX, NORM_SUMSQ = 0, 1           # dlesm_stencil5_resid_f64
 STATS_MAX_FIELDS = 8                  # dlesm_field_stats_async_f64
 TRACER_MAX = 8                        # DLESM_TRACER_MAX (dlesm_tracer_step_f64)
+TRACER_UPWIND, TRACER_MUSCL, TRACER_HANCOCK = 0, 1, 2   # scheme of dlesm_nemolite_coupled_step_dm
 LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
 
@@ -258,6 +259,10 @@ PROTOTYPES = {
     "dlesm_tracer_step_muscl_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_hancock_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_hancock_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
+                                            C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
+                                       [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_halo_exchange_i32": (_i, [_vp, _vp, _vp]),
     "dlesm_shallow_step_smooth_dm_pipelined": (_i, [_vp, C.POINTER(SwParams), _d, _i, _i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dlesm_global_sum_f64": (_i, [C.POINTER(_d)]),
     "dlesm_global_max_f64": (_i, [C.POINTER(_d)]),

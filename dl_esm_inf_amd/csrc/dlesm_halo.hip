@@ -163,6 +163,8 @@ struct dlesm_halo_plan {
     // the previous one is ordered behind it (peer_order)
     bool peer_used = false;
     hipStream_t peer_last_stream = nullptr;
+    // dlesm_halo_exchange_i32: ld x ny doubles the int field travels in, allocated on first use
+    double *i32_scratch = nullptr;
 };
 
 // edge directions follow their bit; diagonals follow their two edges (parallel_comms_mod.f90:
@@ -505,6 +507,7 @@ extern "C" int dlesm_halo_plan_destroy(dlesm_halo_plan *p)
     if (p->sendbuf) (void)hipFree(p->sendbuf);
     if (p->recvbuf) (void)hipFree(p->recvbuf);
     if (p->frame_flag) (void)hipFree(p->frame_flag);
+    if (p->i32_scratch) (void)hipFree(p->i32_scratch);
     for (void *m : p->peer_mapped) (void)hipIpcCloseMemHandle(m);
     if (p->peer_box) (void)hipFree(p->peer_box);
     if (p->peer_counter) (void)hipFree(p->peer_counter);
@@ -2049,6 +2052,198 @@ extern "C" int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *p, double rdt, int 
     return tracer_step_dm_impl("dlesm_tracer_step_hancock_dm", dlesm_tracer_step_hancock_f64, 2, p, rdt, ld, ny, xstart, xstop,
                                ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
                                ntracers, stream);
+}
+
+// One coupled NEMOLite2D-class time step on a decomposed grid (dlesm_nemolite_coupled_step_dm): the
+// flow step of section 6.8 and the tracer sweep of section 6.10, 6.11 or 6.12 on ONE plan of depth 1 or 2, then ONE exchange
+// of the five flow outputs and the new tracers.  The tracer update reads ssha in its own wet cell only and everything else at
+// level n, so it needs nothing from an exchange of the step's outputs: the sweep runs before the exchange, which then carries
+// 5 + ntracers fields.  No new sweep: nemolite_ssha_ring, dlesm_nemolite_step_wet_f64 and the tracer entry as they are.
+extern "C" int dlesm_nemolite_coupled_step_dm(dlesm_halo_plan *p, const dlesm_wet_plan *wet, int scheme,
+                                              const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                              const double *area_t, int ld, int ny, const dlesm_region *tbox,
+                                              const dlesm_region *ubox, const dlesm_region *vbox, const dlesm_obc *obc,
+                                              double ssh_bc, const double *un, const double *vn, const double *ht,
+                                              const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                                              const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua,
+                                              double *va, const double *const *c_in, double *const *c_out, int ntracers,
+                                              void *stream)
+{
+    static const char *const who = "dlesm_nemolite_coupled_step_dm";
+    static const tracer_entry entries[3] = {dlesm_tracer_step_f64, dlesm_tracer_step_muscl_f64, dlesm_tracer_step_hancock_f64};
+    clear_error();
+    DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
+    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
+    if (int rc = ensure_device()) return rc;
+    if (int rc = nemo::step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t,
+                                  sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va))
+        return rc;
+    if (int rc = nemo::wet_check(who, wet, ld, ny, tbox)) return rc;
+    DLESM_REQUIRE(scheme >= DLESM_TRACER_UPWIND && scheme <= DLESM_TRACER_HANCOCK,
+                  "%s: scheme %d (0 upwind, 1 MUSCL, 2 Hancock)", who, scheme);
+    DLESM_REQUIRE(ntracers >= 0 && ntracers <= DLESM_TRACER_MAX, "%s: %d tracers (0..%d)", who, ntracers, DLESM_TRACER_MAX);
+    if (ntracers > 0) {
+        const nemo::TracerFields f{grid->tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
+        if (int rc = nemo::tracer_check(who, ld, ny, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, f, c_in, c_out,
+                                        ntracers))
+            return rc;
+        // what tracer_check does not know of: the step's other four outputs and the arrays of the grid
+        const double *const more[14] = {ssha_u, ssha_v, ua, va, grid->dx_t, grid->dy_t, grid->dx_u, grid->dy_u, grid->dx_v,
+                                        grid->dy_v, grid->area_u, grid->area_v, grid->fcor_u, grid->fcor_v};
+        static const char *const more_name[14] = {"ssha_u", "ssha_v", "ua", "va", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v",
+                                                  "dy_v", "area_u", "area_v", "fcor_u", "fcor_v"};
+        const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
+        for (int k = 0; k < ntracers; k++)
+            for (int m = 0; m < 14; m++)
+                DLESM_REQUIRE(!nemo::overlap(c_out[k], nb, more[m], nb), "%s: c_out[%d] overlaps %s", who, k, more_name[m]);
+    }
+    auto step = [&] {         // (wet == NULL: dlesm_nemolite_step_f64)
+        return dlesm_nemolite_step_wet_f64(wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv,
+                                           sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+    };
+    auto tracers = [&] {
+        if (ntracers == 0) return (int)DLESM_OK;
+        return entries[scheme](params->rdt, ld, ny, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, grid->tmask, area_t,
+                               un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
+    };
+    if (p->sends.empty() && p->recvs.empty()) {      // no neighbour: the two single-domain entries, bit for bit
+        if (int rc = step()) return rc;
+        return tracers();
+    }
+
+    // ---- every refusal of a plan with messages, before anything is launched or exchanged
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
+    int depth = 0;
+    for (const Msg &m : p->recvs) {
+        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
+        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
+        if (!xdir && !ydir) continue;
+        const int d = xdir ? m.nx : m.ny;
+        DLESM_REQUIRE(d == 1 || d == 2, "%s: the plan exchanges depth-%d halos, the step needs depth 1 or 2 (a grid "
+                      "decomposed with halo_width = 1 or 2)", who, d);
+        DLESM_REQUIRE(depth == 0 || d == depth, "%s: the plan mixes depth-%d and depth-%d halos", who, depth, d);
+        depth = d;
+    }
+    DLESM_REQUIRE(ntracers == 0 || scheme == DLESM_TRACER_UPWIND || depth != 1,
+                  "%s: the plan exchanges depth-1 halos, the limited tracer schemes need depth 2 (a grid decomposed with "
+                  "halo_width = 2)", who);
+    DLESM_REQUIRE(nemo::same_box(tbox, ubox) && nemo::same_box(tbox, vbox),
+                  "%s: on a decomposed grid the T, U and V boxes must be one box (every NE grid): T (%d:%d,%d:%d), "
+                  "U (%d:%d,%d:%d), V (%d:%d,%d:%d)", who, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, ubox->xstart,
+                  ubox->xstop, ubox->ystart, ubox->ystop, vbox->xstart, vbox->xstop, vbox->ystart, vbox->ystop);
+    DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
+    RingRects r{};
+    if (!nemo::empty(tbox)) {
+        const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
+        const nemo::Box ring[2] = {{x1 + 1, x1 + 1, y0, y1}, {x0, x1, y1 + 1, y1 + 1}};   // east column, north row
+        for (const Msg &m : p->recvs)
+            for (const nemo::Box &b : ring) {
+                const int a0 = std::max(b.x0, m.i0), a1 = std::min(b.x1, m.i0 + m.nx - 1);
+                const int c0 = std::max(b.y0, m.j0), c1 = std::min(b.y1, m.j0 + m.ny - 1);
+                if (a0 > a1 || c0 > c1) continue;
+                DLESM_REQUIRE(r.n < RingRects::MAX, "%s: more than %d receive strips border the box", who, RingRects::MAX);
+                r.x0[r.n] = a0, r.x1[r.n] = a1, r.y0[r.n] = c0, r.y1[r.n] = c1;
+                r.n++;
+            }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nf = 5 + ntracers;
+    double *outs[5 + DLESM_TRACER_MAX] = {ssha, ssha_u, ssha_v, ua, va};
+    for (int k = 0; k < ntracers; k++) outs[5 + k] = c_out[k];
+    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil((5 + ntracers) / peer_fcap)
+    // mailbox operations per call on every rank -- nothing rank-local (obc, the wet plan, the path the step takes, the box)
+    // changes that number; over RCCL one aggregated group
+    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
+    const int turn = mailbox ? p->peer_fcap : nf;
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
+    if (!mailbox && tuning("dm_aggregate", 1))       // (the buffers of 5 + ntracers fields: a capture is refused here, not later)
+        if (int rc = ensure_agg(p, nf, s)) return rc;
+    if (int rc = join_pending(p, s)) return rc;
+
+    // 1. ssha on the ring cells the neighbours send
+    if (r.n) {
+        int most = 0;
+        for (int k = 0; k < r.n; k++) most = std::max(most, (r.x1[k] - r.x0[k] + 1) * (r.y1[k] - r.y0[k] + 1));
+        const unsigned gx = (unsigned)std::min((most + 255) / 256, 64);
+        hipLaunchKernelGGL(nemolite_ssha_ring, dim3(gx, r.n), dim3(256), 0, s, r, params->rdt, ld, sshn_t, sshn_u, sshn_v, hu,
+                           hv, un, vn, area_t, ssha);
+        DLESM_HIP_TRY(hipGetLastError());
+    }
+    // 2. the single-domain step; 3. the tracer sweep, carried by the level-n transports into the new water column
+    if (int rc = step()) return rc;
+    if (int rc = tracers()) return rc;
+    // 4. one exchange of the 5 + ntracers outputs (mailboxes: in turns of peer_fcap fields)
+    for (int k = 0; k < nf; k += turn)
+        if (int rc = exchange_on(p, outs + k, std::min(turn, nf - k), DLESM_DIRS_ALL, s)) return rc;
+    return DLESM_OK;
+}
+
+// The halos of ONE int field from the neighbours (dlesm_halo_exchange_i32) -- the T mask of a grid
+// decomposed with halo_width = 2, whose second halo cell grid_init can only replicate.  The field travels as doubles (exact
+// for every int32) through the plan's own exchange: widen into a plan-owned scratch, exchange the scratch, narrow the cells of
+// the receive rectangles back.  No other cell of the field is written.
+struct I32Rects {
+    static constexpr int MAX = 32;
+    int n;
+    int x0[MAX], y0[MAX], nx[MAX], ny[MAX];       // 0-based origin and extent
+};
+
+__global__ __launch_bounds__(256) void widen_i32(const int *__restrict__ src, double *__restrict__ dst, size_t n)
+{
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
+        dst[t] = (double)src[t];
+}
+
+// one thread per received cell of rectangle blockIdx.y
+__global__ __launch_bounds__(256) void narrow_i32(I32Rects r, int ld, const double *__restrict__ src, int *__restrict__ dst)
+{
+    const int k = blockIdx.y;
+    const long long w = r.nx[k], n = w * r.ny[k];
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const size_t o = (size_t)(r.y0[k] + t / w) * (size_t)ld + (size_t)(r.x0[k] + t % w);
+        dst[o] = (int)src[o];
+    }
+}
+
+extern "C" int dlesm_halo_exchange_i32(dlesm_halo_plan *p, int *field, void *stream)
+{
+    static const char *const who = "dlesm_halo_exchange_i32";
+    clear_error();
+    DLESM_REQUIRE(p != nullptr && field != nullptr, "%s: null pointer", who);
+    if (p->sends.empty() && p->recvs.empty()) return DLESM_OK;       // no neighbour: nothing to do
+    if (int rc = ensure_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
+    DLESM_REQUIRE(!capturing(s), "%s: the stream is being captured into a graph, and the call may allocate", who);
+    for (const Msg &m : p->recvs)
+        DLESM_REQUIRE(m.i0 >= 0 && m.j0 >= 0 && m.nx >= 0 && m.ny >= 0 && m.i0 + m.nx <= p->ld && m.j0 + m.ny <= p->ny,
+                      "%s: a receive rectangle (%d:%d,%d:%d) leaves the %dx%d field", who, m.i0, m.i0 + m.nx - 1, m.j0,
+                      m.j0 + m.ny - 1, p->ld, p->ny);
+    const size_t n = (size_t)p->ld * (size_t)p->ny;
+    if (!p->i32_scratch) DLESM_HIP_TRY(hipMalloc((void **)&p->i32_scratch, n * sizeof(double)));
+    if (int rc = join_pending(p, s)) return rc;
+    const unsigned gw = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(widen_i32, dim3(gw), dim3(256), 0, s, field, p->i32_scratch, n);
+    DLESM_HIP_TRY(hipGetLastError());
+    if (int rc = exchange_on(p, p->i32_scratch, DLESM_DIRS_ALL, s)) return rc;
+    for (size_t first = 0; first < p->recvs.size(); first += I32Rects::MAX) {
+        I32Rects r{};
+        long long most = 0;
+        for (size_t m = first; m < p->recvs.size() && m < first + I32Rects::MAX; m++) {
+            const Msg &rm = p->recvs[m];
+            if (rm.nx <= 0 || rm.ny <= 0) continue;
+            r.x0[r.n] = rm.i0, r.y0[r.n] = rm.j0, r.nx[r.n] = rm.nx, r.ny[r.n] = rm.ny;
+            most = std::max(most, (long long)rm.nx * rm.ny);
+            r.n++;
+        }
+        if (!r.n) continue;
+        const unsigned gx = (unsigned)std::min<long long>((most + 255) / 256, 64);
+        hipLaunchKernelGGL(narrow_i32, dim3(gx, r.n), dim3(256), 0, s, r, p->ld, p->i32_scratch, field);
+        DLESM_HIP_TRY(hipGetLastError());
+    }
+    return DLESM_OK;
 }
 
 extern "C" int dlesm_global_sum_f64(double *value)

@@ -67,7 +67,7 @@ module grid_mod
      module procedure grid_constructor
   end interface grid_type
 
-  public grid_init, HALO_WIDTH_X, HALO_WIDTH_Y
+  public grid_init, exchange_mask_halos, HALO_WIDTH_X, HALO_WIDTH_Y
 
 contains
 
@@ -233,5 +233,46 @@ contains
                    (/grid%subdomain%internal%xstart - 1, grid%subdomain%internal%ystart - 1/), ierr)
     if (ierr /= 0) call gocean_stop('Set-up of communication tables (call to map_comms()) failed.')
   end subroutine grid_init
+
+  !> The halos of the grid's T mask from the neighbours (dlesm_halo_exchange_i32, DESIGN.md section 6.13): grid_init can only
+  !! replicate the mask's ring outwards, so on a grid decomposed with halo_width = 2 the second halo cell is not the
+  !! neighbour's until this call.  Runs on the device mirror (made here if it does not exist yet), synchronises, and copies the
+  !! mirror back into grid%tmask, so that open_boundary and wet_plan, which are built from the host mask, see it; plans made from
+  !! the previous mask are released.  Collective.  Without distributed memory the plan has no messages: nothing changes.
+  subroutine exchange_mask_halos(grid)
+    use iso_c_binding, only: c_associated, c_loc, c_size_t
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    use dlesm_hip_mod
+    type(grid_type), intent(inout), target :: grid
+    type(c_ptr) :: plan
+    integer(c_size_t) :: nb
+    integer(c_int) :: rc
+    if (.not. allocated(grid%tmask)) call gocean_stop('exchange_mask_halos: grid_init has not been called for this grid')
+    nb = int(grid%nx, c_size_t) * int(grid%ny, c_size_t) * 4_c_size_t
+    if (.not. c_associated(grid%tmask_device)) then
+       if (hipMalloc(grid%tmask_device, nb) /= 0) call gocean_stop('exchange_mask_halos: hipMalloc failed')
+       if (hipMemcpy(grid%tmask_device, c_loc(grid%tmask), nb, 1_c_int) /= 0) &
+            call gocean_stop('exchange_mask_halos: upload failed')
+    end if
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(grid%nx, grid%ny)
+    else
+       plan = serial_plan_for(grid%nx, grid%ny)
+    end if
+    rc = dlesm_halo_exchange_i32(plan, grid%tmask_device, c_null_ptr)
+    if (rc /= 0) call gocean_stop('exchange_mask_halos: ' // dlesm_error_text())
+    if (hipDeviceSynchronize() /= 0) call gocean_stop('exchange_mask_halos: hipDeviceSynchronize failed')
+    if (hipMemcpy(c_loc(grid%tmask), grid%tmask_device, nb, 2_c_int) /= 0) &
+         call gocean_stop('exchange_mask_halos: download failed')
+    if (c_associated(grid%obc)) then                      ! made from the previous mask
+       rc = dlesm_obc_destroy(grid%obc)
+       grid%obc = c_null_ptr
+    end if
+    if (c_associated(grid%wet)) then
+       rc = dlesm_wet_plan_destroy(grid%wet)
+       grid%wet = c_null_ptr
+    end if
+  end subroutine exchange_mask_halos
 
 end module grid_mod

@@ -13,6 +13,8 @@ module dlesm_hip_mod
   !> dirs_mask values of dlesm_halo_exchange_f64 (include/dlesm_hip.h)
   integer(c_int), parameter :: DLESM_DIRS_ALL = 15_c_int, DLESM_DIRS_NO_DIAGONALS = 16_c_int
   integer, parameter :: DLESM_TRACER_MAX = 8           ! dlesm_tracer_step_f64
+  ! the tracer scheme of dlesm_nemolite_coupled_step_dm (DESIGN.md section 6.13)
+  integer(c_int), parameter :: DLESM_TRACER_UPWIND = 0_c_int, DLESM_TRACER_MUSCL = 1_c_int, DLESM_TRACER_HANCOCK = 2_c_int
   !> norm values of dlesm_stencil5_resid_f64
   integer(c_int), parameter :: DLESM_NORM_MAX = 0_c_int, DLESM_NORM_SUMSQ = 1_c_int
   !> `what` values of dlesm_field_locate_f64, and the most fields one dlesm_field_stats_f64 call takes
@@ -872,6 +874,31 @@ module dlesm_hip_mod
        type(c_ptr), intent(in) :: c_in(*), c_out(*)
        integer(c_int), value :: ntracers
        type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)
+     function dlesm_nemolite_coupled_step_dm(plan, wet, scheme, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, &
+          vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, c_in, c_out, ntracers, stream) &
+          bind(C, name="dlesm_nemolite_coupled_step_dm") result(rc)
+       import :: c_int, c_ptr, c_double, c_momentum_params, c_momentum_grid, c_region
+       type(c_ptr), value :: plan, wet
+       integer(c_int), value :: scheme
+       type(c_momentum_params), intent(in) :: params
+       type(c_momentum_grid), intent(in) :: grid
+       type(c_ptr), value :: area_t
+       integer(c_int), value :: ld, ny
+       type(c_region), intent(in) :: tbox, ubox, vbox
+       type(c_ptr), value :: obc
+       real(c_double), value :: ssh_bc
+       type(c_ptr), value :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va
+       type(c_ptr), intent(in) :: c_in(*), c_out(*)
+       integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_halo_exchange_i32(plan, field, stream) bind(C, name="dlesm_halo_exchange_i32") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, field, stream
        integer(c_int) :: rc
      end function
      function dlesm_shallow_step_x2_dm(plan, params, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, &

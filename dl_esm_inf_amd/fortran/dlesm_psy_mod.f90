@@ -57,6 +57,7 @@ module dlesm_psy_mod
   public :: invoke_nemolite_step, invoke_nemolite_step_dm, wet_plan
   public :: invoke_tracer_step, invoke_tracer_step_dm, invoke_tracer_step_muscl, invoke_tracer_step_muscl_dm
   public :: invoke_tracer_step_hancock, invoke_tracer_step_hancock_dm
+  public :: invoke_nemolite_coupled_step_dm
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -647,6 +648,83 @@ contains
     call tracer_step_call('invoke_tracer_step_hancock_dm', plan, .true., 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, &
                           sshn_t, sshn_u, sshn_v)
   end subroutine invoke_tracer_step_hancock_dm
+
+  !> One coupled time step on a decomposed grid (dlesm_nemolite_coupled_step_dm, DESIGN.md section 6.13): the flow step of
+  !! invoke_nemolite_step_dm and the tracer sweep of `scheme` (DLESM_TRACER_UPWIND, DLESM_TRACER_MUSCL or DLESM_TRACER_HANCOCK)
+  !! with rdt = params%rdt, c_in carried to c_out by the level-n transports into the new water column, then ONE exchange of
+  !! ssha, ssha_u, ssha_v, ua, va and every c_out.  Arrays of size zero: the flow step alone.  The flow inputs need valid depth-1
+  !! halos, corners included; c_in depth-1 halos for the upwind scheme, c_in and the grid's mask depth-2 halos for the limited
+  !! ones (exchange_mask_halos fills the mask's); every output leaves with halos of the grid's halo width.  Collective.  The
+  !! grid must have been decomposed with halo_width = 1 or 2, a limited scheme needs halo_width = 2 (without distributed memory
+  !! the plan has no messages: invoke_nemolite_step and the single-domain tracer wrapper, bit for bit).  ssh_bc and skip_land as
+  !! invoke_nemolite_step_dm.
+  subroutine invoke_nemolite_coupled_step_dm(params, scheme, c_out, c_in, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, &
+                                             sshn_t, sshn_u, sshn_v, ssh_bc, skip_land)
+    use parallel_comms_mod, only: halo_plan_for, serial_plan_for
+    use parallel_utils_mod, only: DIST_MEM_ENABLED
+    type(c_momentum_params), intent(in) :: params
+    integer, intent(in) :: scheme
+    type(r2d_field), intent(inout), target :: c_out(:), c_in(:)
+    type(r2d_field), intent(inout), target :: ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    real(go_wp), optional, intent(in) :: ssh_bc
+    logical, optional, intent(in) :: skip_land
+    type(c_momentum_grid) :: mg
+    type(c_region) :: tbox, ubox, vbox
+    type(c_ptr) :: plan, obc, wet
+    type(c_ptr) :: pin(DLESM_TRACER_MAX), pout(DLESM_TRACER_MAX)
+    real(c_double) :: bc
+    integer(c_int) :: rc
+    integer :: hw, k, n
+    hw = ssha%grid%subdomain%internal%xstart - 1
+    if ((hw /= 1 .and. hw /= 2) .or. ssha%grid%subdomain%internal%ystart - 1 /= hw) &
+         call gocean_stop('invoke_nemolite_coupled_step_dm: the grid must be decomposed with halo_width = 1 or 2')
+    if (scheme < DLESM_TRACER_UPWIND .or. scheme > DLESM_TRACER_HANCOCK) &
+         call gocean_stop('invoke_nemolite_coupled_step_dm: the scheme must be DLESM_TRACER_UPWIND, _MUSCL or _HANCOCK')
+    n = size(c_in)
+    if (size(c_out) /= n) call gocean_stop('invoke_nemolite_coupled_step_dm: c_out and c_in differ in size')
+    if (n > DLESM_TRACER_MAX) call gocean_stop('invoke_nemolite_coupled_step_dm: the number of tracers must be 0..8')
+    if (hw == 1 .and. scheme /= DLESM_TRACER_UPWIND .and. n > 0) &
+         call gocean_stop('invoke_nemolite_coupled_step_dm: a limited scheme reads two cells: the grid must be decomposed ' // &
+                          'with halo_width = 2')
+    call need_device(ssha);  call need_device(ssha_u);  call need_device(ssha_v);  call need_device(ua);  call need_device(va)
+    call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(hu);  call need_device(hv)
+    call need_device(sshn_t);  call need_device(sshn_u);  call need_device(sshn_v)
+    pin = c_null_ptr;  pout = c_null_ptr
+    do k = 1, n
+       call need_device(c_in(k));  call need_device(c_out(k))
+       pin(k) = field_device_data(c_in(k));  pout(k) = field_device_data(c_out(k))
+    end do
+    mg = momentum_grid(ssha%grid, 'invoke_nemolite_coupled_step_dm')
+    tbox = c_region(ssha%internal%nx, ssha%internal%ny, ssha%internal%xstart, ssha%internal%xstop, &
+                    ssha%internal%ystart, ssha%internal%ystop)
+    ubox = c_region(ua%internal%nx, ua%internal%ny, ua%internal%xstart, ua%internal%xstop, &
+                    ua%internal%ystart, ua%internal%ystop)
+    vbox = c_region(va%internal%nx, va%internal%ny, va%internal%xstart, va%internal%xstop, &
+                    va%internal%ystart, va%internal%ystop)
+    obc = c_null_ptr
+    bc = 0.0_c_double
+    if (present(ssh_bc)) then
+       obc = open_boundary(ssha%grid)
+       bc = real(ssh_bc, c_double)
+    end if
+    if (DIST_MEM_ENABLED) then
+       plan = halo_plan_for(ssha%grid%nx, ssha%grid%ny)
+    else
+       plan = serial_plan_for(ssha%grid%nx, ssha%grid%ny)
+    end if
+    wet = c_null_ptr
+    if (present(skip_land)) then
+       if (skip_land) wet = wet_plan(ssha%grid)
+    end if
+    rc = dlesm_nemolite_coupled_step_dm(plan, wet, int(scheme, c_int), params, mg, ssha%grid%area_t_device, &
+                                        int(ssha%grid%nx, c_int), int(ssha%grid%ny, c_int), tbox, ubox, vbox, obc, bc, &
+                                        field_device_data(un), field_device_data(vn), field_device_data(ht), &
+                                        field_device_data(hu), field_device_data(hv), field_device_data(sshn_t), &
+                                        field_device_data(sshn_u), field_device_data(sshn_v), field_device_data(ssha), &
+                                        field_device_data(ssha_u), field_device_data(ssha_v), field_device_data(ua), &
+                                        field_device_data(va), pin, pout, int(n, c_int), c_null_ptr)
+    if (rc /= 0) call gocean_stop('invoke_nemolite_coupled_step_dm: ' // dlesm_error_text())
+  end subroutine invoke_nemolite_coupled_step_dm
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

@@ -175,6 +175,29 @@ def halo_plan(grid):
     return grid._halo_plan
 
 
+def exchange_mask_halos(grid, stream=None):
+    """The halos of the grid's T mask from the neighbours (dlesm_halo_exchange_i32): grid_init can only
+    replicate the mask's ring outwards, so on a grid decomposed with halo_width = 2 the second halo cell is not the
+    neighbour's until this call.  Runs on the device mirror, synchronises, and copies the mirror back into grid.tmask, so that
+    psy.wet_plan and psy.open_boundary, which are built from the host mask, see it; plans made from the previous mask are
+    released, as grid_init releases them.  COLLECTIVE: every rank calls it, at the same point."""
+    import torch
+    from .field_mod import _stream_ptr
+    L = _cabi.lib()
+    if grid.tmask is None or getattr(grid, "comm_tables", None) is None:
+        raise _cabi.GoceanStop(_cabi.EABORT, "exchange_mask_halos: grid%tmask requested before grid_init")
+    mirror = grid.tmask_device
+    check(L.dlesm_halo_exchange_i32(halo_plan(grid), grid.tmask_device_ptr, _stream_ptr(stream)))
+    torch.cuda.synchronize()
+    grid.tmask = mirror.cpu().numpy()
+    if grid._obc is not None:                              # made from the previous mask
+        check(L.dlesm_obc_destroy(grid._obc.handle))
+        grid._obc = None
+    if grid._wet is not None:
+        check(L.dlesm_wet_plan_destroy(grid._wet.handle))
+        grid._wet = None
+
+
 def connect_peers(grid, nfields=1):
     """Connect the grid's message plan to its neighbours' mailboxes (dlesm_halo_plan_peer_*): from then on
     dlesm_jacobi5_step_dm[_pipelined] on this grid exchanges by storing straight into the neighbours' memory instead of

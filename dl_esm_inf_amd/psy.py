@@ -380,6 +380,47 @@ def invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, ss
                                                                                          sshn_t, sshn_u, sshn_v, stream)))
 
 
+TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
+
+
+def invoke_nemolite_coupled_step_dm(params, scheme, c_out, c_in, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu, hv, sshn_t, sshn_u,
+                                    sshn_v, ssh_bc=None, stream=None, skip_land=False):
+    """one coupled time step on a decomposed grid (dlesm_nemolite_coupled_step_dm): the flow step of
+    invoke_nemolite_step_dm and the tracer sweep of `scheme` ("upwind" | "muscl" | "hancock") with rdt = params.rdt, c_in
+    carried to c_out by the level-n transports into the new water column, then ONE exchange of ssha, ssha_u, ssha_v, ua, va
+    and every c_out.  c_out and c_in are lists of T-point fields (both empty: the flow step alone).  The flow inputs need valid
+    depth-1 halos, corners included; c_in depth-1 halos for "upwind", c_in and the grid's mask depth-2 halos for the limited
+    schemes (grid_mod.exchange_mask_halos fills the mask's); every output leaves with halos of the grid's halo_width.
+    Collective.  Stops on a halo_width other than 1 or 2, on a limited scheme with halo_width 1, and when the grid's Coriolis
+    parameter was never set.  ssh_bc and skip_land as invoke_nemolite_step_dm."""
+    who = "invoke_nemolite_coupled_step_dm"
+    g = ssha.grid
+    if scheme not in TRACER_SCHEMES:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: scheme %r (one of %s)" % (who, scheme, ", ".join(TRACER_SCHEMES)))
+    c_out, c_in = list(c_out), list(c_in)
+    if len(c_out) != len(c_in):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: %d output fields for %d tracers" % (who, len(c_out), len(c_in)))
+    hw = getattr(g, "halo_width", 1)
+    if hw not in (1, 2):
+        raise _cabi.GoceanStop(_cabi.EABORT, "%s: the grid has halo_width %d; the step exchanges depth-1 or depth-2 halos: "
+                                             "decompose the grid with halo_width = 1 or 2" % (who, hw))
+    if hw == 1 and scheme != "upwind" and c_in:
+        raise _cabi.GoceanStop(_cabi.EABORT, "%s: the grid has halo_width 1; the %s scheme reads two cells and exchanges "
+                                             "depth-2 halos: decompose the grid with halo_width = 2" % (who, scheme))
+    mg = _momentum_grid(g, who)
+    if getattr(g, "comm_tables", None) is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: the grid has no message tables (grid_init after decompose)" % who)
+    obc = None if ssh_bc is None else open_boundary(g).handle
+    n = len(c_in)
+    pin, pout = (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_in]), (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_out])
+    check(_cabi.lib().dlesm_nemolite_coupled_step_dm(
+        grid_mod.halo_plan(g), wet_plan(g).handle if skip_land else None, TRACER_SCHEMES[scheme], C.byref(params), C.byref(mg),
+        C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal), C.byref(ua.internal), C.byref(va.internal),
+        obc, 0.0 if ssh_bc is None else float(ssh_bc),
+        *[f.device_ptr for f in (un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va)], pin, pout, n,
+        _stream_ptr(stream)))
+
+
 def invoke_jacobi5_masked(out_fld, in_fld, stream=None):
     """the masked Jacobi kernel (metadata: GO_GRID_MASK_T): the PSy layer hands the kernel the
     grid's T mask, here its device mirror"""

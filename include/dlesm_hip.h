@@ -1071,6 +1071,44 @@ int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *plan, double rdt, int ld, int 
                                  const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
                                  const double *const *c_in, double *const *c_out, int ntracers, void *stream);
 
+/* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
+ * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
+ * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
+ * definition leaves: dlesm_continuity_f64 over tbox with params->rdt; dlesm_halo_exchange_f64(plan, ssha, DLESM_DIRS_ALL);
+ * next_sshu / next_sshv, momentum and, when obc is not NULL, bc_open, as dlesm_nemolite_step_f64 runs them (wet != NULL: the
+ * contract of dlesm_nemolite_step_wet_f64 for land ssha); the single-domain tracer entry of `scheme` (dlesm_tracer_step_f64,
+ * _muscl_f64 or _hancock_f64) with params->rdt over tbox, grid->tmask, area_t, the level-n flow arrays and the ssha just made,
+ * c_in to c_out; dlesm_halo_exchange_multi_f64(plan, {ssha, ssha_u, ssha_v, ua, va, c_out[0..ntracers-1]}, 5 + ntracers,
+ * DLESM_DIRS_ALL).  The tracer update reads ssha in its own wet cell only and everything else at level n, so one exchange
+ * serves both.
+ * In: the level-n flow arrays with valid depth-1 halos, corners included, as for dlesm_nemolite_step_dm; c_in with depth-1 halos
+ * for DLESM_TRACER_UPWIND; c_in and grid->tmask with depth-2 halos for the two limited schemes (dlesm_halo_exchange_i32 fills
+ * the mask's).  Out: all 5 + ntracers outputs with halos of the plan's depth; a time loop only rotates the pointers.
+ * ntracers = 0 is the flow step alone, on a plan of either depth (c_in / c_out may be NULL; scheme is still checked).
+ * A plan without messages: dlesm_nemolite_step_wet_f64, then the tracer entry over tbox, for any boxes.  A plan with messages
+ * needs tbox == ubox == vbox, x and y receive messages all of depth 1 or all of depth 2, and depth 2 when ntracers > 0 and the
+ * scheme is a limited one.  DLESM_EINVAL before anything is launched or exchanged: every refusal of dlesm_nemolite_step_wet_f64
+ * and of the tracer entries, a scheme outside 0..2, ntracers outside 0..DLESM_TRACER_MAX, a c_out[k] that overlaps ssha_u,
+ * ssha_v, ua, va or an array of grid, a null plan, a plan for other extents, another or a mixed depth, a limited scheme on a
+ * depth-1 plan, and the guards of the other *_dm entries.  Over connected mailboxes the exchange runs in
+ * ceil((5 + ntracers) / mailbox fields) turns on every rank, whatever the box, obc, the wet plan or the path the step takes;
+ * over RCCL it is one aggregated group.  obc and wet are rank-local.  Collective: every rank calls it, in the same order. */
+enum { DLESM_TRACER_UPWIND = 0, DLESM_TRACER_MUSCL = 1, DLESM_TRACER_HANCOCK = 2 };
+int dlesm_nemolite_coupled_step_dm(dlesm_halo_plan *plan, const dlesm_wet_plan *wet, int scheme,
+                                   const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
+                                   const double *area_t, int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox,
+                                   const dlesm_region *vbox, const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn,
+                                   const double *ht, const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
+                                   const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
+                                   const double *const *c_in, double *const *c_out, int ntracers, void *stream);
+/* The halos of one int field of the plan's extents (ny x ld, device) from the neighbours: after the
+ * call every cell a receive message of the plan covers holds the sending rank's value, and no other cell has changed.  All
+ * directions, a plan of any depth; a plan without messages does nothing.  The values travel as doubles (exact for every int)
+ * through a scratch of ld x ny doubles the plan owns, allocated by the first call and freed with the plan: one mailbox
+ * operation per rank.  Asynchronous on `stream`.  DLESM_EINVAL: a null plan or field, an earlier wait that timed out, a stream
+ * that is being captured (the first call allocates).  Collective: every rank calls it, in the same order. */
+int dlesm_halo_exchange_i32(dlesm_halo_plan *plan, int *field, void *stream);
+
 /* global_sum, parallel_utils_mod.f90:230-238: in-place sum of one host double
  * over all ranks (synchronous). */
 int dlesm_global_sum_f64(double *value);
