@@ -814,7 +814,7 @@ def test_distributed_steps_at_the_weak_scaling_tile(D):
 
 # --------------------------------------------------------------------------- grid properties (f.4)
 @pytest.mark.parametrize("nx,ny,alignment", [(5, 4, None), (64, 48, 8), (300, 70, 64), (257, 129, None), (1, 1, 2),
-                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64)])
+                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64), (6, 4200, None)])
 @pytest.mark.parametrize("kernel", [0, 1])
 def test_masked_jacobi_matches_oracle(D, nx, ny, alignment, kernel):
     """a kernel that consumes a grid property: the PSy layer passes grid%tmask_device (GO_GRID_MASK_T).
@@ -899,7 +899,7 @@ def test_masked_jacobi_with_a_mask_at_full_size(D):
 
 # --------------------------------------------------------------------------- general 9-point stencil
 @pytest.mark.parametrize("nx,ny,alignment", [(5, 4, None), (64, 48, 8), (300, 70, 64), (257, 129, None), (1, 1, 2),
-                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64)])
+                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64), (6, 4200, None)])
 @pytest.mark.parametrize("kernel", [0, 1])
 def test_stencil9_matches_oracle(D, nx, ny, alignment, kernel):
     """dlesm_stencil9_f64 (wave-tile form and one-cell-per-thread form) against orc_stencil9, bit for
@@ -1002,7 +1002,7 @@ def _continuity_fields(D, g):
 
 
 @pytest.mark.parametrize("nx,ny,alignment", [(5, 4, None), (64, 48, 8), (300, 70, 64), (257, 129, None), (1, 1, 2),
-                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64)])
+                                             (129, 3, 2), (1000, 37, 64), (4100, 9, 64), (6, 4200, None)])
 @pytest.mark.parametrize("kernel", [0, 1])
 def test_continuity_matches_oracle(D, nx, ny, alignment, kernel):
     """dlesm_continuity_f64 (wave-tile form and one-cell-per-thread form) against orc_continuity, bit for
@@ -1184,7 +1184,7 @@ def test_distributed_steps_captured_into_a_graph(D, pipelined):
 # --------------------------------------------------------------------------- shallow water
 @pytest.mark.parametrize("nx,ny,alignment", [(5, 4, None), (5, 4, 2), (64, 48, 8), (300, 70, 64), (257, 129, None),
                                              (1, 1, 2), (123, 3, 2), (124, 5, 2), (125, 2, 2), (1000, 37, 64),
-                                             (8000, 9, 64)])
+                                             (8000, 9, 64), (6, 4200, None)])
 @pytest.mark.parametrize("sw_kernel,sw_rows,sw_dpp", [(0, 2, 1), (0, 1, 1), (0, 3, 1), (0, 2, 0), (0, 3, 0), (1, 2, 1)])
 def test_shallow_step_matches_oracle(D, nx, ny, alignment, sw_kernel, sw_rows, sw_dpp):
     import torch

@@ -64,7 +64,8 @@ def _launch(D, name, offset, ld, ny, box, out, ins, s0, s1):
 def test_each_kernel_matches_its_oracle_loop_nest(D, name, sw_offset, swk_kernel):
     """arbitrary input arrays (the intermediates are NOT derived from a state), even and odd leading dimensions,
     boxes from one cell to the largest the kernel's stencil allows (touching the array edge on the sides it does
-    not read), ragged widths around the 62/63/64-lane tile boundaries; nothing outside the box is written"""
+    not read), ragged widths around the 62/63/64-lane tile boundaries, 4200 rows (the one-cell-per-thread kernel's row loop
+    makes a second trip past gridDim.y = 4096); nothing outside the box is written"""
     import torch
     D._cabi.lib().dlesm_set_tuning(b"swk_kernel", swk_kernel & 1)
     if swk_kernel == 2:                      # the cache policies large arrays get (in-place kernels: loads too)
@@ -75,7 +76,7 @@ def test_each_kernel_matches_its_oracle_loop_nest(D, name, sw_offset, swk_kernel
     rw, re, rs, rn = N.KERNEL_RING[sw_offset][name]
     offset = D.GO_OFFSET_SW if sw_offset else D.GO_OFFSET_NE
     try:
-        for (ld, nyarr) in [(40, 31), (37, 12), (131, 9), (3, 3), (256, 7), (259, 6), (1030, 40), (4163, 5)]:
+        for (ld, nyarr) in [(40, 31), (37, 12), (131, 9), (3, 3), (256, 7), (259, 6), (1030, 40), (4163, 5), (6, 4200)]:
             rng = np.random.default_rng(ld * 100 + nyarr + len(name))
             host = [rng.random((nyarr, ld)) + 0.5 for _ in range(N.KERNEL_NIN[name])]
             dev = [torch.from_numpy(h).cuda() for h in host]

@@ -1,7 +1,8 @@
 """GPU tests (-m gpu) of tracer transport, dlesm_tracer_step_f64: bit for bit tests/tracer_numpy.py on
 whole arrays -- box, ring and padding of sentinel-filled outputs -- with the wave tile and the general path (HOOK key
 tracer_kernel, odd pitches, unaligned bases), for 1..8 tracers of different data, on sub-boxes, on masks of all land, all wet,
-a wet stripe and open edges; land invariance on the device; the refusals, which write nothing; a time loop with the step
+a wet stripe and open edges; boxes of 4200 rows, which make the second trip of the one-cell-per-thread kernel's row loop
+(gridDim.y = 4096); land invariance on the device; the refusals, which write nothing; a time loop with the step
 captured into a hipGraph; six open-channel steps through the Python wrappers against the CPU loop; one 4096^2 case.
 
 No case past 2^31 cells.  One written after tests/test_gpu_nemolite_large_index.py (shared read-only inputs, 112 GB of arrays,
@@ -96,6 +97,16 @@ def test_shapes_and_paths(D, ld, ny, kernel):
     tm, got = _check(D, ld, ny, (2, ld - 1, 2, ny - 1), 2, kernel, ld * 7 + ny)
     if ld > 8:
         assert (got[0] != TC.SENTINEL).any() and (got[0][1:-1, 1:-1] == TC.SENTINEL).any()
+
+
+# 4200 rows: the second trip of the one-cell-per-thread kernel's row loop (kernel = 1; 13 is an odd pitch, which takes that
+# kernel with kernel = 0), and the tile at the same height
+@pytest.mark.parametrize("ld,ny,kernel", [(12, 4200, 1), (13, 4200, 0), (66, 4200, 0)])
+def test_tall_boxes(D, ld, ny, kernel):
+    """two tracers against the array restatement; wet cells were written beyond row 4096 of the box"""
+    tm, got = _check(D, ld, ny, (2, ld - 1, 2, ny - 1), 2, kernel, ld * 7 + ny)
+    far = tm[4097:ny - 1, 1:ld - 1] > 0              # the box starts at row 1 (0-based): its rows 4096 ..
+    assert far.sum() > ld and all((g[4097:ny - 1, 1:ld - 1][far] != TC.SENTINEL).all() for g in got)
 
 
 @pytest.mark.parametrize("ld,ny", [(300, 70), (4100, 9)])

@@ -5,7 +5,13 @@ with both seams, columns 124 and 248, inside the box; 130 x 6 two; 64 x 5 one; 1
 one-cell-per-thread kernel; boxes start on even and on odd columns, hug the array's edge on all four sides (rows j-2 / j+2
 and columns i-2 / i+2 then fall outside the array, and the random masks put wet cells into the ring), and shrink to one row
 and to one column; 1..8 tracers cover the four instantiations and the two-launch calls.  The HOOK key, an unaligned base and
-land fills of NaN and 1e300 give the same bits; an empty box writes nothing.  The distributed form in loop-back on one GPU
+land fills of NaN and 1e300 give the same bits; an empty box writes nothing.  Wide rows: a row of the box takes
+nxw = (x1 / 2 - c_first + 62) / 62 tiles (0-based x1, c_first = (x0 / 2) & ~7), which the launcher's block shape -- four waves
+a workgroup, the smallest count that is +-1 modulo 32 -- pads with idle tiles: 260 x 9 has 3 real tiles of 31, 1000 x 9 has 9 of
+31 (its real tiles span three workgroups), the sub-box of 1300 x 8 starts mid-row at c_first = 144 and has 9 of 31, 4100 x 7
+has 34 of 63; the j5_* shape keys, which reach this launch, change no bit.  Tall boxes: 4200 rows make the second trip of the
+one-cell-per-thread kernel's row loop (gridDim.y = 4096), at an even and an odd pitch, and the tile sees the same height.  The
+distributed form in loop-back on one GPU
 (rank 0 its own eight neighbours through depth-2 tables) equals the single-domain entry followed by the multi-field
 exchange, a depth-1 plan is refused, and a plan without messages is the single-domain entry."""
 import ctypes as C
@@ -129,7 +135,14 @@ BOXES = [
     (64, 5, (63, 63, 2, 4)),         # ... and beside its east edge
     (131, 7, (2, 130, 2, 6)),        # an odd pitch: one cell per thread
     (131, 7, (3, 129, 4, 4)),
+    (1000, 9, (2, 999, 2, 8)),       # nxw = (499 - 0 + 62) / 62 = 9 real tiles, padded to 31: three workgroups hold real tiles
+    (1300, 8, (301, 1291, 3, 6)),    # starts mid-row: c_first = 150 & ~7 = 144, nxw = (645 - 144 + 62) / 62 = 9, padded to 31
+    (4100, 7, (2, 4099, 2, 6)),      # nxw = (2049 + 62) / 62 = 34 real tiles, padded to 63
 ]
+# 4200 rows: the second trip of the one-cell-per-thread kernel's row loop (kernel = 1; 13 is an odd pitch, which takes that
+# kernel with kernel = 0), and the tile at the same height
+TALL = [(12, 4200, 1), (13, 4200, 0), (66, 4200, 0)]
+SHAPE_KEYS = {"j5_autoshape": 1, "j5_tpb": 0, "j5_pad_tiles": 0}       # the keys test_shape_keys_change_no_bit sets: defaults
 
 
 @pytest.mark.parametrize("ld,ny,box", BOXES)
@@ -142,6 +155,31 @@ def test_boxes_and_paths(D, ld, ny, box, kernel):
     assert (edge > 0).any()
     xs, xe, ys, ye = box
     assert (got[0][ys - 1:ye, xs - 1:xe] != TC.SENTINEL).any()
+
+
+@pytest.mark.parametrize("ld,ny,kernel", TALL)
+def test_tall_boxes(D, ld, ny, kernel):
+    """two tracers against the array restatement; wet cells were written beyond row 4096 of the box"""
+    tm, got = _check(D, ld, ny, _edge_box(ld, ny), 2, kernel, ld * 7 + ny)
+    far = tm[4097:ny - 1, 1:ld - 1] > 0              # the box starts at row 1 (0-based): its rows 4096 ..
+    assert far.sum() > ld and all((g[4097:ny - 1, 1:ld - 1][far] != TC.SENTINEL).all() for g in got)
+
+
+def test_shape_keys_change_no_bit(D):
+    """1000 x 9, three tracers: the j5_* keys of choose_block_shape reach the tile's launch -- no padding (9 tiles), 2 waves a
+    workgroup (15 tiles), 8 and 16 (62 and 124 tiles; the launcher then clamps the workgroup to 4 waves), three tiles more (34)
+    -- and every call leaves the restatement's bits; every key is back at its default afterwards"""
+    ld, ny = 1000, 9
+    box = _edge_box(ld, ny)
+    L = D._cabi.lib()
+    try:
+        for key, value in ((None, 0), ("j5_autoshape", 0), ("j5_tpb", 2), ("j5_tpb", 8), ("j5_tpb", 16), ("j5_pad_tiles", 3)):
+            for name, default in SHAPE_KEYS.items():
+                L.dlesm_set_tuning(name.encode(), value if name == key else default)
+            _check(D, ld, ny, box, 3, 0, ld * 7 + ny)
+    finally:
+        for name, default in SHAPE_KEYS.items():
+            L.dlesm_set_tuning(name.encode(), default)
 
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])

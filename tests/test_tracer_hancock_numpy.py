@@ -75,11 +75,12 @@ def test_the_big_rdt_runs_both_branches_of_the_factor():
         assert TH.face_shares(TC.RDT, box, tm, area_t, *[H[n] for n in TC.FLOW])[1] == 0.0
     print("shares over %d faces: 0 < n < 1 %.3f, n >= 1 %.3f" % (total, mid / total, big / total))
     assert mid / total >= 0.10 and big / total >= 0.10
-    for ld, ny in ((260, 9), (131, 7), (130, 6), (64, 5)):
+    sub = {(1300, 8): (301, 1291, 3, 6)}                  # the GPU tests sweep this array on a sub-box only
+    for ld, ny in ((260, 9), (131, 7), (130, 6), (64, 5), (1000, 9), (1300, 8), (4100, 7), (12, 4200), (13, 4200), (66, 4200)):
         rng = np.random.default_rng(ld * 7 + ny)
         tm = TC.random_mask(rng, ny, ld)
         area_t, H = TC.flow_inputs(rng, tm)
-        m, b = TH.face_shares(RDT_BIG, (2, ld - 1, 2, ny - 1), tm, area_t, *[H[n] for n in TC.FLOW])
+        m, b = TH.face_shares(RDT_BIG, sub.get((ld, ny), (2, ld - 1, 2, ny - 1)), tm, area_t, *[H[n] for n in TC.FLOW])
         print("%dx%d: 0 < n < 1 %.3f, n >= 1 %.3f" % (ld, ny, m, b))
         assert m >= 0.10 and b >= 0.10
 

@@ -1,6 +1,7 @@
 """Test helpers of the tracer transport tests: the flow and tracer inputs the CPU and GPU tests
-share, the land overwrites of the invariance tests, and a NEMOLite2D-class CPU time step built from the existing
-restatements (oracle_lib continuity, momentum_numpy, open_bc_numpy) that carries tracers with tracer_numpy.
+share, the special-value case of the three schemes (sections 6.10-6.12), the land overwrites of the invariance tests, and a
+NEMOLite2D-class CPU time step built from the existing restatements (oracle_lib continuity, momentum_numpy, open_bc_numpy)
+that carries tracers with tracer_numpy.
 Nothing here needs a GPU.
 """
 import math
@@ -10,8 +11,10 @@ import numpy as np
 import momentum_numpy as M
 import open_bc_numpy as B
 import oracle_lib as O
+import tracer_hancock_numpy as TH
+import tracer_muscl_numpy as TM
 import tracer_numpy as TN
-from nemolite_boxes import METRICS, MOM, PRM, _host_inputs, host_grid
+from nemolite_boxes import METRICS, MOM, PRM, SPECIAL, _host_inputs, host_grid, is_subnormal
 
 FLOW = ("un", "vn", "hu", "hv", "ht", "sshn_t", "sshn_u", "sshn_v", "ssha")     # the C entry's order, after tmask and area_t
 RDT = 600.0
@@ -34,6 +37,105 @@ def flow_inputs(rng, tm):
 def tracers(rng, shape, k):
     """k tracers of different data, and sentinel-filled outputs"""
     return [float(n + 1) + rng.random(shape) for n in range(k)], [np.full(shape, SENTINEL) for _ in range(k)]
+
+
+PATCH = (slice(3, 7), slice(8, 40))             # special_case's patch of unit weights: rows 3..6, columns 8..39 (0-based)
+ONE_BELOW = float(np.nextafter(1.0, 0.0))
+PATCH_VELOCITIES = np.array([1.0, ONE_BELOW, 0.5, 0.0, -0.0, -1.0, 2.0, -ONE_BELOW])
+
+
+def _sprinkle(rng, a, share):
+    """nemolite_boxes.SPECIAL drawn into `share` of the cells of a"""
+    pick = rng.random(a.shape) < share
+    a[pick] = rng.choice(SPECIAL, size=int(pick.sum()))
+
+
+def special_case(seed, ld, ny, rdt):
+    """(tm, area_t, H, c_in, c_out) with four tracers, for arrays of at least 9 rows and 42 columns: random_mask and
+    flow_inputs, then the values at which the arithmetic of sections 6.10-6.12 has an edge, in wet cells:
+      * nemolite_boxes.SPECIAL (subnormals, signed zeros, infinities, NaN of both signs, 1e300, 1e154) in 2 % of un and vn,
+        in 0.5 % of every other flow array and in 0.4 % of area_t -- an area of 0 makes q and w infinite;
+      * ssha = -ht on 1 % of the wet cells and sshn_t = -ht on another 1 %: h_new == 0 and h_old == 0 (and one cell of each
+        kind in PATCH's last column, so that a small box holds them whatever the random picks hit);
+      * PATCH, all wet, with area_t = rdt, ht = hu = hv = 1 and every surface 0, so that w == 1 exactly and a face's Courant
+        number is the magnitude of its velocity, drawn from PATCH_VELOCITIES: 1, one ulp below 1, 0.5, 0 and 2;
+      * tracer 0: multiples of 1/2 in 0 .. 2, so that every tie of the limiter occurs (a == b, a == 0, a == -b and
+        2|a| == |a+b|/2); tracer 1: 1 + random with SPECIAL in 2 % of the cells; tracer 2: multiples of 2.5e-310, so that its
+        slopes are subnormal; tracer 3: of the order of 1e300, so that its fluxes overflow.
+    The outputs hold SENTINEL."""
+    rng = np.random.default_rng(seed)
+    tm = random_mask(rng, ny, ld)
+    area_t, H = flow_inputs(rng, tm)
+    shape = tm.shape
+    for k in ("un", "vn"):
+        _sprinkle(rng, H[k], 0.02)
+    for k in ("sshn_u", "sshn_v", "hu", "hv", "ht", "sshn_t", "ssha"):
+        _sprinkle(rng, H[k], 0.005)
+    _sprinkle(rng, area_t, 0.004)
+    pick = rng.random(shape)
+    new, old = (pick < 0.01) & (tm > 0), (pick >= 0.01) & (pick < 0.02) & (tm > 0)
+    H["ssha"][new] = -H["ht"][new]
+    H["sshn_t"][old] = -H["ht"][old]
+    tm[PATCH] = 1
+    area_t[PATCH] = float(rdt)
+    for k in ("ht", "hu", "hv"):
+        H[k][PATCH] = 1.0
+    for k in ("sshn_t", "sshn_u", "sshn_v", "ssha"):
+        H[k][PATCH] = 0.0
+    for k in ("un", "vn"):
+        H[k][PATCH] = rng.choice(PATCH_VELOCITIES, size=H[k][PATCH].shape)
+    H["ssha"][PATCH][0, -1] = -1.0                 # whatever the random picks hit: h_new == 0 in one cell of the patch ...
+    H["sshn_t"][PATCH][2, -1] = -1.0               # ... and h_old == 0 (an infinite w) in another
+    c_in = [0.5 * rng.integers(0, 5, shape), 1.0 + rng.random(shape), 2.5e-310 * rng.integers(-3, 4, shape),
+            1e300 * (rng.random(shape) - 0.5)]
+    _sprinkle(rng, c_in[1], 0.02)
+    return tm, area_t, H, c_in, [np.full(shape, SENTINEL) for _ in range(4)]
+
+
+# the three schemes: (C entry, HOOK key, array restatement, scalar restatement)
+SCHEMES = {
+    "upwind": ("dlesm_tracer_step_f64", "tracer_kernel", TN.tracer_step, TN.tracer_step_scalar),
+    "muscl": ("dlesm_tracer_step_muscl_f64", "tracer_muscl_kernel", TM.tracer_step_muscl, TM.tracer_step_muscl_scalar),
+    "hancock": ("dlesm_tracer_step_hancock_f64", "tracer_hancock_kernel", TH.tracer_step_hancock,
+                TH.tracer_step_hancock_scalar),
+}
+# 260: three wave tiles of the limited schemes with both seams in the box; 131: the odd pitch; 130 x 9: a sub-box
+SPECIAL_SHAPES = [(260, 12, (2, 259, 2, 11)), (131, 10, (2, 130, 2, 9)), (130, 9, (5, 100, 3, 8))]
+RDT_BIG = 3.0e6                                   # puts the random faces on both sides of a Courant number of 1
+_SPECIAL = {}
+
+
+def special_host(ld, ny, rdt):
+    """special_case of the shape with the modules' seeding rule, made once and never modified"""
+    key = (ld, ny, float(rdt))
+    if key not in _SPECIAL:
+        _SPECIAL[key] = special_case(ld * 7 + ny, ld, ny, rdt)
+    return _SPECIAL[key]
+
+
+def special_reference(scheme, ld, ny, box, rdt, k=4):
+    """what the scheme's array restatement leaves of the first k tracers of special_host; made once, never modified"""
+    key = (scheme, ld, ny, box, float(rdt), k)
+    if key not in _SPECIAL:
+        tm, area_t, H, c_in, c_out = special_host(ld, ny, rdt)
+        want = [a.copy() for a in c_out[:k]]
+        SCHEMES[scheme][2](rdt, box, tm, area_t, *[H[n] for n in FLOW], c_in[:k], want)
+        _SPECIAL[key] = want
+    return _SPECIAL[key]
+
+
+def written(tm, box):
+    """the cells a tracer step writes: the wet cells of the box"""
+    xs, xe, ys, ye = box
+    out = np.zeros(tm.shape, dtype=bool)
+    out[ys - 1:ye, xs - 1:xe] = tm[ys - 1:ye, xs - 1:xe] > 0
+    return out
+
+
+def holds_specials(outs, cells):
+    """(an infinity, a NaN, a subnormal) among `cells` of the arrays `outs`"""
+    v = np.concatenate([o[cells] for o in outs])
+    return bool(np.isinf(v).any()), bool(np.isnan(v).any()), bool(is_subnormal(v).any())
 
 
 def reference(rdt, box, tm, area_t, H, c_in, c_out):
