@@ -1843,7 +1843,10 @@ extern "C" int dlesm_shallow_step_smooth_x2_dm(dlesm_halo_plan *p, const dlesm_s
 // exchanges ssha between continuity and next_ssh* only so that the faces of the east column and the north row of the box can
 // read ssha in the ring; where a neighbour sends those ring cells they are its interior cells, and continuity computes them
 // here from the depth-1 halos of level n with the same expression tree and operands, so they are its bits.  Then the
-// single-domain step (section 6.7) unchanged, then ONE exchange of the five outputs.
+// single-domain step (section 6.7) unchanged, then ONE exchange of the five outputs.  The tracer entries (sections 6.10 to
+// 6.12) and the coupled entry (section 6.13) are the same sequence with a tracer sweep behind or in place of the step, so all
+// six entries run ONE body, nemolite_dm_step: its guards, its refusals in their order and its rule for the mailbox turns
+// stand there once.
 
 // the ring cells one receive message of the plan writes that a face of the box reads: its rectangle intersected with the
 // east column (x1+1, y0:y1) and the north row (x0:x1, y1+1); 0-based inclusive
@@ -1870,83 +1873,202 @@ __global__ __launch_bounds__(256) void nemolite_ssha_ring(RingRects r, double rd
     }
 }
 
-// dlesm_nemolite_step_dm (wet == NULL) and dlesm_nemolite_step_wet_dm: the wet plan only reaches step 2
-static int nemolite_step_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_wet_plan *wet,
-                                 const dlesm_momentum_params *params, const dlesm_momentum_grid *grid, const double *area_t,
-                                 int ld, int ny, const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
-                                 const dlesm_obc *obc, double ssh_bc, const double *un, const double *vn, const double *ht,
-                                 const double *hu, const double *hv, const double *sshn_t, const double *sshn_u,
-                                 const double *sshn_v, double *ssha, double *ssha_u, double *ssha_v, double *ua, double *va,
-                                 void *stream)
+// What one call does, for the one body below.  A flow part alone: dlesm_nemolite_step_dm and dlesm_nemolite_step_wet_dm
+// (section 6.8, 6.9).  A tracer part alone: dlesm_tracer_step_dm, _muscl_dm, _hancock_dm (sections 6.10 to 6.12).  Both:
+// dlesm_nemolite_coupled_step_dm (section 6.13).
+struct NemoFlow {                // the arguments of dlesm_nemolite_step_wet_f64 (wet == NULL: dlesm_nemolite_step_f64)
+    const dlesm_wet_plan *wet;
+    const dlesm_momentum_params *params;
+    const dlesm_momentum_grid *grid;
+    const double *area_t;
+    const dlesm_region *tbox, *ubox, *vbox;
+    const dlesm_obc *obc;
+    double ssh_bc;
+    const double *un, *vn, *ht, *hu, *hv, *sshn_t, *sshn_u, *sshn_v;
+    double *ssha, *ssha_u, *ssha_v, *ua, *va;
+};
+struct NemoTracers {             // the arguments of the single-domain tracer entry of `scheme`
+    int scheme;
+    double rdt;                  // rdt, the box and f: next to a flow part the body takes them from it (params->rdt, tbox, ...)
+    int xstart, xstop, ystart, ystop;
+    nemo::TracerFields f;
+    const double *const *c_in;
+    double *const *c_out;
+    int ntracers;
+};
+struct NemoDmStep {
+    const char *who;             // the entry's name, in front of every refusal
+    const NemoFlow *flow;        // NULL: tracers only
+    const NemoTracers *tracers;  // NULL: the flow step only
+    int depth_lo, depth_hi;      // the halo depths a plan with messages may exchange
+    // the aggregated buffers of all the fields are made before join_pending, so that a stream capture is refused there and
+    // not in the exchange.  Only the coupled entry does, as it always has ("One body")
+    bool agg_early;
+};
+
+typedef int (*tracer_entry)(double, int, int, int, int, int, int, const int *, const double *, const double *, const double *,
+                            const double *, const double *, const double *, const double *, const double *, const double *,
+                            const double *, const double *const *, double *const *, int, void *);
+static const tracer_entry tracer_entries[3] = {dlesm_tracer_step_f64, dlesm_tracer_step_muscl_f64, dlesm_tracer_step_hancock_f64};
+
+// the single-domain work, through the public entries (a refusal of theirs names them): the step, then the tracer sweep
+static int nemolite_single_domain(const NemoFlow *fl, const NemoTracers &t, int ld, int ny, void *stream)
 {
+    if (fl)
+        if (int rc = dlesm_nemolite_step_wet_f64(fl->wet, fl->params, fl->grid, fl->area_t, ld, ny, fl->tbox, fl->ubox, fl->vbox,
+                                                 fl->obc, fl->ssh_bc, fl->un, fl->vn, fl->ht, fl->hu, fl->hv, fl->sshn_t,
+                                                 fl->sshn_u, fl->sshn_v, fl->ssha, fl->ssha_u, fl->ssha_v, fl->ua, fl->va, stream))
+            return rc;
+    if (t.ntracers == 0) return DLESM_OK;
+    return tracer_entries[t.scheme](t.rdt, ld, ny, t.xstart, t.xstop, t.ystart, t.ystop, t.f.tmask, t.f.area_t, t.f.un, t.f.vn,
+                                    t.f.hu, t.f.hv, t.f.ht, t.f.sshn_t, t.f.sshn_u, t.f.sshn_v, t.f.ssha, t.c_in, t.c_out,
+                                    t.ntracers, stream);
+}
+
+// the ring cells of tbox that the plan's receive messages write (RingRects above)
+static int ssha_ring_rects(const char *who, const dlesm_halo_plan *p, const dlesm_region *tbox, RingRects &r)
+{
+    if (nemo::empty(tbox)) return DLESM_OK;
+    const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
+    const nemo::Box ring[2] = {{x1 + 1, x1 + 1, y0, y1}, {x0, x1, y1 + 1, y1 + 1}};   // east column, north row
+    for (const Msg &m : p->recvs)
+        for (const nemo::Box &b : ring) {
+            const int a0 = std::max(b.x0, m.i0), a1 = std::min(b.x1, m.i0 + m.nx - 1);
+            const int c0 = std::max(b.y0, m.j0), c1 = std::min(b.y1, m.j0 + m.ny - 1);
+            if (a0 > a1 || c0 > c1) continue;
+            DLESM_REQUIRE(r.n < RingRects::MAX, "%s: more than %d receive strips border the box", who, RingRects::MAX);
+            r.x0[r.n] = a0, r.x1[r.n] = a1, r.y0[r.n] = c0, r.y1[r.n] = c1;
+            r.n++;
+        }
+    return DLESM_OK;
+}
+
+// ssha on the ring cells the neighbours send
+static int ssha_ring_launch(const RingRects &r, const NemoFlow &fl, int ld, hipStream_t s)
+{
+    if (!r.n) return DLESM_OK;
+    int most = 0;
+    for (int k = 0; k < r.n; k++) most = std::max(most, (r.x1[k] - r.x0[k] + 1) * (r.y1[k] - r.y0[k] + 1));
+    const unsigned gx = (unsigned)std::min((most + 255) / 256, 64);
+    hipLaunchKernelGGL(nemolite_ssha_ring, dim3(gx, r.n), dim3(256), 0, s, r, fl.params->rdt, ld, fl.sshn_t, fl.sshn_u, fl.sshn_v,
+                       fl.hu, fl.hv, fl.un, fl.vn, fl.area_t, fl.ssha);
+    DLESM_HIP_TRY(hipGetLastError());
+    return DLESM_OK;
+}
+
+// true: the exchange goes over the plan's connected mailboxes (always in mailbox mode), in turns of at most peer_fcap fields
+static bool exchange_over_mailboxes(const dlesm_halo_plan *p)
+{
+    return p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
+}
+
+// ONE exchange of nf fields; over mailboxes ceil(nf / turn) mailbox operations per call on every rank -- nothing rank-local
+// (obc, the wet plan, the path the step takes, the box) changes that number; over RCCL (turn == nf) one aggregated group
+static int exchange_in_turns(dlesm_halo_plan *p, double *const *fields, int nf, int turn, hipStream_t s)
+{
+    for (int k = 0; k < nf; k += turn)
+        if (int rc = exchange_on(p, fields + k, std::min(turn, nf - k), DLESM_DIRS_ALL, s)) return rc;
+    return DLESM_OK;
+}
+
+static int nemolite_dm_step(const NemoDmStep &d, dlesm_halo_plan *p, int ld, int ny, void *stream)
+{
+    const char *const who = d.who;
+    const NemoFlow *const fl = d.flow;
     clear_error();
     DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
     if (int rc = ensure_device()) return rc;
-    if (int rc = nemo::step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t,
-                                  sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va))
-        return rc;
-    if (int rc = nemo::wet_check(who, wet, ld, ny, tbox)) return rc;
-    const bool comms = !p->sends.empty() || !p->recvs.empty();
-    auto step = [&] {         // (wet == NULL: dlesm_nemolite_step_f64)
-        return dlesm_nemolite_step_wet_f64(wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv,
-                                           sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
-    };
-    if (!comms) return step();       // no neighbour: the single-domain entry, bit for bit
+
+    // ---- the arguments: the checks of the single-domain entries under the entry's own name, and what a coupled step adds
+    if (fl) {
+        if (int rc = nemo::step_check(who, fl->params, fl->grid, fl->area_t, ld, ny, fl->tbox, fl->ubox, fl->vbox, fl->obc, fl->un,
+                                      fl->vn, fl->ht, fl->hu, fl->hv, fl->sshn_t, fl->sshn_u, fl->sshn_v, fl->ssha, fl->ssha_u,
+                                      fl->ssha_v, fl->ua, fl->va))
+            return rc;
+        if (int rc = nemo::wet_check(who, fl->wet, ld, ny, fl->tbox)) return rc;
+    }
+    NemoTracers t{};
+    if (d.tracers) t = *d.tracers;
+    if (fl && d.tracers) {
+        DLESM_REQUIRE(t.scheme >= DLESM_TRACER_UPWIND && t.scheme <= DLESM_TRACER_HANCOCK,
+                      "%s: scheme %d (0 upwind, 1 MUSCL, 2 Hancock)", who, t.scheme);
+        DLESM_REQUIRE(t.ntracers >= 0 && t.ntracers <= DLESM_TRACER_MAX, "%s: %d tracers (0..%d)", who, t.ntracers,
+                      DLESM_TRACER_MAX);
+        // the sweep runs over tbox with params->rdt, on the level-n fields and the ssha the step makes
+        t.rdt = fl->params->rdt;
+        t.xstart = fl->tbox->xstart, t.xstop = fl->tbox->xstop, t.ystart = fl->tbox->ystart, t.ystop = fl->tbox->ystop;
+        t.f = {fl->grid->tmask, fl->area_t, fl->un, fl->vn, fl->hu, fl->hv, fl->ht, fl->sshn_t, fl->sshn_u, fl->sshn_v, fl->ssha};
+    }
+    if (!fl || t.ntracers > 0)       // (tracers only: 1..8 tracers; a coupled step may carry none)
+        if (int rc = nemo::tracer_check(who, ld, ny, t.xstart, t.xstop, t.ystart, t.ystop, t.f, t.c_in, t.c_out, t.ntracers))
+            return rc;
+    if (fl && t.ntracers > 0) {
+        // what tracer_check does not know of: the step's other four outputs and the arrays of the grid
+        const double *const more[14] = {fl->ssha_u, fl->ssha_v, fl->ua, fl->va, fl->grid->dx_t, fl->grid->dy_t, fl->grid->dx_u,
+                                        fl->grid->dy_u, fl->grid->dx_v, fl->grid->dy_v, fl->grid->area_u, fl->grid->area_v,
+                                        fl->grid->fcor_u, fl->grid->fcor_v};
+        static const char *const more_name[14] = {"ssha_u", "ssha_v", "ua", "va", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v",
+                                                  "dy_v", "area_u", "area_v", "fcor_u", "fcor_v"};
+        const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
+        for (int k = 0; k < t.ntracers; k++)
+            for (int m = 0; m < 14; m++)
+                DLESM_REQUIRE(!nemo::overlap(t.c_out[k], nb, more[m], nb), "%s: c_out[%d] overlaps %s", who, k, more_name[m]);
+    }
+    if (p->sends.empty() && p->recvs.empty())        // no neighbour: the single-domain entries, bit for bit
+        return nemolite_single_domain(fl, t, ld, ny, stream);
 
     // ---- every refusal of a plan with messages, before anything is launched or exchanged
     DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
                   "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
+    int depth = 0;
     for (const Msg &m : p->recvs) {
         const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
         const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
         if (!xdir && !ydir) continue;
-        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 1, "%s: the plan exchanges depth-%d halos, the step needs depth 1 "
-                      "(a grid decomposed with halo_width = 1)", who, xdir ? m.nx : m.ny);
+        const int dm = xdir ? m.nx : m.ny;
+        if (d.depth_lo == d.depth_hi)
+            DLESM_REQUIRE(dm == d.depth_lo, "%s: the plan exchanges depth-%d halos, the step needs depth %d "
+                          "(a grid decomposed with halo_width = %d)", who, dm, d.depth_lo, d.depth_lo);
+        else
+            DLESM_REQUIRE(dm >= d.depth_lo && dm <= d.depth_hi, "%s: the plan exchanges depth-%d halos, the step needs depth "
+                          "%d or %d (a grid decomposed with halo_width = %d or %d)", who, dm, d.depth_lo, d.depth_hi, d.depth_lo,
+                          d.depth_hi);
+        DLESM_REQUIRE(depth == 0 || dm == depth, "%s: the plan mixes depth-%d and depth-%d halos", who, depth, dm);
+        depth = dm;
     }
-    DLESM_REQUIRE(nemo::same_box(tbox, ubox) && nemo::same_box(tbox, vbox),
-                  "%s: on a decomposed grid the T, U and V boxes must be one box (every NE grid): T (%d:%d,%d:%d), "
-                  "U (%d:%d,%d:%d), V (%d:%d,%d:%d)", who, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, ubox->xstart,
-                  ubox->xstop, ubox->ystart, ubox->ystop, vbox->xstart, vbox->xstop, vbox->ystart, vbox->ystop);
+    DLESM_REQUIRE(t.ntracers == 0 || t.scheme == DLESM_TRACER_UPWIND || depth != 1,
+                  "%s: the plan exchanges depth-1 halos, the limited tracer schemes need depth 2 (a grid decomposed with "
+                  "halo_width = 2)", who);
+    if (fl)
+        DLESM_REQUIRE(nemo::same_box(fl->tbox, fl->ubox) && nemo::same_box(fl->tbox, fl->vbox),
+                      "%s: on a decomposed grid the T, U and V boxes must be one box (every NE grid): T (%d:%d,%d:%d), "
+                      "U (%d:%d,%d:%d), V (%d:%d,%d:%d)", who, fl->tbox->xstart, fl->tbox->xstop, fl->tbox->ystart,
+                      fl->tbox->ystop, fl->ubox->xstart, fl->ubox->xstop, fl->ubox->ystart, fl->ubox->ystop, fl->vbox->xstart,
+                      fl->vbox->xstop, fl->vbox->ystart, fl->vbox->ystop);
     DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
     RingRects r{};
-    if (!nemo::empty(tbox)) {
-        const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
-        const nemo::Box ring[2] = {{x1 + 1, x1 + 1, y0, y1}, {x0, x1, y1 + 1, y1 + 1}};   // east column, north row
-        for (const Msg &m : p->recvs)
-            for (const nemo::Box &b : ring) {
-                const int a0 = std::max(b.x0, m.i0), a1 = std::min(b.x1, m.i0 + m.nx - 1);
-                const int c0 = std::max(b.y0, m.j0), c1 = std::min(b.y1, m.j0 + m.ny - 1);
-                if (a0 > a1 || c0 > c1) continue;
-                DLESM_REQUIRE(r.n < RingRects::MAX, "%s: more than %d receive strips border the box", who, RingRects::MAX);
-                r.x0[r.n] = a0, r.x1[r.n] = a1, r.y0[r.n] = c0, r.y1[r.n] = c1;
-                r.n++;
-            }
-    }
+    if (fl)
+        if (int rc = ssha_ring_rects(who, p, fl->tbox, r)) return rc;
+
     hipStream_t s = (hipStream_t)stream;
-    double *const outs[5] = {ssha, ssha_u, ssha_v, ua, va};
-    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil(5 / peer_fcap) mailbox
-    // operations per call on every rank -- nothing rank-local (obc, the path step 2 takes, the box) changes that number
-    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
-    const int turn = mailbox ? p->peer_fcap : 5;
+    int nf = 0;
+    double *outs[5 + DLESM_TRACER_MAX];
+    if (fl)
+        for (double *o : {fl->ssha, fl->ssha_u, fl->ssha_v, fl->ua, fl->va}) outs[nf++] = o;
+    for (int k = 0; k < t.ntracers; k++) outs[nf++] = t.c_out[k];
+    const bool mailbox = exchange_over_mailboxes(p);
     if (int rc = capture_ok(p, s, mailbox)) return rc;
+    if (d.agg_early && !mailbox && tuning("dm_aggregate", 1))
+        if (int rc = ensure_agg(p, nf, s)) return rc;
     if (int rc = join_pending(p, s)) return rc;
 
-    // 1. ssha on the ring cells the neighbours send
-    if (r.n) {
-        int most = 0;
-        for (int k = 0; k < r.n; k++) most = std::max(most, (r.x1[k] - r.x0[k] + 1) * (r.y1[k] - r.y0[k] + 1));
-        const unsigned gx = (unsigned)std::min((most + 255) / 256, 64);
-        hipLaunchKernelGGL(nemolite_ssha_ring, dim3(gx, r.n), dim3(256), 0, s, r, params->rdt, ld, sshn_t, sshn_u, sshn_v, hu,
-                           hv, un, vn, area_t, ssha);
-        DLESM_HIP_TRY(hipGetLastError());
-    }
-    // 2. the single-domain step: the sweep, or the five entries, then bc_open
-    if (int rc = step()) return rc;
-    // 3. one exchange of the five outputs (mailboxes: in turns of peer_fcap fields)
-    for (int k = 0; k < 5; k += turn)
-        if (int rc = exchange_on(p, outs + k, std::min(turn, 5 - k), DLESM_DIRS_ALL, s)) return rc;
-    return DLESM_OK;
+    // 1. ssha on the ring cells the neighbours send; 2. the single-domain step: the sweep, or the five entries, then bc_open;
+    // 3. the tracer sweep, carried by the level-n transports into the new water column; 4. one exchange of all the outputs
+    if (fl)
+        if (int rc = ssha_ring_launch(r, *fl, ld, s)) return rc;
+    if (int rc = nemolite_single_domain(fl, t, ld, ny, stream)) return rc;
+    return exchange_in_turns(p, outs, nf, mailbox ? p->peer_fcap : nf, s);
 }
 
 extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_params *params, const dlesm_momentum_grid *grid,
@@ -1956,10 +2078,12 @@ extern "C" int dlesm_nemolite_step_dm(dlesm_halo_plan *p, const dlesm_momentum_p
                                       const double *sshn_t, const double *sshn_u, const double *sshn_v, double *ssha,
                                       double *ssha_u, double *ssha_v, double *ua, double *va, void *stream)
 {
-    return nemolite_step_dm_impl("dlesm_nemolite_step_dm", p, nullptr, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc,
-                                 ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+    const NemoFlow fl{nullptr, params, grid, area_t, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v,
+                      ssha, ssha_u, ssha_v, ua, va};
+    return nemolite_dm_step({"dlesm_nemolite_step_dm", &fl, nullptr, 1, 1, false}, p, ld, ny, stream);
 }
 
+// the wet plan only reaches the single-domain step
 extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_plan *wet, const dlesm_momentum_params *params,
                                           const dlesm_momentum_grid *grid, const double *area_t, int ld, int ny,
                                           const dlesm_region *tbox, const dlesm_region *ubox, const dlesm_region *vbox,
@@ -1968,66 +2092,23 @@ extern "C" int dlesm_nemolite_step_wet_dm(dlesm_halo_plan *p, const dlesm_wet_pl
                                           const double *sshn_u, const double *sshn_v, double *ssha, double *ssha_u,
                                           double *ssha_v, double *ua, double *va, void *stream)
 {
-    return nemolite_step_dm_impl("dlesm_nemolite_step_wet_dm", p, wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc,
-                                 ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
+    const NemoFlow fl{wet, params, grid, area_t, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v,
+                      ssha, ssha_u, ssha_v, ua, va};
+    return nemolite_dm_step({"dlesm_nemolite_step_wet_dm", &fl, nullptr, 1, 1, false}, p, ld, ny, stream);
 }
 
-// Tracer transport on a decomposed grid (DESIGN.md sections 6.10, 6.11 and 6.12): the single-domain sweep, then ONE exchange of the
-// new tracers -- `entry` followed by dlesm_halo_exchange_multi_f64, with dlesm_nemolite_step_dm's guards and its rule for the
-// mailbox turns.  `depth` is the halo depth a plan with messages must exchange: 1 for the upwind sweep, 2 for the two limited ones.
-typedef int (*tracer_entry)(double, int, int, int, int, int, int, const int *, const double *, const double *, const double *,
-                            const double *, const double *, const double *, const double *, const double *, const double *,
-                            const double *, const double *const *, double *const *, int, void *);
-static int tracer_step_dm_impl(const char *who, tracer_entry entry, int depth, dlesm_halo_plan *p, double rdt, int ld, int ny,
-                               int xstart, int xstop, int ystart, int ystop, const int *tmask, const double *area_t,
-                               const double *un, const double *vn, const double *hu, const double *hv, const double *ht,
-                               const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
-                               const double *const *c_in, double *const *c_out, int ntracers, void *stream)
-{
-    clear_error();
-    DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
-    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
-    if (int rc = ensure_device()) return rc;
-    const nemo::TracerFields f{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
-    if (int rc = nemo::tracer_check(who, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers)) return rc;
-    auto step = [&] {
-        return entry(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha,
-                     c_in, c_out, ntracers, stream);
-    };
-    if (p->sends.empty() && p->recvs.empty()) return step();     // no neighbour: the single-domain entry, bit for bit
-
-    // ---- every refusal of a plan with messages, before anything is launched or exchanged
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
-    for (const Msg &m : p->recvs) {
-        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
-        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
-        if (!xdir && !ydir) continue;
-        DLESM_REQUIRE((xdir ? m.nx : m.ny) == depth, "%s: the plan exchanges depth-%d halos, the step needs depth %d "
-                      "(a grid decomposed with halo_width = %d)", who, xdir ? m.nx : m.ny, depth, depth);
-    }
-    DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
-    hipStream_t s = (hipStream_t)stream;
-    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil(ntracers / peer_fcap) mailbox
-    // operations per call on every rank, whatever the box
-    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
-    const int turn = mailbox ? p->peer_fcap : ntracers;
-    if (int rc = capture_ok(p, s, mailbox)) return rc;
-    if (int rc = join_pending(p, s)) return rc;
-    if (int rc = step()) return rc;
-    for (int k = 0; k < ntracers; k += turn)
-        if (int rc = exchange_on(p, c_out + k, std::min(turn, ntracers - k), DLESM_DIRS_ALL, s)) return rc;
-    return DLESM_OK;
-}
-
+// Tracer transport on a decomposed grid (DESIGN.md sections 6.10, 6.11 and 6.12): the single-domain sweep, then ONE exchange of
+// the new tracers -- the entry of the scheme followed by dlesm_halo_exchange_multi_f64.  A plan with messages must exchange
+// depth 1 for the upwind sweep, depth 2 for the two limited ones.
 extern "C" int dlesm_tracer_step_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
                                     int ystop, const int *tmask, const double *area_t, const double *un, const double *vn,
                                     const double *hu, const double *hv, const double *ht, const double *sshn_t,
                                     const double *sshn_u, const double *sshn_v, const double *ssha,
                                     const double *const *c_in, double *const *c_out, int ntracers, void *stream)
 {
-    return tracer_step_dm_impl("dlesm_tracer_step_dm", dlesm_tracer_step_f64, 1, p, rdt, ld, ny, xstart, xstop, ystart, ystop,
-                               tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
+    const NemoTracers t{DLESM_TRACER_UPWIND, rdt, xstart, xstop, ystart, ystop,
+                        {tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha}, c_in, c_out, ntracers};
+    return nemolite_dm_step({"dlesm_tracer_step_dm", nullptr, &t, 1, 1, false}, p, ld, ny, stream);
 }
 
 extern "C" int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
@@ -2037,9 +2118,9 @@ extern "C" int dlesm_tracer_step_muscl_dm(dlesm_halo_plan *p, double rdt, int ld
                                           const double *ssha, const double *const *c_in, double *const *c_out, int ntracers,
                                           void *stream)
 {
-    return tracer_step_dm_impl("dlesm_tracer_step_muscl_dm", dlesm_tracer_step_muscl_f64, 2, p, rdt, ld, ny, xstart, xstop,
-                               ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
-                               ntracers, stream);
+    const NemoTracers t{DLESM_TRACER_MUSCL, rdt, xstart, xstop, ystart, ystop,
+                        {tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha}, c_in, c_out, ntracers};
+    return nemolite_dm_step({"dlesm_tracer_step_muscl_dm", nullptr, &t, 2, 2, false}, p, ld, ny, stream);
 }
 
 extern "C" int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *p, double rdt, int ld, int ny, int xstart, int xstop, int ystart,
@@ -2049,9 +2130,9 @@ extern "C" int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *p, double rdt, int 
                                             const double *ssha, const double *const *c_in, double *const *c_out,
                                             int ntracers, void *stream)
 {
-    return tracer_step_dm_impl("dlesm_tracer_step_hancock_dm", dlesm_tracer_step_hancock_f64, 2, p, rdt, ld, ny, xstart, xstop,
-                               ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out,
-                               ntracers, stream);
+    const NemoTracers t{DLESM_TRACER_HANCOCK, rdt, xstart, xstop, ystart, ystop,
+                        {tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha}, c_in, c_out, ntracers};
+    return nemolite_dm_step({"dlesm_tracer_step_hancock_dm", nullptr, &t, 2, 2, false}, p, ld, ny, stream);
 }
 
 // One coupled NEMOLite2D-class time step on a decomposed grid (dlesm_nemolite_coupled_step_dm): the
@@ -2069,114 +2150,10 @@ extern "C" int dlesm_nemolite_coupled_step_dm(dlesm_halo_plan *p, const dlesm_we
                                               double *va, const double *const *c_in, double *const *c_out, int ntracers,
                                               void *stream)
 {
-    static const char *const who = "dlesm_nemolite_coupled_step_dm";
-    static const tracer_entry entries[3] = {dlesm_tracer_step_f64, dlesm_tracer_step_muscl_f64, dlesm_tracer_step_hancock_f64};
-    clear_error();
-    DLESM_REQUIRE(p != nullptr, "%s: null plan", who);
-    DLESM_REQUIRE(p->ld == ld && p->ny == ny, "%s: the plan is for %dx%d fields, got %dx%d", who, p->ld, p->ny, ld, ny);
-    if (int rc = ensure_device()) return rc;
-    if (int rc = nemo::step_check(who, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, un, vn, ht, hu, hv, sshn_t,
-                                  sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va))
-        return rc;
-    if (int rc = nemo::wet_check(who, wet, ld, ny, tbox)) return rc;
-    DLESM_REQUIRE(scheme >= DLESM_TRACER_UPWIND && scheme <= DLESM_TRACER_HANCOCK,
-                  "%s: scheme %d (0 upwind, 1 MUSCL, 2 Hancock)", who, scheme);
-    DLESM_REQUIRE(ntracers >= 0 && ntracers <= DLESM_TRACER_MAX, "%s: %d tracers (0..%d)", who, ntracers, DLESM_TRACER_MAX);
-    if (ntracers > 0) {
-        const nemo::TracerFields f{grid->tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha};
-        if (int rc = nemo::tracer_check(who, ld, ny, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, f, c_in, c_out,
-                                        ntracers))
-            return rc;
-        // what tracer_check does not know of: the step's other four outputs and the arrays of the grid
-        const double *const more[14] = {ssha_u, ssha_v, ua, va, grid->dx_t, grid->dy_t, grid->dx_u, grid->dy_u, grid->dx_v,
-                                        grid->dy_v, grid->area_u, grid->area_v, grid->fcor_u, grid->fcor_v};
-        static const char *const more_name[14] = {"ssha_u", "ssha_v", "ua", "va", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v",
-                                                  "dy_v", "area_u", "area_v", "fcor_u", "fcor_v"};
-        const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
-        for (int k = 0; k < ntracers; k++)
-            for (int m = 0; m < 14; m++)
-                DLESM_REQUIRE(!nemo::overlap(c_out[k], nb, more[m], nb), "%s: c_out[%d] overlaps %s", who, k, more_name[m]);
-    }
-    auto step = [&] {         // (wet == NULL: dlesm_nemolite_step_f64)
-        return dlesm_nemolite_step_wet_f64(wet, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv,
-                                           sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, stream);
-    };
-    auto tracers = [&] {
-        if (ntracers == 0) return (int)DLESM_OK;
-        return entries[scheme](params->rdt, ld, ny, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, grid->tmask, area_t,
-                               un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha, c_in, c_out, ntracers, stream);
-    };
-    if (p->sends.empty() && p->recvs.empty()) {      // no neighbour: the two single-domain entries, bit for bit
-        if (int rc = step()) return rc;
-        return tracers();
-    }
-
-    // ---- every refusal of a plan with messages, before anything is launched or exchanged
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "%s: an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)", who);
-    int depth = 0;
-    for (const Msg &m : p->recvs) {
-        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
-        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
-        if (!xdir && !ydir) continue;
-        const int d = xdir ? m.nx : m.ny;
-        DLESM_REQUIRE(d == 1 || d == 2, "%s: the plan exchanges depth-%d halos, the step needs depth 1 or 2 (a grid "
-                      "decomposed with halo_width = 1 or 2)", who, d);
-        DLESM_REQUIRE(depth == 0 || d == depth, "%s: the plan mixes depth-%d and depth-%d halos", who, depth, d);
-        depth = d;
-    }
-    DLESM_REQUIRE(ntracers == 0 || scheme == DLESM_TRACER_UPWIND || depth != 1,
-                  "%s: the plan exchanges depth-1 halos, the limited tracer schemes need depth 2 (a grid decomposed with "
-                  "halo_width = 2)", who);
-    DLESM_REQUIRE(nemo::same_box(tbox, ubox) && nemo::same_box(tbox, vbox),
-                  "%s: on a decomposed grid the T, U and V boxes must be one box (every NE grid): T (%d:%d,%d:%d), "
-                  "U (%d:%d,%d:%d), V (%d:%d,%d:%d)", who, tbox->xstart, tbox->xstop, tbox->ystart, tbox->ystop, ubox->xstart,
-                  ubox->xstop, ubox->ystart, ubox->ystop, vbox->xstart, vbox->xstop, vbox->ystart, vbox->ystop);
-    DLESM_REQUIRE(!g_mailbox || p->peer_on, "%s: mailbox mode, and the plan's mailboxes are not connected", who);
-    RingRects r{};
-    if (!nemo::empty(tbox)) {
-        const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
-        const nemo::Box ring[2] = {{x1 + 1, x1 + 1, y0, y1}, {x0, x1, y1 + 1, y1 + 1}};   // east column, north row
-        for (const Msg &m : p->recvs)
-            for (const nemo::Box &b : ring) {
-                const int a0 = std::max(b.x0, m.i0), a1 = std::min(b.x1, m.i0 + m.nx - 1);
-                const int c0 = std::max(b.y0, m.j0), c1 = std::min(b.y1, m.j0 + m.ny - 1);
-                if (a0 > a1 || c0 > c1) continue;
-                DLESM_REQUIRE(r.n < RingRects::MAX, "%s: more than %d receive strips border the box", who, RingRects::MAX);
-                r.x0[r.n] = a0, r.x1[r.n] = a1, r.y0[r.n] = c0, r.y1[r.n] = c1;
-                r.n++;
-            }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int nf = 5 + ntracers;
-    double *outs[5 + DLESM_TRACER_MAX] = {ssha, ssha_u, ssha_v, ua, va};
-    for (int k = 0; k < ntracers; k++) outs[5 + k] = c_out[k];
-    // over connected mailboxes (always in mailbox mode): turns of at most peer_fcap fields, ceil((5 + ntracers) / peer_fcap)
-    // mailbox operations per call on every rank -- nothing rank-local (obc, the wet plan, the path the step takes, the box)
-    // changes that number; over RCCL one aggregated group
-    const bool mailbox = p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
-    const int turn = mailbox ? p->peer_fcap : nf;
-    if (int rc = capture_ok(p, s, mailbox)) return rc;
-    if (!mailbox && tuning("dm_aggregate", 1))       // (the buffers of 5 + ntracers fields: a capture is refused here, not later)
-        if (int rc = ensure_agg(p, nf, s)) return rc;
-    if (int rc = join_pending(p, s)) return rc;
-
-    // 1. ssha on the ring cells the neighbours send
-    if (r.n) {
-        int most = 0;
-        for (int k = 0; k < r.n; k++) most = std::max(most, (r.x1[k] - r.x0[k] + 1) * (r.y1[k] - r.y0[k] + 1));
-        const unsigned gx = (unsigned)std::min((most + 255) / 256, 64);
-        hipLaunchKernelGGL(nemolite_ssha_ring, dim3(gx, r.n), dim3(256), 0, s, r, params->rdt, ld, sshn_t, sshn_u, sshn_v, hu,
-                           hv, un, vn, area_t, ssha);
-        DLESM_HIP_TRY(hipGetLastError());
-    }
-    // 2. the single-domain step; 3. the tracer sweep, carried by the level-n transports into the new water column
-    if (int rc = step()) return rc;
-    if (int rc = tracers()) return rc;
-    // 4. one exchange of the 5 + ntracers outputs (mailboxes: in turns of peer_fcap fields)
-    for (int k = 0; k < nf; k += turn)
-        if (int rc = exchange_on(p, outs + k, std::min(turn, nf - k), DLESM_DIRS_ALL, s)) return rc;
-    return DLESM_OK;
+    const NemoFlow fl{wet, params, grid, area_t, tbox, ubox, vbox, obc, ssh_bc, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v,
+                      ssha, ssha_u, ssha_v, ua, va};
+    const NemoTracers t{scheme, 0.0, 0, 0, 0, 0, {}, c_in, c_out, ntracers};
+    return nemolite_dm_step({"dlesm_nemolite_coupled_step_dm", &fl, &t, 1, 2, true}, p, ld, ny, stream);
 }
 
 // The halos of ONE int field from the neighbours (dlesm_halo_exchange_i32) -- the T mask of a grid

@@ -275,16 +275,45 @@ def invoke_nemolite_step_dm(params, ssha, ssha_u, ssha_v, ua, va, un, vn, ht, hu
         check(_cabi.lib().dlesm_nemolite_step_dm(grid_mod.halo_plan(g), *args))
 
 
-def _tracer_args(who, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream):
+def _tracer_ptrs(who, c_out, c_in):
+    """the pointer arrays of the tracers, c_in's and c_out's, and their number"""
     c_out, c_in = list(c_out), list(c_in)
     if len(c_out) != len(c_in):
         raise _cabi.DlesmError(_cabi.EINVAL, "%s: %d output fields for %d tracers" % (who, len(c_out), len(c_in)))
-    g, it = ssha.grid, ssha.internal
     n = len(c_in)
-    pin, pout = (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_in]), (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_out])
+    return (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_in]), (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_out]), n
+
+
+def _tracer_args(who, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream):
+    pin, pout, n = _tracer_ptrs(who, c_out, c_in)
+    g, it = ssha.grid, ssha.internal
     return (float(rdt), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
             C.c_void_p(g.area_t_device.data_ptr()), *[f.device_ptr for f in (un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha)],
             pin, pout, n, _stream_ptr(stream))
+
+
+_TRACER_HALO_STOP = {1: "%s: the grid has halo_width %d; the step exchanges depth-1 halos: decompose the grid with halo_width = 1",
+                     2: "%s: the grid has halo_width %d; the step reads two cells and exchanges depth-2 halos: decompose the "
+                        "grid with halo_width = 2"}
+
+
+def _tracer_step(who, entry, halo_width, rdt, c_out, c_in, ssha, *flow, stream=None):
+    """the body of the six invoke_tracer_step* wrappers: `who` in front of every stop, the C entry `entry`, and the halo width
+    a decomposed grid must have (None: the single-domain wrapper, which stops on a decomposed grid)"""
+    g = ssha.grid
+    if halo_width is None:
+        if g.decomp is not None and g.decomp.ndomains > 1:
+            raise _cabi.GoceanStop(_cabi.EABORT, "%s: the grid is decomposed (%d subdomains): the new tracers need a halo "
+                                                 "exchange; use %s_dm" % (who, g.decomp.ndomains, who))
+        plan = ()
+    else:
+        hw = getattr(g, "halo_width", 1)
+        if hw != halo_width:
+            raise _cabi.GoceanStop(_cabi.EABORT, _TRACER_HALO_STOP[halo_width] % (who, hw))
+        if getattr(g, "comm_tables", None) is None:
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: the grid has no message tables (grid_init after decompose)" % who)
+        plan = (grid_mod.halo_plan(g),)
+    check(getattr(_cabi.lib(), entry)(*plan, *_tracer_args(who, rdt, c_out, c_in, ssha, *flow, stream)))
 
 
 def invoke_tracer_step(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
@@ -292,42 +321,24 @@ def invoke_tracer_step(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_
     continuity's face transports of level n (un, vn, hu, hv, sshn_u, sshn_v), from the water column ht + sshn_t to ht + ssha,
     over the T internal region, on wet cells only.  c_out and c_in are lists of T-point fields; ssha is what the time step
     made from the same level-n inputs.  Single domain: stops on a decomposed grid."""
-    g = ssha.grid
-    if g.decomp is not None and g.decomp.ndomains > 1:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step: the grid is decomposed (%d subdomains): the new tracers "
-                                             "need a halo exchange; use invoke_tracer_step_dm" % g.decomp.ndomains)
-    check(_cabi.lib().dlesm_tracer_step_f64(*_tracer_args("invoke_tracer_step", rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
-                                                          sshn_t, sshn_u, sshn_v, stream)))
+    _tracer_step("invoke_tracer_step", "dlesm_tracer_step_f64", None, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u,
+                 sshn_v, stream=stream)
 
 
 def invoke_tracer_step_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
     """invoke_tracer_step and ONE exchange of the new tracers on a decomposed grid (dlesm_tracer_step_dm, DESIGN.md section
     6.10), bit for bit invoke_tracer_step -> halo_exchange_multi(c_out).  The flow fields and c_in need valid depth-1 halos;
     c_out leaves with them.  Collective.  Stops on a grid with halo_width other than 1."""
-    g = ssha.grid
-    hw = getattr(g, "halo_width", 1)
-    if hw != 1:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_dm: the grid has halo_width %d; the step exchanges depth-1 "
-                                             "halos: decompose the grid with halo_width = 1" % hw)
-    if getattr(g, "comm_tables", None) is None:
-        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_dm: the grid has no message tables (grid_init after "
-                                             "decompose)")
-    check(_cabi.lib().dlesm_tracer_step_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_dm", rdt, c_out, c_in, ssha,
-                                                                                 un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v,
-                                                                                 stream)))
+    _tracer_step("invoke_tracer_step_dm", "dlesm_tracer_step_dm", 1, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u,
+                 sshn_v, stream=stream)
 
 
 def invoke_tracer_step_muscl(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
     """invoke_tracer_step with second-order limited face values (dlesm_tracer_step_muscl_f64): the
     upwind cell's monotonised-central slope rebuilds what a face carries; land, open cells and cells next to land keep the
     upwind value.  Same arguments and rules.  Single domain: stops on a decomposed grid."""
-    g = ssha.grid
-    if g.decomp is not None and g.decomp.ndomains > 1:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_muscl: the grid is decomposed (%d subdomains): the new "
-                                             "tracers need a halo exchange; use invoke_tracer_step_muscl_dm"
-                               % g.decomp.ndomains)
-    check(_cabi.lib().dlesm_tracer_step_muscl_f64(*_tracer_args("invoke_tracer_step_muscl", rdt, c_out, c_in, ssha, un, vn, ht,
-                                                                hu, hv, sshn_t, sshn_u, sshn_v, stream)))
+    _tracer_step("invoke_tracer_step_muscl", "dlesm_tracer_step_muscl_f64", None, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
+                 sshn_t, sshn_u, sshn_v, stream=stream)
 
 
 def invoke_tracer_step_muscl_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
@@ -335,30 +346,16 @@ def invoke_tracer_step_muscl_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn
     DESIGN.md section 6.11), bit for bit invoke_tracer_step_muscl -> halo_exchange_multi(c_out).  The grid's mask and c_in
     need valid depth-2 halos, the flow fields depth-1 halos; c_out leaves with depth-2 halos.  Collective.  Stops on a grid
     with halo_width other than 2."""
-    g = ssha.grid
-    hw = getattr(g, "halo_width", 1)
-    if hw != 2:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_muscl_dm: the grid has halo_width %d; the step reads two "
-                                             "cells and exchanges depth-2 halos: decompose the grid with halo_width = 2" % hw)
-    if getattr(g, "comm_tables", None) is None:
-        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_muscl_dm: the grid has no message tables (grid_init after "
-                                             "decompose)")
-    check(_cabi.lib().dlesm_tracer_step_muscl_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_muscl_dm", rdt, c_out,
-                                                                                       c_in, ssha, un, vn, ht, hu, hv, sshn_t,
-                                                                                       sshn_u, sshn_v, stream)))
+    _tracer_step("invoke_tracer_step_muscl_dm", "dlesm_tracer_step_muscl_dm", 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
+                 sshn_t, sshn_u, sshn_v, stream=stream)
 
 
 def invoke_tracer_step_hancock(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
     """invoke_tracer_step_muscl with time-centred face values (dlesm_tracer_step_hancock_f64): the
     slope's factor 0.5 becomes 0.5 * (1 - n), n the face's Courant number in its upwind cell, 0 where n is not in [0, 1).
     Same arguments and rules.  Single domain: stops on a decomposed grid."""
-    g = ssha.grid
-    if g.decomp is not None and g.decomp.ndomains > 1:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_hancock: the grid is decomposed (%d subdomains): the new "
-                                             "tracers need a halo exchange; use invoke_tracer_step_hancock_dm"
-                               % g.decomp.ndomains)
-    check(_cabi.lib().dlesm_tracer_step_hancock_f64(*_tracer_args("invoke_tracer_step_hancock", rdt, c_out, c_in, ssha, un, vn,
-                                                                  ht, hu, hv, sshn_t, sshn_u, sshn_v, stream)))
+    _tracer_step("invoke_tracer_step_hancock", "dlesm_tracer_step_hancock_f64", None, rdt, c_out, c_in, ssha, un, vn, ht, hu,
+                 hv, sshn_t, sshn_u, sshn_v, stream=stream)
 
 
 def invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, stream=None):
@@ -367,17 +364,8 @@ def invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, ss
     halo_exchange_multi(c_out).  The grid's mask and c_in need valid depth-2 halos, the flow fields depth-1 halos (area_t, ht
     and sshn_t among them: w of the cell beyond the box is built from them); c_out leaves with depth-2 halos.  Collective.
     Stops on a grid with halo_width other than 2."""
-    g = ssha.grid
-    hw = getattr(g, "halo_width", 1)
-    if hw != 2:
-        raise _cabi.GoceanStop(_cabi.EABORT, "invoke_tracer_step_hancock_dm: the grid has halo_width %d; the step reads two "
-                                             "cells and exchanges depth-2 halos: decompose the grid with halo_width = 2" % hw)
-    if getattr(g, "comm_tables", None) is None:
-        raise _cabi.DlesmError(_cabi.EINVAL, "invoke_tracer_step_hancock_dm: the grid has no message tables (grid_init after "
-                                             "decompose)")
-    check(_cabi.lib().dlesm_tracer_step_hancock_dm(grid_mod.halo_plan(g), *_tracer_args("invoke_tracer_step_hancock_dm", rdt,
-                                                                                         c_out, c_in, ssha, un, vn, ht, hu, hv,
-                                                                                         sshn_t, sshn_u, sshn_v, stream)))
+    _tracer_step("invoke_tracer_step_hancock_dm", "dlesm_tracer_step_hancock_dm", 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
+                 sshn_t, sshn_u, sshn_v, stream=stream)
 
 
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
@@ -397,22 +385,18 @@ def invoke_nemolite_coupled_step_dm(params, scheme, c_out, c_in, ssha, ssha_u, s
     g = ssha.grid
     if scheme not in TRACER_SCHEMES:
         raise _cabi.DlesmError(_cabi.EINVAL, "%s: scheme %r (one of %s)" % (who, scheme, ", ".join(TRACER_SCHEMES)))
-    c_out, c_in = list(c_out), list(c_in)
-    if len(c_out) != len(c_in):
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: %d output fields for %d tracers" % (who, len(c_out), len(c_in)))
+    pin, pout, n = _tracer_ptrs(who, c_out, c_in)
     hw = getattr(g, "halo_width", 1)
     if hw not in (1, 2):
         raise _cabi.GoceanStop(_cabi.EABORT, "%s: the grid has halo_width %d; the step exchanges depth-1 or depth-2 halos: "
                                              "decompose the grid with halo_width = 1 or 2" % (who, hw))
-    if hw == 1 and scheme != "upwind" and c_in:
+    if hw == 1 and scheme != "upwind" and n:
         raise _cabi.GoceanStop(_cabi.EABORT, "%s: the grid has halo_width 1; the %s scheme reads two cells and exchanges "
                                              "depth-2 halos: decompose the grid with halo_width = 2" % (who, scheme))
     mg = _momentum_grid(g, who)
     if getattr(g, "comm_tables", None) is None:
         raise _cabi.DlesmError(_cabi.EINVAL, "%s: the grid has no message tables (grid_init after decompose)" % who)
     obc = None if ssh_bc is None else open_boundary(g).handle
-    n = len(c_in)
-    pin, pout = (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_in]), (C.c_void_p * max(n, 1))(*[f.device_ptr for f in c_out])
     check(_cabi.lib().dlesm_nemolite_coupled_step_dm(
         grid_mod.halo_plan(g), wet_plan(g).handle if skip_land else None, TRACER_SCHEMES[scheme], C.byref(params), C.byref(mg),
         C.c_void_p(g.area_t_device.data_ptr()), g.nx, g.ny, C.byref(ssha.internal), C.byref(ua.internal), C.byref(va.internal),

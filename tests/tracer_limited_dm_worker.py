@@ -1,17 +1,22 @@
-"""One rank of the N-process test of second-order limited tracer transport on a decomposed grid (dlesm_tracer_step_muscl_dm
-through psy.invoke_tracer_step_muscl_dm; tests/test_a_tracer_muscl_dm_ranks_gpu.py).  The ranks are separate processes sharing
+"""One rank of the N-process test of limited tracer transport on a decomposed grid, SCHEME = muscl (second order:
+dlesm_tracer_step_muscl_dm through psy.invoke_tracer_step_muscl_dm) or hancock (time-centred: dlesm_tracer_step_hancock_dm
+through psy.invoke_tracer_step_hancock_dm); tests/test_a_tracer_dm_ranks_gpu.py.  The ranks are separate processes sharing
 device 0 in mailbox mode: the decomposition (halo_width = 2) and the depth-2 message tables are the product's own, the blobs
 travel through a gloo group, no RCCL.
 
 Tracer-only steps: the flow is fixed -- random velocities of both signs in x and y over the open channel's mask with an island
 across the tile boundaries, cut from the undivided arrays, so every rank's flow arrays hold valid halos of any depth -- and
-STEPS calls of invoke_tracer_step_muscl_dm carry two tracers, every rank against tests/tracer_muscl_numpy.py run on the
-UNDIVIDED domain.  Checked after every step: every internal cell and every depth-2 halo cell, inside the global array, of both
-tracers, bit for bit.  The mask keeps the undivided domain's ring free of wet cells.  grid_init gives
-the grid's mask its one-cell ring only and replicates it outwards; the entry wants valid depth-2 halos, so each rank sets the
-grid's host mask to its window of the global mask before the device mirror is made.
+STEPS calls of the scheme's wrapper carry two tracers, every rank against tests/tracer_muscl_numpy.py or
+tests/tracer_hancock_numpy.py run on the UNDIVIDED domain.  Checked after every step: every internal cell and every depth-2 halo
+cell, inside the global array, of both tracers, bit for bit.  muscl runs at tracer_cases.RDT.  hancock runs at rdt = 3.0e6,
+which puts more than a tenth of the faces of the undivided domain's wet cells at a Courant number in (0, 1) and more than a
+tenth at 1 or above (asserted on the host), so the factor, its fall-back to the upwind value and w of the cell beyond a tile's
+box -- built from the depth-1 halos of area_t, ht and sshn_t -- are all compared.  The mask keeps the undivided domain's ring
+free of wet cells (DESIGN.md sections 6.11 and 6.12).  grid_init gives the grid's mask its one-cell ring only and replicates it
+outwards; the entries want valid depth-2 halos, so each rank sets the grid's host mask to its window of the global mask before
+the device mirror is made.
 
-    RANK=r WORLD_SIZE=n MASTER_ADDR=127.0.0.1 MASTER_PORT=p python tests/tracer_muscl_dm_worker.py NX NY NDX NDY STEPS
+    RANK=r WORLD_SIZE=n MASTER_ADDR=127.0.0.1 MASTER_PORT=p python tests/tracer_limited_dm_worker.py SCHEME NX NY NDX NDY STEPS
 """
 import os
 import sys
@@ -22,7 +27,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-NX, NY, NDX, NDY, STEPS = (int(a) for a in sys.argv[1:6])
+SCHEME = sys.argv[1]
+assert SCHEME in ("muscl", "hancock"), SCHEME
+NX, NY, NDX, NDY, STEPS = (int(a) for a in sys.argv[2:7])
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 
 import torch  # noqa: E402
@@ -31,6 +38,7 @@ import torch.distributed as dist  # noqa: E402
 dist.init_process_group("gloo", rank=rank, world_size=world)
 import dl_esm_inf_amd as D  # noqa: E402
 import tracer_cases as TC  # noqa: E402
+import tracer_hancock_numpy as TH  # noqa: E402
 import tracer_muscl_numpy as TM  # noqa: E402
 import tracer_numpy as TN  # noqa: E402
 from nemolite_boxes import _host_inputs  # noqa: E402
@@ -43,6 +51,9 @@ D.parallel_init(rank, world, transport="mailbox")
 GNY, GLD = NY + 2, NX + 2                 # the undivided domain and its one-cell ring
 GBOX = (2, NX + 1, 2, NY + 1)             # its internal region, 1-based
 DXY = 1000.0
+# the wrapper, its restatement on the host, rdt
+INVOKE, HOST_STEP, RDT = {"muscl": (D.psy.invoke_tracer_step_muscl_dm, TM.tracer_step_muscl, TC.RDT),
+                          "hancock": (D.psy.invoke_tracer_step_hancock_dm, TH.tracer_step_hancock, 3.0e6)}[SCHEME]
 
 user = TC.channel_user_mask(NX, NY)
 user[NY // 2 - 6:NY // 2 + 5, NX // 2 - 9:NX // 2 + 8] = 0          # an island across the tile boundaries
@@ -77,6 +88,9 @@ Hall = _host_inputs(rng, user.shape)
 Hall["ssha"] = 0.1 * rng.normal(size=user.shape)
 H = {k: Hall[k] for k in TC.FLOW}
 area_t = np.full(user.shape, DXY * DXY)
+if SCHEME == "hancock":
+    mid, big = TH.face_shares(RDT, GBOX, user, area_t, *[H[k] for k in TC.FLOW])
+    assert mid >= 0.10 and big >= 0.10, (mid, big)
 c_in, c_out = TC.tracers(rng, user.shape, 2)
 c_out = [c.copy() for c in c_in]                   # an open cell's boundary value sits in both buffers
 T, U, V = D.GO_T_POINTS, D.GO_U_POINTS, D.GO_V_POINTS
@@ -118,8 +132,8 @@ errors = 0
 start = [c.copy() for c in c_in]
 s = torch.cuda.Stream()
 for step in range(STEPS):
-    D.psy.invoke_tracer_step_muscl_dm(TC.RDT, Co, Ci, *[F[k] for k in pts], stream=s)
-    TM.tracer_step_muscl(TC.RDT, GBOX, user, area_t, *[H[k] for k in TC.FLOW], c_in, c_out)
+    INVOKE(RDT, Co, Ci, *[F[k] for k in pts], stream=s)
+    HOST_STEP(RDT, GBOX, user, area_t, *[H[k] for k in TC.FLOW], c_in, c_out)
     s.synchronize()
     errors += compare(step)
     Ci, Co, c_in, c_out = Co, Ci, c_out, c_in
