@@ -1455,9 +1455,7 @@ extern "C" int dlesm_jacobi5_multi_step_dm(dlesm_halo_plan *p, const double *in,
 // the three new fields.  No RCCL kernel, no side stream.  (The time-loop entry takes the same route: the wait sits behind
 // the whole sweep in stream order, by which time the neighbours' rings have long arrived.)
 static int shallow_step_peer(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
-                             int ystop, const double *u, const double *v, const double *pf, const double *uold,
-                             const double *vold, const double *pold, double *unew, double *vnew, double *pnew, hipStream_t s,
-                             const double *smooth_alpha)
+                             int ystop, const SwFields &f, hipStream_t s, const double *smooth_alpha)
 {
     DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
                   "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
@@ -1495,31 +1493,18 @@ static int shallow_step_peer(dlesm_halo_plan *p, const dlesm_sw_params *q, int l
         if (int rc = peer_in_strips(p, DLESM_DIRS_ALL, seq, 3, job.un, &job.nun)) return rc;
     bool fused = false;
     if (fp.n && tuning("sw_dm_fused", 1))
-        if (int rc = launch_shallow_framed(*q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
-                                           job, s, &fused, smooth_alpha))
-            return rc;
+        if (int rc = launch_shallow_framed(*q, ld, ny, xstart, xstop, ystart, ystop, f, job, s, &fused, smooth_alpha)) return rc;
     if (!fused) {     // arrays or boxes the tile kernel does not take: the ring in its own launch, its flags behind it, the interior
-        if (int rc = launch_shallow_frame(*q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
-                                          &fp, s, smooth_alpha))
-            return rc;
+        if (int rc = launch_shallow_frame(*q, ld, ny, xstart, xstop, ystart, ystop, f, &fp, s, smooth_alpha)) return rc;
         if (int rc = launch_peer_flags_set(job.peer_flag, job.npeer, seq, p->peer_seqw, p->frame_timed_out, s)) return rc;
-        if (xstop - xstart >= 2 && ystop - ystart >= 2) {
-            int rc;
-            if (smooth_alpha)
-                rc = dlesm_shallow_step_smooth_f64(q, *smooth_alpha, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, u, v, pf,
-                                                   const_cast<double *>(uold), const_cast<double *>(vold), const_cast<double *>(pold),
-                                                   unew, vnew, pnew, s);
-            else
-                rc = dlesm_shallow_step_f64(q, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, u, v, pf, uold, vold, pold, unew,
-                                            vnew, pnew, s);
-            if (rc) return rc;
-        }
+        if (xstop - xstart >= 2 && ystop - ystart >= 2)
+            if (int rc = sw_step_box(q, smooth_alpha, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, f, s)) return rc;
     }
     p->peer_seq = seq;
     if (fused && join_inside && job.nun > 0) return DLESM_OK;        // joined inside the launch
     PeerStrips st{};
     if (int rc = peer_in_strips(p, DLESM_DIRS_ALL, seq, 3, st.s, &st.n)) return rc;
-    double *fields[3] = {unew, vnew, pnew};
+    double *fields[3] = {f.unew, f.vnew, f.pnew};
     return launch_peer_unpack(st, seq, p->peer_seqw, fields, 3, ld, p->frame_timed_out, s);
 }
 
@@ -1527,11 +1512,8 @@ static int shallow_step_peer(dlesm_halo_plan *p, const dlesm_sw_params *q, int l
 // then ONE grouped exchange of the three new fields on the side stream while the interior is
 // computed on the caller's stream; join.  The new fields leave with valid depth-1 halos
 // (corners included: the 3x3 footprint needs them).
-static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart,
-                                int xstop, int ystart, int ystop, const double *u, const double *v,
-                                const double *pf, const double *uold, const double *vold,
-                                const double *pold, double *unew, double *vnew, double *pnew,
-                                hipStream_t s, bool pipelined, const double *smooth_alpha = nullptr)
+static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
+                                int ystop, const SwFields &f, hipStream_t s, bool pipelined, const double *smooth_alpha = nullptr)
 {
     DLESM_REQUIRE(p != nullptr && q != nullptr, "null pointer");
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
@@ -1547,12 +1529,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
                            streams_run_concurrently(s);
     if (!can_chain)
         if (int rc = join_pending(p, s)) return rc;
-    auto box = [&](int xs, int xe, int ys, int ye) {
-        if (smooth_alpha)
-            return dlesm_shallow_step_smooth_f64(q, *smooth_alpha, ld, ny, xs, xe, ys, ye, u, v, pf, const_cast<double *>(uold),
-                                                 const_cast<double *>(vold), const_cast<double *>(pold), unew, vnew, pnew, s);
-        return dlesm_shallow_step_f64(q, ld, ny, xs, xe, ys, ye, u, v, pf, uold, vold, pold, unew, vnew, pnew, s);
-    };
+    auto box = [&](int xs, int xe, int ys, int ye) { return sw_step_box(q, smooth_alpha, ld, ny, xs, xe, ys, ye, f, s); };
     const bool comms = !p->sends.empty() || !p->recvs.empty();
     if (!comms) return box(xstart, xstop, ystart, ystop);
     // mailbox mode has no other transport to fall through to (no communicator): say what is wrong instead of an RCCL error
@@ -1560,8 +1537,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
                   "mailbox mode: the distributed shallow-water step exchanges three fields, this plan's mailboxes have room for %d "
                   "(DLESM_MAILBOX_FIELDS / tuning mailbox_fields, default 3)", p->peer_fcap);
     if (p->peer_on && p->peer_fcap >= 3 && (g_mailbox || tuning("dm_peer", 1)))      // mailboxes connected for three fields
-        return shallow_step_peer(p, q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew, s,
-                                 smooth_alpha);
+        return shallow_step_peer(p, q, ld, ny, xstart, xstop, ystart, ystop, f, s, smooth_alpha);
     // 1. frame: the one-cell ring of the box, one cell per thread, all four sides, its west/east columns
     //    written straight into the send buffers of the three new fields -- no pack launches.
     //    sw_dm_frame=0: the round-1 form (four thin boxes + pack kernels).
@@ -1589,7 +1565,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
             fp.n = 0;
         }
     }
-    double *fields[3] = {unew, vnew, pnew};
+    double *fields[3] = {f.unew, f.vnew, f.pnew};
     // One launch (as the Jacobi step): the ring as the first workgroups of the interior sweep, a device flag
     // hands it to the exchange on the side stream -- no frame launch, no event record on the caller's stream.
     DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
@@ -1606,9 +1582,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
         job.halo_wait_ticks = remote_wait_ticks();
         job.acquire = tuning("dm_acquire", 1);
         bool fused = false;
-        if (int rc = launch_shallow_framed(*q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew,
-                                           pnew, job, s, &fused, smooth_alpha))
-            return rc;
+        if (int rc = launch_shallow_framed(*q, ld, ny, xstart, xstop, ystart, ystop, f, job, s, &fused, smooth_alpha)) return rc;
         if (fused) {
             p->frame_seq = job.seq;
             p->pending = false;                          // the chained wait (if any) is inside the launch
@@ -1634,8 +1608,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
         if (int rc = join_pending(p, s)) return rc;
     }
     if (one_frame) {
-        if (int rc = launch_shallow_frame(*q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew,
-                                          pnew, prepacked ? &fp : nullptr, s, smooth_alpha))
+        if (int rc = launch_shallow_frame(*q, ld, ny, xstart, xstop, ystart, ystop, f, prepacked ? &fp : nullptr, s, smooth_alpha))
             return rc;
     } else {
         if (int rc = box(xstart, xstop, ystart, ystart)) return rc;
@@ -1662,7 +1635,7 @@ extern "C" int dlesm_shallow_step_dm(dlesm_halo_plan *p, const dlesm_sw_params *
                                      const double *pold, double *unew, double *vnew, double *pnew,
                                      void *stream)
 {
-    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
+    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, pf, uold, vold, pold, unew, vnew, pnew},
                                 (hipStream_t)stream, false);
 }
 
@@ -1672,7 +1645,7 @@ extern "C" int dlesm_shallow_step_dm_pipelined(dlesm_halo_plan *p, const dlesm_s
                                                const double *vold, const double *pold, double *unew, double *vnew,
                                                double *pnew, void *stream)
 {
-    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
+    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, pf, uold, vold, pold, unew, vnew, pnew},
                                 (hipStream_t)stream, true);
 }
 
@@ -1683,7 +1656,7 @@ extern "C" int dlesm_shallow_step_smooth_dm(dlesm_halo_plan *p, const dlesm_sw_p
                                             const double *pf, double *uold, double *vold, double *pold, double *unew,
                                             double *vnew, double *pnew, void *stream)
 {
-    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
+    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, pf, uold, vold, pold, unew, vnew, pnew},
                                 (hipStream_t)stream, false, &alpha);
 }
 
@@ -1692,7 +1665,7 @@ extern "C" int dlesm_shallow_step_smooth_dm_pipelined(dlesm_halo_plan *p, const 
                                                       const double *v, const double *pf, double *uold, double *vold,
                                                       double *pold, double *unew, double *vnew, double *pnew, void *stream)
 {
-    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, u, v, pf, uold, vold, pold, unew, vnew, pnew,
+    return shallow_step_dm_impl(p, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, pf, uold, vold, pold, unew, vnew, pnew},
                                 (hipStream_t)stream, true, &alpha);
 }
 
@@ -1763,23 +1736,19 @@ static int shallow_x2_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_s
         }
         // filtered: old2 <- old, T <- u (the fixed ring of the unfiltered level n+1), step_smooth over the grown box (T = n+1,
         // old2 = filtered n), step_smooth over the box (new2 = n+2, old2 = filtered n+1 on the box; its grown ring is exchanged)
-        const size_t bytes = (size_t)ld * ny * sizeof(double);
-        double *t[3] = {nullptr, nullptr, nullptr};
-        for (int k = 0; k < 3; k++)
-            if (hipMallocAsync((void **)&t[k], bytes, s) != hipSuccess) {
-                for (int k2 = 0; k2 < k; k2++) (void)hipFreeAsync(t[k2], s);
-                return fail(DLESM_EHIP, "%s: no scratch memory for the intermediate time level", who);
-            }
-        int rc = DLESM_OK;
-        for (int k = 0; k < 3 && !rc; k++)
-            if (hipMemcpyAsync(w[6 + k], all[3 + k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(t[k], all[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                rc = fail(DLESM_EHIP, "%s: copy failed", who);
-        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, ex0, ex1, ey0, ey1, all[0], all[1], all[2], w[6], w[7], w[8], t[0],
-                                                    t[1], t[2], s);
-        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], w[6], w[7], w[8],
-                                                    w[9], w[10], w[11], s);
-        for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
+        const int rc = with_scratch_levels(who, ld, ny, s, [&](double *const (&t)[3]) {
+            const size_t bytes = (size_t)ld * ny * sizeof(double);
+            int rc = DLESM_OK;
+            for (int k = 0; k < 3 && !rc; k++)
+                if (hipMemcpyAsync(w[6 + k], all[3 + k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                    hipMemcpyAsync(t[k], all[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                    rc = fail(DLESM_EHIP, "%s: copy failed", who);
+            if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, ex0, ex1, ey0, ey1, all[0], all[1], all[2], w[6], w[7], w[8], t[0],
+                                                        t[1], t[2], s);
+            if (!rc) rc = dlesm_shallow_step_smooth_f64(q, *alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], w[6], w[7], w[8],
+                                                        w[9], w[10], w[11], s);
+            return rc;
+        });
         return rc ? rc : exchange(s);
     }
     auto box = [&](int xs, int xe, int ys, int ye) {

@@ -152,10 +152,49 @@ struct FramePack3 {
         return i >= s[q].i0 && i < s[q].i0 + s[q].ni && j >= s[q].j0 && j < s[q].j0 + s[q].nj;
     }
 };
+struct SwFields {                        // the nine arrays of one leapfrog step
+    const double *u, *v, *p;             // level n
+    const double *uold, *vold, *pold;    // level n-1 (the filtered forms also write it)
+    double *unew, *vnew, *pnew;          // level n+1
+};
+// May a shallow-water launch use 16-byte lanes (the wave-tile kernels)?  The n bases are 16-byte aligned, and the leading
+// dimension is even (every row then starts on 16 bytes) or the last column the launch touches, east0 (0-based), lies inside
+// the last whole two-column chunk of a row.  east0 is the caller's to say: xstop - 1 for a box, xstop - 2 for the interior of
+// the framed step (launch_shallow_framed), xstop - 1 + ge for the grown box of the two-step distributed form.
+inline bool sw_lanes16_fit(int ld, int east0, const double *const *f, int n)
+{
+    bool ok = ld % 2 == 0 || east0 + 1 <= 2 * (ld / 2) - 1;
+    for (int k = 0; k < n; k++) ok = ok && ((uintptr_t)f[k] % 16 == 0);
+    return ok;
+}
+inline bool sw_lanes16_fit(int ld, int east0, const SwFields &f)
+{
+    const double *const nine[9] = {f.u, f.v, f.p, f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew};
+    return sw_lanes16_fit(ld, east0, nine, 9);
+}
 int launch_shallow_frame(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                         const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
-                         const FramePack3 *pack, hipStream_t s, const double *smooth_alpha = nullptr);
+                         const SwFields &f, const FramePack3 *pack, hipStream_t s, const double *smooth_alpha = nullptr);
+// the NE step on one 1-based box through the public entries (their refusals apply): dlesm_shallow_step_smooth_f64 when
+// smooth_alpha is given, else dlesm_shallow_step_f64 -- the interior and the thin boxes of the distributed step
+int sw_step_box(const dlesm_sw_params *q, const double *smooth_alpha, int ld, int ny, int xs, int xe, int ys, int ye,
+                const SwFields &f, hipStream_t s);
+// Three stream-ordered scratch arrays of ld x ny doubles for an intermediate time level (the definition the filtered two-step
+// entries fall back to): allocated on s -- what it got is given back if one allocation fails --, handed to body(t), freed on
+// every path; returns the body's code.  who: the entry's name, in front of the error text.
+template <class F>
+int with_scratch_levels(const char *who, int ld, int ny, hipStream_t s, F &&body)
+{
+    const size_t bytes = (size_t)ld * ny * sizeof(double);
+    double *t[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; k++)
+        if (hipMallocAsync((void **)&t[k], bytes, s) != hipSuccess) {
+            for (int k2 = 0; k2 < k; k2++) (void)hipFreeAsync(t[k2], s);
+            return fail(DLESM_EHIP, "%s: no scratch memory for the intermediate time level", who);
+        }
+    const int rc = body(t);
+    for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
+    return rc;
+}
 
 // the frame as the first workgroups of the interior launch (jacobi5_tile_framed): when their last
 // one is done, `seq` is stored to `flag` (device memory; frame_flag_wait sleeps on it)
@@ -318,18 +357,10 @@ struct SwFrameJob {
     int nun, nunb;
     int diag;                     // profiling only (results wrong): 1 = no frame cells, 2 = south/north rows only
 };
-// shallow-water step, register-tiled linear sweep (dlesm_shallow.hip); 0-based inclusive box
-void launch_shallow_tile(const dlesm_sw_params &q, int ld, int x0, int x1, int y0, int y1,
-                         const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, double *unew, double *vnew,
-                         double *pnew, hipStream_t s, bool sw_offset = false, SwFrameJob *fj = nullptr, int wrap = 0,
-                         const double *smooth_alpha = nullptr);   // non-null: also uold/vold/pold <- time_smooth, in place
 // frame of the box + interior sweep of the NE shallow-water step in one launch; *fused = false (nothing
 // launched) when the arrays do not qualify for the tile kernel
 int launch_shallow_framed(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                          const double *u, const double *v, const double *p, const double *uold,
-                          const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
-                          SwFrameJob job, hipStream_t s, bool *fused, const double *smooth_alpha = nullptr);
+                          const SwFields &f, SwFrameJob job, hipStream_t s, bool *fused, const double *smooth_alpha = nullptr);
 
 } // namespace dlesm
 

@@ -1459,85 +1459,6 @@ int launch_stencil5_frame(const double *in, double *out, int ld, int ny, int xst
 }
 
 // ===========================================================================
-// Shallow-water u/v/h update, NE staggering, all intermediates (cu, cv, z, h)
-// recomputed in registers from the 3x3 neighbourhood of u, v, p: 6 fields read,
-// 3 written = 72 B/cell of algorithmic traffic.
-// First, direct form: neighbours come from L1/L2.
-// ===========================================================================
-__global__ __launch_bounds__(256) void shallow_step_direct(
-    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
-    const double *__restrict__ v, const double *__restrict__ p, const double *__restrict__ uold,
-    const double *__restrict__ vold, const double *__restrict__ pold, double *__restrict__ unew,
-    double *__restrict__ vnew, double *__restrict__ pnew)
-{
-    const int i = x0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > x1) return;
-    for (int j = y0 + blockIdx.y; j <= y1; j += gridDim.y)
-        shallow_point_ne(q, ld, (size_t)j * ld + i, u, v, p, uold, vold, pold, unew, vnew, pnew);
-}
-
-// the same for boxes a few columns wide and many rows tall (frame columns): lanes run along j
-__global__ __launch_bounds__(256) void shallow_step_direct_cols(
-    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
-    const double *__restrict__ v, const double *__restrict__ p, const double *__restrict__ uold,
-    const double *__restrict__ vold, const double *__restrict__ pold, double *__restrict__ unew,
-    double *__restrict__ vnew, double *__restrict__ pnew)
-{
-    const int j = y0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > y1) return;
-    for (int i = x0; i <= x1; i++)
-        shallow_point_ne(q, ld, (size_t)j * ld + i, u, v, p, uold, vold, pold, unew, vnew, pnew);
-}
-
-// the one-cell frame of the box (the cells a neighbour needs first in the distributed step): one cell
-// per thread, all four sides in ONE launch; cells a neighbour will receive also go into the aggregated
-// send buffer of the three new fields (FramePack3)
-__global__ __launch_bounds__(256) void shallow_frame_k(
-    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
-    const double *__restrict__ v, const double *__restrict__ p, const double *uold,
-    const double *vold, const double *pold, double *__restrict__ unew,
-    double *__restrict__ vnew, double *__restrict__ pnew, FramePack3 pk, int smooth, double alpha)
-{
-    const long total = frame_cells(x1 - x0 + 1, y1 - y0 + 1);
-    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        int i, j;
-        frame_index(t, x0, x1, y0, y1, i, j);
-        const size_t o = (size_t)j * ld + i;
-        const SwPoint r = shallow_values_ne(q, ld, o, u, v, p, uold, vold, pold);
-        unew[o] = r.un;
-        vnew[o] = r.vn;
-        pnew[o] = r.pn;
-        if (smooth) smooth_old_level(alpha, o, u, v, p, r, const_cast<double *>(uold), const_cast<double *>(vold), const_cast<double *>(pold));
-        for (int k = 0; k < pk.n; k++)
-            if (pk.holds(k, i, j)) {
-                double *b = pk.at(k);          // (a neighbour's mailbox with the peer transport: uncached memory, the
-                b[pk.slot(k, 0, i, j)] = r.un; //  stores have left by the end of the kernel; its flags are raised by a
-                b[pk.slot(k, 1, i, j)] = r.vn; //  launch behind this one)
-                b[pk.slot(k, 2, i, j)] = r.pn;
-            }
-    }
-}
-
-int launch_shallow_frame(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                         const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
-                         const FramePack3 *pack, hipStream_t s, const double *smooth_alpha)
-{
-    if (xstop < xstart || ystop < ystart) return DLESM_OK;
-    if (int rc = check_box("shallow frame", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
-    const long cells = 2L * (xstop - xstart + 1) + 2L * (ystop - ystart + 1);
-    int blocks = (int)((cells + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    FramePack3 pk{};
-    if (pack) pk = *pack;
-    hipLaunchKernelGGL(shallow_frame_k, dim3(blocks), dim3(256), 0, s, q, ld, xstart - 1, xstop - 1, ystart - 1,
-                       ystop - 1, u, v, p, uold, vold, pold, unew, vnew, pnew, pk, smooth_alpha ? 1 : 0,
-                       smooth_alpha ? *smooth_alpha : 0.0);
-    DLESM_HIP_TRY(hipGetLastError());
-    return DLESM_OK;
-}
-
-// ===========================================================================
 // small utility kernels
 // ===========================================================================
 __global__ void copy_patch_k(const double *__restrict__ src, double *__restrict__ dst, int ld, int sx0,
@@ -1897,49 +1818,6 @@ extern "C" int dlesm_stencil5_planned_shape(int ld, int xstart, int xstop, int y
         *rows_per_tile = it->second.rows ? it->second.rows : (vec == 2 ? 2 : 4);
         break;
     }
-    return DLESM_OK;
-}
-
-extern "C" int dlesm_shallow_step_f64(const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop,
-                                      int ystart, int ystop, const double *u, const double *v,
-                                      const double *p, const double *uold, const double *vold,
-                                      const double *pold, double *unew, double *vnew, double *pnew,
-                                      void *stream)
-{
-    if (int rc = ensure_device()) return rc;
-    DLESM_REQUIRE(q && u && v && p && uold && vold && pold && unew && vnew && pnew, "null pointer");
-    if (xstop < xstart || ystop < ystart) return DLESM_OK;
-    if (int rc = check_box("dlesm_shallow_step_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
-    DLESM_REQUIRE(unew != u && unew != v && unew != p && vnew != u && vnew != v && vnew != p &&
-                      pnew != u && pnew != v && pnew != p,
-                  "shallow step: outputs alias the 3x3-read inputs");
-    const int nx = xstop - xstart + 1, nyb = ystop - ystart + 1;
-    // 16-byte lanes; on an odd leading dimension (rows alternately 8-byte aligned) only while
-    // the east ring column stays inside the last whole 2-column chunk of a row
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew,
-                            (const double *)pnew})
-        aligned = aligned && ((uintptr_t)f % 16 == 0);
-    // sw_kernel: 0 (default) = register-tiled sweep of dlesm_shallow.hip, 73.7 % of HBM peak at
-    // 8192^2; 1 = direct form, 62 % (scripts/shallow_probe.py, profiles/r01_shallow_*.txt)
-    // boxes a few columns wide (the west/east frame columns of the distributed step): a wave tile would load
-    // 128 columns x 4 rows of three arrays for two useful cells -- one cell per thread moves 6 x less
-    const bool thin = nx <= SW_THIN_BOX && nyb > 8;
-    if (aligned && tuning("sw_kernel", 0) == 0 && !thin) {
-        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold,
-                            unew, vnew, pnew, (hipStream_t)stream);
-        DLESM_HIP_TRY(hipGetLastError());
-        return DLESM_OK;
-    }
-    // odd leading dimension / thin boxes: direct form, neighbours through L1/L2
-    if (thin)
-        hipLaunchKernelGGL(shallow_step_direct_cols, dim3((nyb + 255) / 256), dim3(256), 0, (hipStream_t)stream, *q, ld,
-                           xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew, vnew, pnew);
-    else
-        hipLaunchKernelGGL(shallow_step_direct, dim3((nx + 255) / 256, nyb > 4096 ? 4096 : nyb), dim3(256), 0,
-                           (hipStream_t)stream, *q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold,
-                           vold, pold, unew, vnew, pnew);
-    DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;
 }
 

@@ -40,10 +40,11 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // multiple of 16 --, else 1 (62 output chunks): on an odd pitch (the reference's default alignment) no tile covers whole lines
 // whatever its width, and the wider halo only costs (8192^2, alignment 1, planned shapes, same box: step 0.836-0.845 ms with
 // 56 lanes against 0.808-0.813 with 62).
-static inline int sw_halo_lanes(int ld, std::initializer_list<const double *> arrays)
+static inline int sw_halo_lanes(int ld, const SwFields &f)
 {
     bool lines = ld % 16 == 0;
-    for (const double *f : arrays) lines = lines && ((uintptr_t)f % 128 == 0);
+    for (const double *a : {f.u, f.v, f.p, f.uold, f.vold, f.pold, (const double *)f.unew, (const double *)f.vnew, (const double *)f.pnew})
+        lines = lines && ((uintptr_t)a % 128 == 0);
     return lines ? 4 : 1;
 }
 
@@ -629,13 +630,15 @@ static void sw_rule_shape(int ld, int x0, int x1, int hl, int *nxw_out, int *tpb
     *tpb_out = tpb;
 }
 
-void launch_shallow_tile(const dlesm_sw_params &q, int ld, int x0, int x1, int y0, int y1,
-                         const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, double *unew, double *vnew,
-                         double *pnew, hipStream_t s, bool sw_offset, SwFrameJob *fj, int wrap, const double *smooth_alpha)
+// shallow-water step, register-tiled linear sweep; 0-based inclusive box
+static void launch_shallow_tile(const dlesm_sw_params &q, int ld, int x0, int x1, int y0, int y1, const SwFields &f, hipStream_t s,
+                                bool sw_offset = false, SwFrameJob *fj = nullptr, int wrap = 0,
+                                const double *smooth_alpha = nullptr)   // non-null: also uold/vold/pold <- time_smooth, in place
 {
+    const double *u = f.u, *v = f.v, *p = f.p, *uold = f.uold, *vold = f.vold, *pold = f.pold;   // (as the launches below name them)
+    double *unew = f.unew, *vnew = f.vnew, *pnew = f.pnew;
     const int cb = sw_first_chunk(x0);
-    const int hl = sw_halo_lanes(ld, {u, v, p, uold, vold, pold, unew, vnew, pnew});
+    const int hl = sw_halo_lanes(ld, f);
     int nxw, tpb, ntm = tuning("sw_nt", sw_nt_default(ld, y0, y1)) & (kLab ? 15 : 3);      // (bits 4, 8: experiments, lab build only)
     SwSmooth sm{0.0, nullptr, nullptr, nullptr};
     if (smooth_alpha) sm = SwSmooth{*smooth_alpha, const_cast<double *>(uold), const_cast<double *>(vold), const_cast<double *>(pold)};
@@ -771,31 +774,139 @@ void launch_shallow_tile(const dlesm_sw_params &q, int ld, int x0, int x1, int y
 #undef DLESM_SW3
 }
 
+// ===========================================================================
+// Shallow-water u/v/h update, NE staggering, all intermediates (cu, cv, z, h)
+// recomputed in registers from the 3x3 neighbourhood of u, v, p: 6 fields read,
+// 3 written = 72 B/cell of algorithmic traffic.
+// First, direct form: neighbours come from L1/L2.
+// ===========================================================================
+__global__ __launch_bounds__(256) void shallow_step_direct(
+    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
+    const double *__restrict__ v, const double *__restrict__ p, const double *__restrict__ uold,
+    const double *__restrict__ vold, const double *__restrict__ pold, double *__restrict__ unew,
+    double *__restrict__ vnew, double *__restrict__ pnew)
+{
+    const int i = x0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > x1) return;
+    for (int j = y0 + blockIdx.y; j <= y1; j += gridDim.y)
+        shallow_point_ne(q, ld, (size_t)j * ld + i, u, v, p, uold, vold, pold, unew, vnew, pnew);
+}
+
+// the same for boxes a few columns wide and many rows tall (frame columns): lanes run along j
+__global__ __launch_bounds__(256) void shallow_step_direct_cols(
+    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
+    const double *__restrict__ v, const double *__restrict__ p, const double *__restrict__ uold,
+    const double *__restrict__ vold, const double *__restrict__ pold, double *__restrict__ unew,
+    double *__restrict__ vnew, double *__restrict__ pnew)
+{
+    const int j = y0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > y1) return;
+    for (int i = x0; i <= x1; i++)
+        shallow_point_ne(q, ld, (size_t)j * ld + i, u, v, p, uold, vold, pold, unew, vnew, pnew);
+}
+
+// the one-cell frame of the box (the cells a neighbour needs first in the distributed step): one cell
+// per thread, all four sides in ONE launch; cells a neighbour will receive also go into the aggregated
+// send buffer of the three new fields (FramePack3)
+__global__ __launch_bounds__(256) void shallow_frame_k(
+    dlesm_sw_params q, int ld, int x0, int x1, int y0, int y1, const double *__restrict__ u,
+    const double *__restrict__ v, const double *__restrict__ p, const double *uold,
+    const double *vold, const double *pold, double *__restrict__ unew,
+    double *__restrict__ vnew, double *__restrict__ pnew, FramePack3 pk, int smooth, double alpha)
+{
+    const long total = frame_cells(x1 - x0 + 1, y1 - y0 + 1);
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        int i, j;
+        frame_index(t, x0, x1, y0, y1, i, j);
+        const size_t o = (size_t)j * ld + i;
+        const SwPoint r = shallow_values_ne(q, ld, o, u, v, p, uold, vold, pold);
+        unew[o] = r.un;
+        vnew[o] = r.vn;
+        pnew[o] = r.pn;
+        if (smooth) smooth_old_level(alpha, o, u, v, p, r, const_cast<double *>(uold), const_cast<double *>(vold), const_cast<double *>(pold));
+        for (int k = 0; k < pk.n; k++)
+            if (pk.holds(k, i, j)) {
+                double *b = pk.at(k);          // (a neighbour's mailbox with the peer transport: uncached memory, the
+                b[pk.slot(k, 0, i, j)] = r.un; //  stores have left by the end of the kernel; its flags are raised by a
+                b[pk.slot(k, 1, i, j)] = r.vn; //  launch behind this one)
+                b[pk.slot(k, 2, i, j)] = r.pn;
+            }
+    }
+}
+
+int launch_shallow_frame(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                         const SwFields &f, const FramePack3 *pack, hipStream_t s, const double *smooth_alpha)
+{
+    if (xstop < xstart || ystop < ystart) return DLESM_OK;
+    if (int rc = check_box("shallow frame", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
+    const long cells = 2L * (xstop - xstart + 1) + 2L * (ystop - ystart + 1);
+    int blocks = (int)((cells + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    FramePack3 pk{};
+    if (pack) pk = *pack;
+    hipLaunchKernelGGL(shallow_frame_k, dim3(blocks), dim3(256), 0, s, q, ld, xstart - 1, xstop - 1, ystart - 1,
+                       ystop - 1, f.u, f.v, f.p, f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew, pk, smooth_alpha ? 1 : 0,
+                       smooth_alpha ? *smooth_alpha : 0.0);
+    DLESM_HIP_TRY(hipGetLastError());
+    return DLESM_OK;
+}
+
 } // namespace dlesm
 
-int dlesm::launch_shallow_framed(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart,
-                                 int ystop, const double *u, const double *v, const double *p, const double *uold,
-                                 const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
-                                 SwFrameJob job, hipStream_t s, bool *fused, const double *smooth_alpha)
+int dlesm::launch_shallow_framed(const dlesm_sw_params &q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                 const SwFields &f, SwFrameJob job, hipStream_t s, bool *fused, const double *smooth_alpha)
 {
     *fused = false;
     if (xstop - xstart < 2 || ystop - ystart < 2) return DLESM_OK;          // no interior: two-launch path
     if (int rc = check_box("dlesm_shallow_step_dm", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
-    bool aligned = ld % 2 == 0 || (xstop - 2) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew,
-                            (const double *)pnew})
-        aligned = aligned && ((uintptr_t)f % 16 == 0);
-    if (!aligned || tuning("sw_kernel", 0) != 0 || tuning("sw_tile_rows", 2) != 2 || !tuning("sw_dpp", 1)) return DLESM_OK;
+    // (the interior's east column: the frame takes column xstop - 1)
+    if (!sw_lanes16_fit(ld, xstop - 2, f) || tuning("sw_kernel", 0) != 0 || tuning("sw_tile_rows", 2) != 2 || !tuning("sw_dpp", 1)) return DLESM_OK;
     job.fx0 = xstart - 1, job.fx1 = xstop - 1, job.fy0 = ystart - 1, job.fy1 = ystop - 1;
     job.diag = tuning("sw_dm_diag", 0);
-    launch_shallow_tile(q, ld, xstart, xstop - 2, ystart, ystop - 2, u, v, p, uold, vold, pold, unew, vnew, pnew, s,
-                        false, &job, 0, smooth_alpha);
+    launch_shallow_tile(q, ld, xstart, xstop - 2, ystart, ystop - 2, f, s, false, &job, 0, smooth_alpha);
     DLESM_HIP_TRY(hipGetLastError());
     *fused = true;
     return DLESM_OK;
 }
 
 using namespace dlesm;
+
+extern "C" int dlesm_shallow_step_f64(const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop,
+                                      int ystart, int ystop, const double *u, const double *v,
+                                      const double *p, const double *uold, const double *vold,
+                                      const double *pold, double *unew, double *vnew, double *pnew,
+                                      void *stream)
+{
+    if (int rc = ensure_device()) return rc;
+    DLESM_REQUIRE(q && u && v && p && uold && vold && pold && unew && vnew && pnew, "null pointer");
+    if (xstop < xstart || ystop < ystart) return DLESM_OK;
+    if (int rc = check_box("dlesm_shallow_step_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
+    DLESM_REQUIRE(unew != u && unew != v && unew != p && vnew != u && vnew != v && vnew != p &&
+                      pnew != u && pnew != v && pnew != p,
+                  "shallow step: outputs alias the 3x3-read inputs");
+    const int nx = xstop - xstart + 1, nyb = ystop - ystart + 1;
+    const SwFields f{u, v, p, uold, vold, pold, unew, vnew, pnew};
+    // sw_kernel: 0 (default) = register-tiled sweep of dlesm_shallow.hip, 73.7 % of HBM peak at
+    // 8192^2; 1 = direct form, 62 % (scripts/shallow_probe.py, profiles/r01_shallow_*.txt)
+    // boxes a few columns wide (the west/east frame columns of the distributed step): a wave tile would load
+    // 128 columns x 4 rows of three arrays for two useful cells -- one cell per thread moves 6 x less
+    const bool thin = nx <= SW_THIN_BOX && nyb > 8;
+    if (sw_lanes16_fit(ld, xstop - 1, f) && tuning("sw_kernel", 0) == 0 && !thin) {
+        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, f, (hipStream_t)stream);
+        DLESM_HIP_TRY(hipGetLastError());
+        return DLESM_OK;
+    }
+    // odd leading dimension / thin boxes: direct form, neighbours through L1/L2
+    if (thin)
+        hipLaunchKernelGGL(shallow_step_direct_cols, dim3((nyb + 255) / 256), dim3(256), 0, (hipStream_t)stream, *q, ld,
+                           xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew, vnew, pnew);
+    else
+        hipLaunchKernelGGL(shallow_step_direct, dim3((nx + 255) / 256, nyb > 4096 ? 4096 : nyb), dim3(256), 0,
+                           (hipStream_t)stream, *q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold,
+                           vold, pold, unew, vnew, pnew);
+    DLESM_HIP_TRY(hipGetLastError());
+    return DLESM_OK;
+}
 
 // SW staggering, one cell per thread, neighbours through L1/L2: the
 // configuration is serial-only in the reference (periodic boundaries), small next to the NE step.
@@ -852,14 +963,10 @@ extern "C" int dlesm_shallow_step_sw_f64(const dlesm_sw_params *q, int ld, int n
                       pnew != u && pnew != v && pnew != p,
                   "shallow step: outputs alias the 3x3-read inputs");
     const int nx = xstop - xstart + 1, h = ystop - ystart + 1;
+    const SwFields f{u, v, p, uold, vold, pold, unew, vnew, pnew};
     // 16-byte lanes under the same conditions as the NE step (dlesm_shallow_step_f64)
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew,
-                            (const double *)pnew})
-        aligned = aligned && ((uintptr_t)f % 16 == 0);
-    if (aligned && tuning("sw_kernel", 0) == 0) {
-        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew,
-                            vnew, pnew, (hipStream_t)stream, true);
+    if (sw_lanes16_fit(ld, xstop - 1, f) && tuning("sw_kernel", 0) == 0) {
+        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, f, (hipStream_t)stream, true);
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
@@ -887,13 +994,9 @@ extern "C" int dlesm_shallow_step_sw_periodic_f64(const dlesm_sw_params *q, int 
                       pnew != u && pnew != v && pnew != p && unew != vnew && unew != pnew && vnew != pnew,
                   "shallow step: outputs alias the 3x3-read inputs or each other");
     const int wrap = (bc_x == DLESM_BC_PERIODIC ? 1 : 0) | (bc_y == DLESM_BC_PERIODIC ? 2 : 0);
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew,
-                            (const double *)pnew})
-        aligned = aligned && ((uintptr_t)f % 16 == 0);
-    if (aligned && tuning("sw_kernel", 0) == 0 && tuning("sw_wrap_fused", 1)) {
-        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew,
-                            vnew, pnew, (hipStream_t)stream, true, nullptr, wrap);
+    const SwFields f{u, v, p, uold, vold, pold, unew, vnew, pnew};
+    if (sw_lanes16_fit(ld, xstop - 1, f) && tuning("sw_kernel", 0) == 0 && tuning("sw_wrap_fused", 1)) {
+        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, f, (hipStream_t)stream, true, nullptr, wrap);
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
@@ -907,17 +1010,9 @@ extern "C" int dlesm_shallow_step_sw_periodic_f64(const dlesm_sw_params *q, int 
 
 // ---- the step WITH the Asselin filter of the old level (time_smooth) folded in: one launch = one whole time step of
 // the GOcean leapfrog, 96 B/cell (six arrays read, six written) instead of 72 + 3 x 32 = 168 for step + three filters.
-static bool nine_aligned(int ld, int xstop, const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, const double *unew, const double *vnew, const double *pnew)
+static int nine_distinct(const char *who, const SwFields &f)
 {
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : {u, v, p, uold, vold, pold, unew, vnew, pnew}) aligned = aligned && ((uintptr_t)f % 16 == 0);
-    return aligned;
-}
-static int nine_distinct(const char *who, const double *u, const double *v, const double *p, const double *uold,
-                         const double *vold, const double *pold, const double *unew, const double *vnew, const double *pnew)
-{
-    const double *a[9] = {u, v, p, uold, vold, pold, unew, vnew, pnew};
+    const double *a[9] = {f.u, f.v, f.p, f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew};
     for (int i = 0; i < 9; i++)
         for (int j = i + 1; j < 9; j++)
             if (a[i] == a[j]) return fail(DLESM_EINVAL, "%s: the nine fields must be nine different arrays", who);
@@ -933,13 +1028,12 @@ extern "C" int dlesm_shallow_step_smooth_f64(const dlesm_sw_params *q, double al
     DLESM_REQUIRE(q && u && v && p && uold && vold && pold && unew && vnew && pnew, "null pointer");
     if (xstop < xstart || ystop < ystart) return DLESM_OK;
     if (int rc = check_box("dlesm_shallow_step_smooth_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
-    if (int rc = nine_distinct("dlesm_shallow_step_smooth_f64", u, v, p, uold, vold, pold, unew, vnew, pnew)) return rc;
+    const SwFields f{u, v, p, uold, vold, pold, unew, vnew, pnew};
+    if (int rc = nine_distinct("dlesm_shallow_step_smooth_f64", f)) return rc;
     const int nx = xstop - xstart + 1, nyb = ystop - ystart + 1;
     const bool thin = nx <= SW_THIN_BOX && nyb > 8;
-    if (nine_aligned(ld, xstop, u, v, p, uold, vold, pold, unew, vnew, pnew) && tuning("sw_kernel", 0) == 0 && !thin &&
-        tuning("sw_smooth_fused", 1)) {
-        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew, vnew, pnew,
-                            (hipStream_t)stream, false, nullptr, 0, &alpha);
+    if (sw_lanes16_fit(ld, xstop - 1, f) && tuning("sw_kernel", 0) == 0 && !thin && tuning("sw_smooth_fused", 1)) {
+        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, f, (hipStream_t)stream, false, nullptr, 0, &alpha);
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
@@ -949,6 +1043,15 @@ extern "C" int dlesm_shallow_step_smooth_f64(const dlesm_sw_params *q, double al
     if (int rc = dlesm_time_smooth_f64(ld, ny, xstart, xstop, ystart, ystop, alpha, u, unew, uold, stream)) return rc;
     if (int rc = dlesm_time_smooth_f64(ld, ny, xstart, xstop, ystart, ystop, alpha, v, vnew, vold, stream)) return rc;
     return dlesm_time_smooth_f64(ld, ny, xstart, xstop, ystart, ystop, alpha, p, pnew, pold, stream);
+}
+
+int dlesm::sw_step_box(const dlesm_sw_params *q, const double *smooth_alpha, int ld, int ny, int xs, int xe, int ys, int ye,
+                       const SwFields &f, hipStream_t s)
+{
+    if (smooth_alpha)
+        return dlesm_shallow_step_smooth_f64(q, *smooth_alpha, ld, ny, xs, xe, ys, ye, f.u, f.v, f.p, const_cast<double *>(f.uold),
+                                             const_cast<double *>(f.vold), const_cast<double *>(f.pold), f.unew, f.vnew, f.pnew, s);
+    return dlesm_shallow_step_f64(q, ld, ny, xs, xe, ys, ye, f.u, f.v, f.p, f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew, s);
 }
 
 extern "C" int dlesm_shallow_step_sw_smooth_periodic_f64(const dlesm_sw_params *q, double alpha, int ld, int ny,
@@ -961,12 +1064,11 @@ extern "C" int dlesm_shallow_step_sw_smooth_periodic_f64(const dlesm_sw_params *
     const int xstart = internal->xstart, xstop = internal->xstop, ystart = internal->ystart, ystop = internal->ystop;
     if (xstop < xstart || ystop < ystart) return DLESM_OK;
     if (int rc = check_box("dlesm_shallow_step_sw_smooth_periodic_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
-    if (int rc = nine_distinct("dlesm_shallow_step_sw_smooth_periodic_f64", u, v, p, uold, vold, pold, unew, vnew, pnew)) return rc;
+    const SwFields f{u, v, p, uold, vold, pold, unew, vnew, pnew};
+    if (int rc = nine_distinct("dlesm_shallow_step_sw_smooth_periodic_f64", f)) return rc;
     const int wrap = (bc_x == DLESM_BC_PERIODIC ? 1 : 0) | (bc_y == DLESM_BC_PERIODIC ? 2 : 0);
-    if (nine_aligned(ld, xstop, u, v, p, uold, vold, pold, unew, vnew, pnew) && tuning("sw_kernel", 0) == 0 &&
-        tuning("sw_wrap_fused", 1) && tuning("sw_smooth_fused", 1)) {
-        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, u, v, p, uold, vold, pold, unew, vnew, pnew,
-                            (hipStream_t)stream, true, nullptr, wrap, &alpha);
+    if (sw_lanes16_fit(ld, xstop - 1, f) && tuning("sw_kernel", 0) == 0 && tuning("sw_wrap_fused", 1) && tuning("sw_smooth_fused", 1)) {
+        launch_shallow_tile(*q, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, f, (hipStream_t)stream, true, nullptr, wrap, &alpha);
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     }
@@ -1041,25 +1143,18 @@ extern "C" int dlesm_periodic_halos_apply_f64(double *field, int ld, int ny, con
     return dlesm_periodic_halos_apply_multi_f64(one, 1, ld, ny, internal, bc_x, bc_y, stream);
 }
 
-static int shallow_autotune(bool sw_offset, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop,
-                            int ystart, int ystop, const double *u, const double *v,
-                            const double *p, const double *uold, const double *vold,
-                            const double *pold, double *unew, double *vnew, double *pnew,
-                            void *stream)
+static int shallow_autotune(bool sw_offset, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                            const SwFields &f, void *stream)
 {
     // the step itself validates the arguments, warms the clocks, and tells whether the tile kernel applies
-    if (int rc = (sw_offset ? dlesm_shallow_step_sw_f64 : dlesm_shallow_step_f64)(q, ld, ny, xstart, xstop, ystart, ystop, u, v, p,
-                                                                                  uold, vold, pold, unew, vnew, pnew, stream))
+    if (int rc = (sw_offset ? dlesm_shallow_step_sw_f64 : dlesm_shallow_step_f64)(q, ld, ny, xstart, xstop, ystart, ystop, f.u, f.v, f.p,
+                                                                                  f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew, stream))
         return rc;
-    {   // arrays the step sent to the one-cell-per-thread form have no shapes to choose from
-        bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-        for (const double *f : {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew, (const double *)pnew})
-            aligned = aligned && ((uintptr_t)f % 16 == 0);
-        if (!aligned) return DLESM_OK;
-    }
+    // arrays the step sent to the one-cell-per-thread form have no shapes to choose from
+    if (!sw_lanes16_fit(ld, xstop - 1, f)) return DLESM_OK;
     if (xstop < xstart || ystop < ystart || tuning("sw_kernel", 0) != 0) return DLESM_OK;
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
-    const int hl = sw_halo_lanes(ld, {u, v, p, uold, vold, pold, (const double *)unew, (const double *)vnew, (const double *)pnew});
+    const int hl = sw_halo_lanes(ld, f);
     const int nxw0 = (x1 / 2 - sw_first_chunk(x0) + (64 - 2 * hl)) / (64 - 2 * hl);
     if (nxw0 < 16 || tuning("sw_tile_rows", 2) != 2) return DLESM_OK;      // thin boxes: nothing to choose
     hipStream_t s = (hipStream_t)stream;
@@ -1098,7 +1193,7 @@ static int shallow_autotune(bool sw_offset, const dlesm_sw_params *q, int ld, in
                 { std::lock_guard<std::mutex> lk(g_sw_mu); g_sw_override = c; }
                 (void)hipEventRecord(e0, s);
                 for (int rep = 0; rep < 3; rep++)
-                    launch_shallow_tile(*q, ld, x0, x1, y0, y1, u, v, p, uold, vold, pold, unew, vnew, pnew, s, sw_offset);
+                    launch_shallow_tile(*q, ld, x0, x1, y0, y1, f, s, sw_offset);
                 (void)hipEventRecord(e1, s);
                 { std::lock_guard<std::mutex> lk(g_sw_mu); g_sw_override = SwShape{0, 0, 0}; }
                 if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess)
@@ -1138,7 +1233,7 @@ extern "C" int dlesm_shallow_autotune_f64(const dlesm_sw_params *q, int ld, int 
                                           const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
                                           void *stream)
 {
-    return shallow_autotune(false, q, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, unew, vnew, pnew, stream);
+    return shallow_autotune(false, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, p, uold, vold, pold, unew, vnew, pnew}, stream);
 }
 
 extern "C" int dlesm_shallow_autotune_sw_f64(const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
@@ -1146,5 +1241,5 @@ extern "C" int dlesm_shallow_autotune_sw_f64(const dlesm_sw_params *q, int ld, i
                                              const double *vold, const double *pold, double *unew, double *vnew, double *pnew,
                                              void *stream)
 {
-    return shallow_autotune(true, q, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, unew, vnew, pnew, stream);
+    return shallow_autotune(true, q, ld, ny, xstart, xstop, ystart, ystop, {u, v, p, uold, vold, pold, unew, vnew, pnew}, stream);
 }

@@ -555,13 +555,11 @@ int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny)
     return DLESM_OK;
 }
 
-// The wave-tile conditions of the GROW kernels: 16-byte aligned bases, and an even leading dimension or a grown box
-// whose last computed column (xstop + ge) and its east operand lie in whole 2-column chunks.
+// The wave-tile conditions of the GROW kernels: the fit rule (sw_lanes16_fit) for the grown box, whose last computed column is
+// xstop + ge, and the two tuning switches.
 bool x2_grown_fits(int ld, int xstop, int ge, const double *const (&all)[12])
 {
-    bool ok = ld % 2 == 0 || (xstop - 1 + ge) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : all) ok = ok && ((uintptr_t)f % 16 == 0);
-    return ok && tuning("sw_kernel", 0) == 0 && tuning("sw_x2_fused", 1) != 0;
+    return sw_lanes16_fit(ld, xstop - 1 + ge, all, 12) && tuning("sw_kernel", 0) == 0 && tuning("sw_x2_fused", 1) != 0;
 }
 
 // One launch of shallow_tile_x2<..., GROW> over the piece (xs..xe, ys..ye) of the sub-domain box (bx0..bx1, by0..by1), all 1-based;
@@ -605,10 +603,8 @@ extern "C" int dlesm_shallow_step_x2_f64(const dlesm_sw_params *q, int ld, int n
     if (int rc = check_box("dlesm_shallow_step_x2_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
     const double *all[12] = {u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2};
     if (int rc = x2_disjoint("dlesm_shallow_step_x2_f64", all, ld, ny)) return rc;
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : all) aligned = aligned && ((uintptr_t)f % 16 == 0);
     hipStream_t s = (hipStream_t)stream;
-    if (!aligned || tuning("sw_kernel", 0) != 0 || !tuning("sw_x2_fused", 1)) {      // the definition: two single steps
+    if (!sw_lanes16_fit(ld, xstop - 1, all, 12) || tuning("sw_kernel", 0) != 0 || !tuning("sw_x2_fused", 1)) {      // the definition: two single steps
         if (int rc = dlesm_shallow_step_f64(q, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold, vold, pold, unew, vnew, pnew, stream)) return rc;
         return dlesm_shallow_step_f64(q, ld, ny, xstart, xstop, ystart, ystop, unew, vnew, pnew, u, v, p, unew2, vnew2, pnew2, stream);
     }
@@ -645,10 +641,8 @@ extern "C" int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double
     if (int rc = check_box("dlesm_shallow_step_smooth_x2_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
     const double *all[12] = {u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2};
     if (int rc = x2_disjoint("dlesm_shallow_step_smooth_x2_f64", all, ld, ny)) return rc;
-    bool aligned = ld % 2 == 0 || (xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : all) aligned = aligned && ((uintptr_t)f % 16 == 0);
     hipStream_t s = (hipStream_t)stream;
-    if (aligned && tuning("sw_kernel", 0) == 0 && tuning("sw_x2_fused", 1)) {
+    if (sw_lanes16_fit(ld, xstop - 1, all, 12) && tuning("sw_kernel", 0) == 0 && tuning("sw_x2_fused", 1)) {
         // (X2Arrays: u1.. = where the stored level n+1 goes -- here the filtered one; u2.. = level n+2)
         launch_x2(*q, ld, ny, xstart, xstop, ystart, ystop, X2Arrays{u, v, p, uold, vold, pold, uold2, vold2, pold2, unew2, vnew2, pnew2}, &alpha, s);
         DLESM_HIP_TRY(hipGetLastError());
@@ -656,24 +650,18 @@ extern "C" int dlesm_shallow_step_smooth_x2_f64(const dlesm_sw_params *q, double
     }
     // the definition: old2 <- old on the box (the only cells the filter reads, and the only ones the fused kernel writes);
     // T <- u (the level-n+1 ring); step_smooth(u, old2 -> filtered n, T = n+1); step_smooth(T, old2 -> filtered n+1, new2 = n+2)
-    const size_t bytes = (size_t)ld * ny * sizeof(double);
-    double *t[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++)
-        if (hipMallocAsync((void **)&t[k], bytes, s) != hipSuccess) {
-            for (int q2 = 0; q2 < k; q2++) (void)hipFreeAsync(t[q2], s);
-            return fail(DLESM_EHIP, "dlesm_shallow_step_smooth_x2_f64: no scratch memory for the intermediate time level");
-        }
-    const double *src[6] = {uold, vold, pold, u, v, p};
-    double *dst[6] = {uold2, vold2, pold2, t[0], t[1], t[2]};
-    int rc = DLESM_OK;
-    for (int k = 0; k < 6 && !rc; k++)
-        if ((k < 3 ? copy_box(dst[k], src[k], ld, xstart, xstop, ystart, ystop, s)
-                   : hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-            rc = fail(DLESM_EHIP, "dlesm_shallow_step_smooth_x2_f64: copy failed");
-    if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
-    if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
-    for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
-    return rc;
+    return with_scratch_levels("dlesm_shallow_step_smooth_x2_f64", ld, ny, s, [&](double *const (&t)[3]) {
+        const double *src[6] = {uold, vold, pold, u, v, p};
+        double *dst[6] = {uold2, vold2, pold2, t[0], t[1], t[2]};
+        int rc = DLESM_OK;
+        for (int k = 0; k < 6 && !rc; k++)
+            if ((k < 3 ? copy_box(dst[k], src[k], ld, xstart, xstop, ystart, ystop, s)
+                       : hipMemcpyAsync(dst[k], src[k], (size_t)ld * ny * sizeof(double), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+                rc = fail(DLESM_EHIP, "dlesm_shallow_step_smooth_x2_f64: copy failed");
+        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
+        if (!rc) rc = dlesm_shallow_step_smooth_f64(q, alpha, ld, ny, xstart, xstop, ystart, ystop, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
+        return rc;
+    });
 }
 
 // ---- the SW-offset, doubly periodic model (the GOcean `shallow` benchmark's configuration) --------------------------------------
@@ -683,8 +671,7 @@ static int sw_x2_common(const char *who, const dlesm_region *internal, int ld, i
     for (const double *f : all) DLESM_REQUIRE(f != nullptr, "null pointer");
     if (int rc = check_box(who, ld, ny, internal->xstart, internal->xstop, internal->ystart, internal->ystop, 1)) return rc;
     if (int rc = x2_disjoint(who, all, ld, ny)) return rc;
-    *aligned = ld % 2 == 0 || (internal->xstop - 1) + 1 <= 2 * (ld / 2) - 1;
-    for (const double *f : all) *aligned = *aligned && ((uintptr_t)f % 16 == 0);
+    *aligned = sw_lanes16_fit(ld, internal->xstop - 1, all, 12);
     return DLESM_OK;
 }
 
@@ -743,21 +730,15 @@ extern "C" int dlesm_shallow_step_sw_smooth_x2_periodic_f64(const dlesm_sw_param
     }
     // the definition, through three stream-ordered scratch arrays for the unfiltered level n+1; old2 <- old on the box only
     // (what the filter reads; the steps write the periodic images), so that no other cell of old2 is touched
-    const size_t bytes = (size_t)ld * ny * sizeof(double);
-    double *t[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++)
-        if (hipMallocAsync((void **)&t[k], bytes, s) != hipSuccess) {
-            for (int q2 = 0; q2 < k; q2++) (void)hipFreeAsync(t[q2], s);
-            return fail(DLESM_EHIP, "dlesm_shallow_step_sw_smooth_x2_periodic_f64: no scratch memory for the intermediate time level");
-        }
-    const double *src[3] = {uold, vold, pold};
-    double *dst[3] = {uold2, vold2, pold2};
-    int rc = DLESM_OK;
-    for (int k = 0; k < 3 && !rc; k++)
-        if (copy_box(dst[k], src[k], ld, internal->xstart, internal->xstop, internal->ystart, internal->ystop, s) != hipSuccess)
-            rc = fail(DLESM_EHIP, "dlesm_shallow_step_sw_smooth_x2_periodic_f64: copy failed");
-    if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
-    if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
-    for (int k = 0; k < 3; k++) (void)hipFreeAsync(t[k], s);
-    return rc;
+    return with_scratch_levels("dlesm_shallow_step_sw_smooth_x2_periodic_f64", ld, ny, s, [&](double *const (&t)[3]) {
+        const double *src[3] = {uold, vold, pold};
+        double *dst[3] = {uold2, vold2, pold2};
+        int rc = DLESM_OK;
+        for (int k = 0; k < 3 && !rc; k++)
+            if (copy_box(dst[k], src[k], ld, internal->xstart, internal->xstop, internal->ystart, internal->ystop, s) != hipSuccess)
+                rc = fail(DLESM_EHIP, "dlesm_shallow_step_sw_smooth_x2_periodic_f64: copy failed");
+        if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, u, v, p, uold2, vold2, pold2, t[0], t[1], t[2], stream);
+        if (!rc) rc = dlesm_shallow_step_sw_smooth_periodic_f64(q, alpha, ld, ny, internal, bc_x, bc_y, t[0], t[1], t[2], uold2, vold2, pold2, unew2, vnew2, pnew2, stream);
+        return rc;
+    });
 }

@@ -572,43 +572,48 @@ def shallow_params(dx, dy, dt):
     return SwParams(fsdx=4.0 / dx, fsdy=4.0 / dy, tdts8=tdt / 8.0, tdtsdx=tdt / dx, tdtsdy=tdt / dy)
 
 
+def _shallow_head(params, alpha, plan, fields):
+    """what every shallow-water entry takes first: [plan,] params, [alpha,] and the extents of the arrays (p is fields[2])"""
+    g = fields[2].grid
+    return (() if plan is None else (plan,)) + (C.byref(params),) + (() if alpha is None else (float(alpha),)) + (g.nx, g.ny)
+
+
+def _shallow_box(entry, params, alpha, plan, fields, stream):
+    """the body of the shallow-water wrappers whose C entry takes the box as four integers: the internal region of p, then the
+    9 or 12 arrays and the stream"""
+    it = fields[2].internal
+    check(getattr(_cabi.lib(), entry)(*_shallow_head(params, alpha, plan, fields), it.xstart, it.xstop, it.ystart, it.ystop,
+                                      *[f.device_ptr for f in fields], _stream_ptr(stream)))
+
+
+def _shallow_region(entry, params, alpha, fields, stream):
+    """the same for the periodic entries, which take p's internal region and the grid's boundary conditions in x and y"""
+    p = fields[2]
+    check(getattr(_cabi.lib(), entry)(*_shallow_head(params, alpha, None, fields), C.byref(p.internal),
+                                      *p.grid.boundary_conditions[:2], *[f.device_ptr for f in fields], _stream_ptr(stream)))
+
+
 def invoke_shallow_step(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_f64(C.byref(params), g.nx, g.ny, it.xstart, it.xstop,
-                                             it.ystart, it.ystop, u.device_ptr, v.device_ptr,
-                                             p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                             pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                             pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_f64", params, None, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_x2(params, u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2, stream=None):
     """TWO leapfrog steps in one launch (dlesm_shallow_step_x2_f64): level n+1 into unew / vnew / pnew, level n+2 into
     unew2 / vnew2 / pnew2 -- the bits of two invoke_shallow_step calls at 48 instead of 72 B/cell/step.  Time loop:
     (cur, old, new1, new2) <- (new2, new1, old, cur) after every call."""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_x2_f64(C.byref(params), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
-                                                *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2)],
-                                                _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_x2_f64", params, None, None, (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2), stream)
 
 
 def invoke_shallow_step_smooth_x2(params, alpha, u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream=None):
     """TWO filtered leapfrog steps (update + time_smooth, twice) in one launch (dlesm_shallow_step_smooth_x2_f64): level n+2 into
     unew2.., the filtered level n+1 into uold2..; inputs untouched.  Time loop: ping-pong (cur, old) <-> (unew2.., uold2..)."""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_smooth_x2_f64(
-        C.byref(params), alpha, g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
-        *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2)], _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_smooth_x2_f64", params, alpha, None, (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2), stream)
 
 
 def invoke_shallow_step_sw(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """the SW-offset form (the GOcean `shallow` staggering); periodic models follow it with
     apply_periodic_halos on the three new fields"""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_sw_f64(C.byref(params), g.nx, g.ny, it.xstart, it.xstop,
-                                                it.ystart, it.ystop, u.device_ptr, v.device_ptr,
-                                                p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                                pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                                pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_sw_f64", params, None, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 # ---- the GOcean `shallow` kernels one by one: what an unmodified generated PSy layer calls ----------------
@@ -706,50 +711,30 @@ GO_BC_PERIODIC_ = grid_mod.GO_BC_PERIODIC
 def invoke_shallow_step_sw_periodic(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """the SW-offset step over the internal region AND the periodic copies of the three new fields in one launch
     (== invoke_shallow_step_sw + apply_periodic_halos_multi, bit for bit)"""
-    g = p.grid
-    check(_cabi.lib().dlesm_shallow_step_sw_periodic_f64(C.byref(params), g.nx, g.ny, C.byref(p.internal),
-                                                         g.boundary_conditions[0], g.boundary_conditions[1],
-                                                         u.device_ptr, v.device_ptr, p.device_ptr, uold.device_ptr,
-                                                         vold.device_ptr, pold.device_ptr, unew.device_ptr,
-                                                         vnew.device_ptr, pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_region("dlesm_shallow_step_sw_periodic_f64", params, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_sw_x2_periodic(params, u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2, stream=None):
     """two steps of the SW-offset periodic model in one launch (== two invoke_shallow_step_sw_periodic calls)"""
-    g = p.grid
-    check(_cabi.lib().dlesm_shallow_step_sw_x2_periodic_f64(
-        C.byref(params), g.nx, g.ny, C.byref(p.internal), g.boundary_conditions[0], g.boundary_conditions[1],
-        *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2)], _stream_ptr(stream)))
+    _shallow_region("dlesm_shallow_step_sw_x2_periodic_f64", params, None, (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2), stream)
 
 
 def invoke_shallow_step_sw_smooth_x2_periodic(params, alpha, u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream=None):
     """two WHOLE time steps of the GOcean `shallow` benchmark (update + time_smooth + periodic images, twice) in one launch:
     level n+2 into unew2.., the filtered level n+1 into uold2..; ping-pong between the two sextets"""
-    g = p.grid
-    check(_cabi.lib().dlesm_shallow_step_sw_smooth_x2_periodic_f64(
-        C.byref(params), float(alpha), g.nx, g.ny, C.byref(p.internal), g.boundary_conditions[0], g.boundary_conditions[1],
-        *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2)], _stream_ptr(stream)))
+    _shallow_region("dlesm_shallow_step_sw_smooth_x2_periodic_f64", params, alpha, (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2), stream)
 
 
 def invoke_shallow_step_smooth(params, alpha, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """one whole leapfrog step of the GOcean benchmark in one launch (NE offset): the u/v/h update + time_smooth of the
     old level in place (== invoke_shallow_step + 3 x invoke_time_smooth, bit for bit).  Afterwards rotate u <- unew."""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_smooth_f64(C.byref(params), float(alpha), g.nx, g.ny, it.xstart, it.xstop, it.ystart,
-                                                    it.ystop, u.device_ptr, v.device_ptr, p.device_ptr, uold.device_ptr,
-                                                    vold.device_ptr, pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                                    pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_smooth_f64", params, alpha, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_sw_smooth_periodic(params, alpha, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """the same for the SW-offset periodic model: step + time_smooth + the periodic images of the new and of the filtered
     old level, one launch"""
-    g = p.grid
-    check(_cabi.lib().dlesm_shallow_step_sw_smooth_periodic_f64(C.byref(params), float(alpha), g.nx, g.ny, C.byref(p.internal),
-                                                                g.boundary_conditions[0], g.boundary_conditions[1],
-                                                                u.device_ptr, v.device_ptr, p.device_ptr, uold.device_ptr,
-                                                                vold.device_ptr, pold.device_ptr, unew.device_ptr,
-                                                                vnew.device_ptr, pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_region("dlesm_shallow_step_sw_smooth_periodic_f64", params, alpha, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def apply_periodic_halos(fld, stream=None):
@@ -772,55 +757,31 @@ def apply_periodic_halos_multi(fields, stream=None):
 def autotune_shallow(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """optional planning call for invoke_shallow_step: time the launch shapes / cache policies once
     for this field geometry (each trial is the same valid step) and keep the fastest"""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_autotune_f64(C.byref(params), g.nx, g.ny, it.xstart, it.xstop,
-                                                 it.ystart, it.ystop, u.device_ptr, v.device_ptr,
-                                                 p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                                 pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                                 pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_autotune_f64", params, None, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def autotune_shallow_sw(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """the planning call of the SW-offset step (invoke_shallow_step_sw / invoke_shallow_step_sw_periodic)"""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_autotune_sw_f64(C.byref(params), g.nx, g.ny, it.xstart, it.xstop,
-                                                    it.ystart, it.ystop, u.device_ptr, v.device_ptr,
-                                                    p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                                    pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                                    pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_autotune_sw_f64", params, None, None, (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_dm(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """distributed form: frame of the new fields, one grouped exchange of all three behind the
     interior; unew, vnew, pnew leave with valid halos"""
-    g, it = p.grid, p.internal
-    plan = grid_mod.halo_plan(g)
-    check(_cabi.lib().dlesm_shallow_step_dm(plan, C.byref(params), g.nx, g.ny, it.xstart, it.xstop,
-                                            it.ystart, it.ystop, u.device_ptr, v.device_ptr,
-                                            p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                            pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                            pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_dm", params, None, grid_mod.halo_plan(p.grid), (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_dm_pipelined(params, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None):
     """the distributed shallow-water step inside a time loop: returns with the exchange of the new
     fields in flight; the next such step waits for it on the device.  halo_join(grid) before anything
     else reads their halos."""
-    g, it = p.grid, p.internal
-    check(_cabi.lib().dlesm_shallow_step_dm_pipelined(grid_mod.halo_plan(g), C.byref(params), g.nx, g.ny,
-                                                      it.xstart, it.xstop, it.ystart, it.ystop, u.device_ptr,
-                                                      v.device_ptr, p.device_ptr, uold.device_ptr, vold.device_ptr,
-                                                      pold.device_ptr, unew.device_ptr, vnew.device_ptr,
-                                                      pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_dm_pipelined", params, None, grid_mod.halo_plan(p.grid), (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def invoke_shallow_step_smooth_dm(params, alpha, u, v, p, uold, vold, pold, unew, vnew, pnew, stream=None, pipelined=False):
     """the distributed step with the Asselin filter of the old level folded in (joined or time-loop form)"""
-    g, it = p.grid, p.internal
-    fn = _cabi.lib().dlesm_shallow_step_smooth_dm_pipelined if pipelined else _cabi.lib().dlesm_shallow_step_smooth_dm
-    check(fn(grid_mod.halo_plan(g), C.byref(params), float(alpha), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
-             u.device_ptr, v.device_ptr, p.device_ptr, uold.device_ptr, vold.device_ptr, pold.device_ptr, unew.device_ptr,
-             vnew.device_ptr, pnew.device_ptr, _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_smooth_dm_pipelined" if pipelined else "dlesm_shallow_step_smooth_dm", params, alpha,
+                 grid_mod.halo_plan(p.grid), (u, v, p, uold, vold, pold, unew, vnew, pnew), stream)
 
 
 def _x2_dm_plan(g, who):
@@ -837,22 +798,16 @@ def invoke_shallow_step_x2_dm(params, u, v, p, uold, vold, pold, unew, vnew, pne
     """TWO leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_x2_dm; halo_width = 2): level n+2
     into unew2.. with valid depth-2 halos, level n+1 into unew.. on the box grown by one cell towards every neighbour, which is
     all the next call reads of it.  Time loop: (cur, old, new1, new2) <- (new2, new1, old, cur) after every call."""
-    g, it = p.grid, p.internal
-    plan = _x2_dm_plan(g, "invoke_shallow_step_x2_dm")
-    check(_cabi.lib().dlesm_shallow_step_x2_dm(plan, C.byref(params), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
-                                               *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2)],
-                                               _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_x2_dm", params, None, _x2_dm_plan(p.grid, "invoke_shallow_step_x2_dm"),
+                 (u, v, p, uold, vold, pold, unew, vnew, pnew, unew2, vnew2, pnew2), stream)
 
 
 def invoke_shallow_step_smooth_x2_dm(params, alpha, u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2, stream=None):
     """TWO filtered leapfrog steps and ONE depth-2 exchange on a decomposed grid (dlesm_shallow_step_smooth_x2_dm; halo_width = 2):
     level n+2 into unew2.., the filtered level n+1 into uold2.., both with valid depth-2 halos; inputs untouched.  The filtered
     old level must carry valid depth-1 halos.  Time loop: ping-pong (cur, old) <-> (unew2.., uold2..)."""
-    g, it = p.grid, p.internal
-    plan = _x2_dm_plan(g, "invoke_shallow_step_smooth_x2_dm")
-    check(_cabi.lib().dlesm_shallow_step_smooth_x2_dm(
-        plan, C.byref(params), float(alpha), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop,
-        *[f.device_ptr for f in (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2)], _stream_ptr(stream)))
+    _shallow_box("dlesm_shallow_step_smooth_x2_dm", params, alpha, _x2_dm_plan(p.grid, "invoke_shallow_step_smooth_x2_dm"),
+                 (u, v, p, uold, vold, pold, unew2, vnew2, pnew2, uold2, vold2, pold2), stream)
 
 
 def halo_exchange_multi(fields, stream=None, dirs=_cabi.DIRS_ALL):

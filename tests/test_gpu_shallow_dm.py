@@ -438,3 +438,42 @@ def test_shallow_time_loop_over_the_mailboxes_captured_into_a_graph(D, nx, ny, a
     del graph
     D._cabi.check(L.dlesm_halo_plan_destroy(plan))
     g._halo_plan = None
+
+
+@pytest.mark.parametrize("xstop", [129, 130])
+@pytest.mark.parametrize("filtered", [False, True])
+def test_both_sides_of_the_lane_fit_on_an_odd_leading_dimension(D, filtered, xstop):
+    """dlesm_shallow_step_dm / _smooth_dm on raw 131 x 12 arrays (16-byte aligned bases) with a loop-back plan for the box
+    (2:xstop, 2:11): the interior of the one-launch form ends at column xstop - 2, the box of the other forms at xstop - 1,
+    on either side of the last whole two-column chunk of a row (2 * (ld / 2) - 1 = 129).  Every array, every cell, bit for
+    bit the oracle's step + exchange of the new level (+ time_smooth of the old one)."""
+    import torch
+    from dm_overhead import loopback_tables
+    L = D._cabi.lib()
+    ld, ny, box = 131, 12, (2, xstop, 2, 11)
+    t = loopback_tables(D, D._cabi.Region(xstop - 1, 10, *box))
+    oc = O.Comms()
+    C.memmove(C.byref(oc), C.byref(t), C.sizeof(oc))
+    rng = np.random.default_rng(131 * 12 + xstop)
+    H = [rng.random((ny, ld)) * 0.01 + (1.0 if k % 3 == 2 else -0.005) for k in range(6)] + [np.full((ny, ld), 9.0) for _ in range(3)]
+    Dv = [torch.from_numpy(h).cuda() for h in H]
+    assert all(d.data_ptr() % 16 == 0 for d in Dv)
+    prm = D.psy.shallow_params(1.0e5, 1.0e5, 20.0)
+    plan = C.c_void_p()
+    D._cabi.check(L.dlesm_halo_plan_create(C.byref(t), ld, ny, C.byref(plan)))
+    try:
+        ptrs = [C.c_void_p(d.data_ptr()) for d in Dv]
+        if filtered:
+            D._cabi.check(L.dlesm_shallow_step_smooth_dm(plan, C.byref(prm), 0.001, ld, ny, *box, *ptrs, None))
+        else:
+            D._cabi.check(L.dlesm_shallow_step_dm(plan, C.byref(prm), ld, ny, *box, *ptrs, None))
+        O.sw_step(prm, ld, box, *H)
+        for k in range(3):
+            assert O.exchange_all([H[6 + k]], [ld], [oc]) == 0
+            if filtered:
+                O.sw_kernel("time_smooth", False, ld, box, H[3 + k], [H[k], H[6 + k], H[3 + k]], 0.001)
+        torch.cuda.synchronize()
+        for k in range(9):
+            assert np.array_equal(Dv[k].cpu().numpy(), H[k]), k
+    finally:
+        D._cabi.check(L.dlesm_halo_plan_destroy(plan))

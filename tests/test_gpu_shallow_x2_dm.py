@@ -330,3 +330,42 @@ def test_x2_dm_refusals(D):
             D.psy.invoke_shallow_step_smooth_x2_dm(prm, ALPHA, *[S.F[n] for n in NAMES])
     finally:
         S.close()
+
+
+@pytest.mark.parametrize("xstop", [128, 129])
+def test_both_sides_of_the_lane_fit_on_an_odd_leading_dimension(D, xstop):
+    """dlesm_shallow_step_x2_dm on raw 131 x 12 arrays (16-byte aligned bases) with a loop-back depth-2 plan for the box
+    (3:xstop, 3:10): with an east neighbour the last computed column is xstop + 1, on either side of the last whole two-column
+    chunk of a row (2 * (ld / 2) - 1 = 129): the wave tiles at 128, two single steps at 129.  Level n+2 whole arrays, level
+    n+1 on the grown box, inputs untouched, bit for bit the oracle's step + depth-2 exchange, twice."""
+    import torch
+    from dm_overhead import loopback_tables
+    L = D._cabi.lib()
+    ld, ny, box = 131, 12, (3, xstop, 3, 10)
+    t = loopback_tables(D, D._cabi.Region(xstop - 2, 8, *box), 2)
+    oc = O.Comms()
+    C.memmove(C.byref(oc), C.byref(t), C.sizeof(oc))
+    rng = np.random.default_rng(131 * 12 + xstop)
+    H = [rng.random((ny, ld)) * 0.01 + (1.0 if k % 3 == 2 else -0.005) for k in range(6)] + [np.full((ny, ld), 9.0) for _ in range(6)]
+    for h in H[:6]:
+        assert O.exchange_all([h], [ld], [oc]) == 0
+    Dv = [torch.from_numpy(h).cuda() for h in H]
+    assert all(d.data_ptr() % 16 == 0 for d in Dv)
+    W = [h.copy() for h in H]
+    prm = D.psy.shallow_params(1.0e5, 1.0e5, 90.0)
+    for cur, old, new in ((W[:3], W[3:6], W[6:9]), (W[6:9], W[:3], W[9:])):
+        O.sw_step(prm, ld, box, *cur, *old, *new)
+        for a in new:
+            assert O.exchange_all([a], [ld], [oc]) == 0
+    plan = C.c_void_p()
+    D._cabi.check(L.dlesm_halo_plan_create(C.byref(t), ld, ny, C.byref(plan)))
+    try:
+        D._cabi.check(L.dlesm_shallow_step_x2_dm(plan, C.byref(prm), ld, ny, *box, *[C.c_void_p(d.data_ptr()) for d in Dv], None))
+        torch.cuda.synchronize()
+        grown = np.zeros((ny, ld), dtype=bool)
+        grown[box[2] - 2:box[3] + 1, box[0] - 2:box[1] + 1] = True
+        for k in range(12):
+            got, want = Dv[k].cpu().numpy(), (np.where(grown, W[k], H[k]) if 6 <= k < 9 else W[k])
+            assert np.array_equal(got, want), (k, _diff(got, want))
+    finally:
+        D._cabi.check(L.dlesm_halo_plan_destroy(plan))

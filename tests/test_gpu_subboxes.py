@@ -160,3 +160,38 @@ def test_two_filtered_steps_per_launch_on_subboxes(T, case):
         if k < 9:      # level n+2 is written on the box only, by both
             assert np.array_equal(np.where(_inbox(ny, ld, xs, xe, ys, ye), 0.0, A[k].cpu().numpy()),
                                   np.where(_inbox(ny, ld, xs, xe, ys, ye), 0.0, H[k])), ("cells outside the box written", k)
+
+
+@pytest.mark.parametrize("xstop", [129, 130])
+@pytest.mark.parametrize("entry", ["step", "step_sw", "smooth", "x2"])
+def test_both_sides_of_the_lane_fit_on_an_odd_leading_dimension(T, entry, xstop):
+    """ld = 131 (rows alternately 8-byte aligned), 16-byte aligned bases, two wave tiles per row: a box whose east column is
+    the last one of the last whole two-column chunk (xstop = 129 = 2 * (ld / 2) - 1) still takes the wave-tile kernel, one
+    column further (130) it takes the entry's other path.  Both bit for bit the oracle's, every array, every cell."""
+    torch, D, L = T
+    ld, ny, box = 131, 12, (2, xstop, 2, 11)
+    rng = np.random.default_rng(ld * 12 + xstop)
+    n = 12 if entry == "x2" else 9
+    H, Dv = zip(*[_rand(torch, rng, ny, ld, lo=(1.0 if k % 3 == 2 else -0.5)) for k in range(n)])
+    assert all(t.data_ptr() % 16 == 0 for t in Dv)
+    H = [h.copy() for h in H]
+    prm = D.psy.shallow_params(1.0e5, 1.0e5, 40.0)
+    ptrs = [_ptr(t) for t in Dv]
+    if entry == "step":
+        D._cabi.check(L.dlesm_shallow_step_f64(C.byref(prm), ld, ny, *box, *ptrs, None))
+        O.sw_step(prm, ld, box, *H)
+    elif entry == "step_sw":
+        D._cabi.check(L.dlesm_shallow_step_sw_f64(C.byref(prm), ld, ny, *box, *ptrs, None))
+        O.sw_step_sw(prm, ld, box, *H)
+    elif entry == "smooth":
+        D._cabi.check(L.dlesm_shallow_step_smooth_f64(C.byref(prm), 0.001, ld, ny, *box, *ptrs, None))
+        O.sw_step(prm, ld, box, *H)
+        for k in range(3):
+            O.sw_kernel("time_smooth", False, ld, box, H[3 + k], [H[k], H[6 + k], H[3 + k]], 0.001)
+    else:
+        D._cabi.check(L.dlesm_shallow_step_x2_f64(C.byref(prm), ld, ny, *box, *ptrs, None))
+        O.sw_step(prm, ld, box, *H[:6], *H[6:9])
+        O.sw_step(prm, ld, box, *H[6:9], *H[:3], *H[9:])
+    torch.cuda.synchronize()
+    for k in range(n):
+        assert np.array_equal(Dv[k].cpu().numpy(), H[k]), k
