@@ -109,6 +109,19 @@ class FieldStats(C.Structure):
                 f"count={self.count}, nonfinite={self.nonfinite})")
 
 
+class TracerCourant(C.Structure):
+    """dlesm_tracer_courant: what dlesm_tracer_courant_f64 says about a box"""
+    _fields_ = [("face_max", C.c_double), ("outflow_max", C.c_double), ("face_index", C.c_int64),
+                ("outflow_index", C.c_int64), ("face_over", C.c_int64), ("outflow_over", C.c_int64),
+                ("invalid", C.c_int64), ("wet", C.c_int64)]
+
+    def as8(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+    def __repr__(self):
+        return "TracerCourant(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_) + ")"
+
+
 MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
 
 
@@ -259,6 +272,8 @@ PROTOTYPES = {
     "dlesm_tracer_step_muscl_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_hancock_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_step_hancock_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_tracer_courant_async_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_d, _d, _vp, _vp]),
+    "dlesm_tracer_courant_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_d, _d, C.POINTER(TracerCourant), _vp]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

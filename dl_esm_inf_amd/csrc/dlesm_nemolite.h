@@ -121,6 +121,19 @@ __device__ __forceinline__ TracerCourant tracer_courant(const TracerFlow &f, dou
                          hancock_factor(fabs(f.r3) * (f.r3 >= 0.0 ? w : w_n)),
                          hancock_factor(fabs(f.r4) * (f.r4 >= 0.0 ? w_s : w))};
 }
+// The four face Courant numbers n1..n4 themselves (east, west, north, south), the arguments of hancock_factor above, for the
+// Courant check (dlesm_courant.hip).  tracer_courant keeps its own copy of the four products: routed
+// through this function the Hancock kernels compile to other instructions, and their code is to stay as it was measured.  A
+// change to one of the two is a change to both.
+struct TracerNumbers {
+    double n1, n2, n3, n4;
+};
+__device__ __forceinline__ TracerNumbers tracer_numbers(const TracerFlow &f, double w, double w_e, double w_w, double w_n,
+                                                        double w_s)
+{
+    return TracerNumbers{fabs(f.r1) * (f.r1 >= 0.0 ? w : w_e), fabs(f.r2) * (f.r2 >= 0.0 ? w_w : w),
+                         fabs(f.r3) * (f.r3 >= 0.0 ? w : w_n), fabs(f.r4) * (f.r4 >= 0.0 ? w_s : w)};
+}
 // tracer_point_muscl with the face factors g1..g4 in the place of 0.5.  g = 0.0 gives tracer_point's face value.
 __device__ __forceinline__ double tracer_point_hancock(const TracerFlow &f, const TracerCourant &g, double c, double c_e,
                                                        double c_w, double c_n, double c_s, double sx, double sx_e, double sx_w,

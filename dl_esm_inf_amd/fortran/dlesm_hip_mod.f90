@@ -65,6 +65,12 @@ module dlesm_hip_mod
      integer(c_int64_t) :: count, nonfinite
   end type field_stats_type
 
+  !> struct dlesm_tracer_courant (DESIGN.md section 6.14): 64 bytes.  The indices are 0-based linear, (j-1)*ld + (i-1); -1: none
+  type, bind(C) :: tracer_courant_type
+     real(c_double) :: face_max, outflow_max
+     integer(c_int64_t) :: face_index, outflow_index, face_over, outflow_over, invalid, wet
+  end type tracer_courant_type
+
   interface
      ! ---- host-side index maps -------------------------------------------
      function dlesm_alignment_from_env(alignment) bind(C, name="dlesm_alignment_from_env") result(rc)
@@ -873,6 +879,28 @@ module dlesm_hip_mod
        type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, ssha
        type(c_ptr), intent(in) :: c_in(*), c_out(*)
        integer(c_int), value :: ntracers
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     ! ---- the tracer schemes' Courant check (DESIGN.md section 6.14): the flow arrays of the tracer entries without ssha
+     function dlesm_tracer_courant_async_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, &
+          sshn_u, sshn_v, face_limit, outflow_limit, result_dev, stream) bind(C, name="dlesm_tracer_courant_async_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v
+       real(c_double), value :: face_limit, outflow_limit
+       type(c_ptr), value :: result_dev, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_tracer_courant_f64(rdt, ld, ny, xstart, xstop, ystart, ystop, tmask, area_t, un, vn, hu, hv, ht, sshn_t, &
+          sshn_u, sshn_v, face_limit, outflow_limit, result_host, stream) bind(C, name="dlesm_tracer_courant_f64") result(rc)
+       import :: c_int, c_ptr, c_double, tracer_courant_type
+       real(c_double), value :: rdt
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v
+       real(c_double), value :: face_limit, outflow_limit
+       type(tracer_courant_type), intent(out) :: result_host
        type(c_ptr), value :: stream
        integer(c_int) :: rc
      end function

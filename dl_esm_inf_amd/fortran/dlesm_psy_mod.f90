@@ -58,6 +58,7 @@ module dlesm_psy_mod
   public :: invoke_tracer_step, invoke_tracer_step_dm, invoke_tracer_step_muscl, invoke_tracer_step_muscl_dm
   public :: invoke_tracer_step_hancock, invoke_tracer_step_hancock_dm
   public :: invoke_nemolite_coupled_step_dm
+  public :: tracer_courant, tracer_courant_type
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -725,6 +726,81 @@ contains
                                         field_device_data(va), pin, pout, int(n, c_int), c_null_ptr)
     if (rc /= 0) call gocean_stop('invoke_nemolite_coupled_step_dm: ' // dlesm_error_text())
   end subroutine invoke_nemolite_coupled_step_dm
+
+  !> "May I take a tracer step with this rdt" (dlesm_tracer_courant_f64, DESIGN.md section 6.14): one read-only sweep over the
+  !! level-n flow, over the T internal region with the grid's mask and area_t, that needs no ssha.  res, the same on every rank:
+  !! the largest face Courant number of a wet cell exactly as invoke_tracer_step_hancock computes it, the largest outflow
+  !! number, how many wet cells reach face_limit (default 0.5) and outflow_limit (default 1.0), how many hold a number that is
+  !! not finite and >= 0, and how many are wet.  res%face_index / res%outflow_index are those of the owning rank -- the lowest
+  !! rank (1-based, get_rank) that holds a cell with the maximum, returned in face_rank / outflow_rank (0: none, index -1) --
+  !! 0-based linear in its local arrays: i = mod(index, nx) + 1, j = index / nx + 1.  Synchronous.  On a decomposed grid the
+  !! flow fields need valid depth-1 halos; collective there.
+  subroutine tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, res, face_limit, outflow_limit, face_rank, &
+                            outflow_rank)
+    use parallel_utils_mod, only: DIST_MEM_ENABLED, get_rank
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
+    type(tracer_courant_type), intent(out) :: res
+    real(go_wp), optional, intent(in) :: face_limit, outflow_limit
+    integer, optional, intent(out) :: face_rank, outflow_rank
+    real(c_double) :: fl, ol
+    integer(c_int) :: rc
+    integer :: fr, orank
+    fl = 0.5_c_double;  ol = 1.0_c_double
+    if (present(face_limit)) fl = real(face_limit, c_double)
+    if (present(outflow_limit)) ol = real(outflow_limit, c_double)
+    call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(hu);  call need_device(hv)
+    call need_device(sshn_t);  call need_device(sshn_u);  call need_device(sshn_v)
+    call grid_to_device(sshn_t%grid)
+    rc = dlesm_tracer_courant_f64(real(rdt, c_double), int(sshn_t%grid%nx, c_int), int(sshn_t%grid%ny, c_int), &
+                                  int(sshn_t%internal%xstart, c_int), int(sshn_t%internal%xstop, c_int), &
+                                  int(sshn_t%internal%ystart, c_int), int(sshn_t%internal%ystop, c_int), &
+                                  sshn_t%grid%tmask_device, sshn_t%grid%area_t_device, field_device_data(un), &
+                                  field_device_data(vn), field_device_data(hu), field_device_data(hv), field_device_data(ht), &
+                                  field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), fl, ol, &
+                                  res, c_null_ptr)
+    if (rc /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
+    fr = 0;  orank = 0
+    if (res%face_index >= 0) fr = get_rank()
+    if (res%outflow_index >= 0) orank = get_rank()
+    if (DIST_MEM_ENABLED) then
+       call place(res%face_max, res%face_index, fr)
+       call place(res%outflow_max, res%outflow_index, orank)
+       call total(res%face_over);  call total(res%outflow_over);  call total(res%invalid);  call total(res%wet)
+    end if
+    if (present(face_rank)) face_rank = fr
+    if (present(outflow_rank)) outflow_rank = orank
+  contains
+    ! the maximum over the ranks, the lowest rank that attains it and that rank's index (no NaN enters these collectives)
+    subroutine place(top, index, owner)
+      real(c_double), intent(inout) :: top
+      integer(c_int64_t), intent(inout) :: index
+      integer, intent(inout) :: owner
+      real(c_double) :: x, mine
+      logical :: have
+      x = top
+      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
+      have = index >= 0 .and. top == x
+      top = x
+      mine = -1.0e9_c_double
+      if (have) mine = -real(get_rank(), c_double)
+      if (dlesm_global_max_f64(mine) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
+      owner = 0
+      if (mine > -1.0e9_c_double) owner = nint(-mine)
+      x = 0.0_c_double
+      if (have .and. owner == get_rank()) x = real(index, c_double)            ! exact below 2**53
+      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
+      index = -1
+      if (owner > 0) index = nint(x, c_int64_t)
+    end subroutine place
+    subroutine total(n)
+      integer(c_int64_t), intent(inout) :: n
+      real(c_double) :: x
+      x = real(n, c_double)                                                    ! exact below 2**53
+      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
+      n = nint(x, c_int64_t)
+    end subroutine total
+  end subroutine tracer_courant
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

@@ -2,6 +2,7 @@
 (`do jj = fld%internal%ystart, ... ; do ji = ...; call kern_code(ji, jj, ...)`, form
 infrastructure_mod.f90:32-41) becomes one launch of the matching HIP kernel over the same
 index box."""
+import collections
 import ctypes as C
 import math
 
@@ -366,6 +367,89 @@ def invoke_tracer_step_hancock_dm(rdt, c_out, c_in, ssha, un, vn, ht, hu, hv, ss
     Stops on a grid with halo_width other than 2."""
     _tracer_step("invoke_tracer_step_hancock_dm", "dlesm_tracer_step_hancock_dm", 2, rdt, c_out, c_in, ssha, un, vn, ht, hu, hv,
                  sshn_t, sshn_u, sshn_v, stream=stream)
+
+
+TracerCourantResult = collections.namedtuple(
+    "TracerCourantResult", "face_max outflow_max face_at outflow_at face_over outflow_over invalid wet rdt_limit")
+
+
+def tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit=0.5, outflow_limit=1.0, stream=None):
+    """"may I take a tracer step with this rdt" (dlesm_tracer_courant_async_f64): one read-only sweep
+    over the level-n flow, over the T internal region with the grid's mask and area_t, that needs no ssha -- callable before
+    the flow step.  Returns a TracerCourantResult, the same on every rank:
+      face_max      the largest face Courant number of a wet cell, exactly as invoke_tracer_step_hancock computes it (the
+                    limited sweeps keep a profile's range while it is <= 1/2; the Hancock sweep falls back to the upwind face
+                    value where it is >= 1);
+      outflow_max   the largest outflow number of a wet cell (the upwind sweep keeps c >= 0 while it is <= 1);
+      face_at, outflow_at   (rank, i, j) of a cell that attains each: the lowest rank (1-based, parallel_mod.get_rank) that
+                    holds one and the local 1-based indices of its first such cell, or None;
+      face_over, outflow_over   wet cells with a face number >= face_limit / an outflow number >= outflow_limit;
+      invalid       wet cells in which a number is not finite and >= 0 (they enter no maximum);  wet: the wet cells;
+      rdt_limit     rdt * min(face_limit / face_max, outflow_limit / outflow_max), inf when both maxima are 0 -- an
+                    ESTIMATE of the largest rdt that keeps both limits: the numbers are linear in rdt only up to rounding.
+    On a decomposed grid the flow fields need valid depth-1 halos; collective there."""
+    import torch
+
+    from . import parallel_mod
+    g, it = sshn_t.grid, sshn_t.internal
+    L = _cabi.lib()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(s):                              # (device memory on the caller's stream: see field_mod.field_stats)
+        res = torch.empty(8, dtype=torch.float64, device=sshn_t.data.device)
+        check(L.dlesm_tracer_courant_async_f64(
+            float(rdt), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+            C.c_void_p(g.area_t_device.data_ptr()), *[f.device_ptr for f in (un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v)],
+            float(face_limit), float(outflow_limit), C.c_void_p(res.data_ptr()), _stream_ptr(s)))
+        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
+    r = _cabi.TracerCourant.from_buffer_copy(host.tobytes())
+    rank, many = parallel_mod.get_rank(), parallel_mod.get_num_ranks() > 1
+
+    def glob(fn, v):
+        if not many:
+            return v
+        val = C.c_double(v)
+        check(fn(C.byref(val)))
+        return val.value
+
+    def place(local_max, index):
+        """the global maximum and (rank, i, j) of the lowest rank that attains it"""
+        top = glob(L.dlesm_global_max_f64, local_max)       # (no NaN, nothing negative: see the record's definition)
+        mine = index >= 0 and local_max == top
+        owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if mine else -1.0e9))
+        i = int(glob(L.dlesm_global_sum_f64, float(index % g.nx + 1) if mine and rank == owner else 0.0))
+        j = int(glob(L.dlesm_global_sum_f64, float(index // g.nx + 1) if mine and rank == owner else 0.0))
+        return top, ((owner, i, j) if owner < 1.0e9 else None)
+
+    face_max, face_at = place(r.face_max, r.face_index)
+    outflow_max, outflow_at = place(r.outflow_max, r.outflow_index)
+    counts = [int(glob(L.dlesm_global_sum_f64, float(c)))   # exact below 2**53
+              for c in (r.face_over, r.outflow_over, r.invalid, r.wet)]
+    ratio = min(float(face_limit) / face_max if face_max > 0.0 else math.inf,
+                float(outflow_limit) / outflow_max if outflow_max > 0.0 else math.inf)
+    return TracerCourantResult(face_max, outflow_max, face_at, outflow_at, *counts,
+                               float(rdt) * ratio if ratio != math.inf else math.inf)
+
+
+def tracer_courant_check(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit=0.5, outflow_limit=1.0, stream=None):
+    """tracer_courant, and DlesmError -- on every rank -- when a wet cell holds a number that is not finite and >= 0, reaches
+    face_limit or reaches outflow_limit.  The message names which of the three, the value, and the rank and local 1-based
+    (i, j) of the cell that holds the maximum (an invalid cell enters no maximum: its count is all the record has).  Returns
+    the TracerCourantResult otherwise."""
+    r = tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit, outflow_limit, stream)
+
+    def where(at):
+        return "at local (i, j) = (%d, %d) on rank %d" % (at[1], at[2], at[0]) if at else "nowhere"
+    if r.invalid > 0:
+        why = "invalid: %d wet cell(s) hold a Courant number that is not finite and >= 0 (rdt = %r)" % (r.invalid, float(rdt))
+    elif r.face_over > 0:
+        why = "face_over: %d wet cell(s) reach face_limit = %r; face_max = %r %s" % (
+            r.face_over, float(face_limit), r.face_max, where(r.face_at))
+    elif r.outflow_over > 0:
+        why = "outflow_over: %d wet cell(s) reach outflow_limit = %r; outflow_max = %r %s" % (
+            r.outflow_over, float(outflow_limit), r.outflow_max, where(r.outflow_at))
+    else:
+        return r
+    raise _cabi.DlesmError(_cabi.EABORT, "tracer_courant_check: %s; rdt_limit = %r" % (why, r.rdt_limit))
 
 
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}

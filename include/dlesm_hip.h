@@ -1071,6 +1071,51 @@ int dlesm_tracer_step_hancock_dm(dlesm_halo_plan *plan, double rdt, int ld, int 
                                  const double *sshn_t, const double *sshn_u, const double *sshn_v, const double *ssha,
                                  const double *const *c_in, double *const *c_out, int ntracers, void *stream);
 
+/* The tracer schemes' Courant check: "may I take this step with this rdt".  One read-only sweep over
+ * the level-n flow (no ssha: callable before the flow step) that evaluates, in every wet T cell (tmask > 0) of the 1-based
+ * inclusive box, the four face Courant numbers n1..n4 of dlesm_tracer_step_hancock_f64 -- the same expression tree, bit for
+ * bit -- and the cell's outflow number, with on1..on4 = tmask != 0 at (i+1,j), (i-1,j), (i,j+1), (i,j-1):
+ *     valid(x) = x >= 0 && x <= DBL_MAX                               (a NaN, an infinity and a negative number fail it)
+ *     o1 = (on1 && r1 > 0) ?  r1 : 0      o2 = (on2 && r2 < 0) ? -r2 : 0
+ *     o3 = (on3 && r3 > 0) ?  r3 : 0      o4 = (on4 && r4 < 0) ? -r4 : 0
+ *     o  = (((o1 + o2) + o3) + o4) * w(i,j)        the upwind step keeps c >= 0 while o <= 1
+ *     m  = the largest valid n_k among the faces with on_k ("none" if there is no such face)
+ *     bad = !(w(i,j) > 0 && w(i,j) <= DBL_MAX) || (some on_k face has !valid(n_k)) || !valid(o)
+ * and reduces them to the record below.  Every member is exact: the record does not depend on the kernel form, the launch
+ * shape, alignment, the stream or repeats, and what land holds (a NaN in area_t, ht, sshn_t of a land cell, in un / vn on a
+ * face that touches land) changes no member.  An empty box and a box without a wet cell give {0, 0, -1, -1, 0, 0, 0, 0}. */
+typedef struct dlesm_tracer_courant {   /* 64 bytes, no padding */
+    double  face_max;       /* max of m over the wet cells of the box that have one; 0.0 if none (compare by value) */
+    double  outflow_max;    /* max of the valid o over the wet cells of the box; 0.0 if none */
+    int64_t face_index;     /* lowest 0-based linear index (j-1)*ld + (i-1) of a wet cell with m == face_max; -1 if none */
+    int64_t outflow_index;  /* the same for o == outflow_max */
+    int64_t face_over;      /* wet cells with an m >= face_limit */
+    int64_t outflow_over;   /* wet cells with a valid o >= outflow_limit */
+    int64_t invalid;        /* wet cells with bad */
+    int64_t wet;            /* wet cells of the box */
+} dlesm_tracer_courant;
+/* The array arguments are dlesm_tracer_step_f64's without ssha and the tracers (device memory, ny x ld, the box with a
+ * one-cell ring inside the array).  *result_dev (device memory) is written when `stream` gets there; the scratch is
+ * stream-ordered, nothing else is written, there are no floating-point atomics and the host is not synchronised.
+ * DLESM_EINVAL before anything is launched: a null pointer, a double array not 8-byte aligned or a mask not 4-byte aligned, a
+ * box that does not fit with its ring, a limit that is NaN or <= 0, a result_dev inside an input array, a stream that is
+ * being captured.  Even ld with 16-byte bases (8-byte for the mask) takes the wave-tile kernel, anything else -- and the HOOK
+ * key tracer_courant_kernel = 1 -- the one-cell-per-thread kernel.  There is no plan argument: the sweep exchanges nothing; on
+ * a decomposed grid the inputs need valid depth-1 halos and the caller combines the ranks' records. */
+int dlesm_tracer_courant_async_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                   const int *tmask, const double *area_t, const double *un, const double *vn,
+                                   const double *hu, const double *hv, const double *ht,
+                                   const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                                   double face_limit, double outflow_limit,
+                                   dlesm_tracer_courant *result_dev, void *stream);
+/* The synchronous twin: the same record in host memory; returns when it is there. */
+int dlesm_tracer_courant_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                             const int *tmask, const double *area_t, const double *un, const double *vn,
+                             const double *hu, const double *hv, const double *ht,
+                             const double *sshn_t, const double *sshn_u, const double *sshn_v,
+                             double face_limit, double outflow_limit,
+                             dlesm_tracer_courant *result_host, void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
