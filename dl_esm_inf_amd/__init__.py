@@ -11,7 +11,7 @@ Nothing here falls back to the CPU: without the built library the import fails, 
 every device entry point raises.
 """
 from . import _cabi
-from ._cabi import DlesmError, GoceanStop, FieldStats, TracerCourant  # noqa: F401
+from ._cabi import DlesmError, GoceanStop, FieldStats, TracerCourant, FlowCourant  # noqa: F401
 
 _cabi.lib()  # fail loudly, at import time, if the HIP extension is missing
 

@@ -122,6 +122,20 @@ class TracerCourant(C.Structure):
         return "TracerCourant(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_) + ")"
 
 
+class FlowCourant(C.Structure):
+    """dlesm_flow_courant: what dlesm_flow_courant_f64 says about a box"""
+    _fields_ = ([(n, C.c_double) for n in ("gravity_max", "advective_max", "viscous_max", "depth_min")] +
+                [(n, C.c_int64) for n in ("gravity_index", "advective_index", "viscous_index", "depth_index", "gravity_over",
+                                          "advective_over", "viscous_over", "shallow", "invalid", "wet")] +
+                [("reserved", C.c_int64 * 2)])
+
+    def as16(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_[:14]) + tuple(self.reserved)
+
+    def __repr__(self):
+        return "FlowCourant(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_[:14]) + ")"
+
+
 MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
 
 
@@ -274,6 +288,8 @@ PROTOTYPES = {
     "dlesm_tracer_step_hancock_dm": (_i, [_vp, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
     "dlesm_tracer_courant_async_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_d, _d, _vp, _vp]),
     "dlesm_tracer_courant_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_d, _d, C.POINTER(TracerCourant), _vp]),
+    "dlesm_flow_courant_async_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, _vp, _vp]),
+    "dlesm_flow_courant_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, C.POINTER(FlowCourant), _vp]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

@@ -17,10 +17,12 @@
 // courant_level: workgroup b combines records [b * 1024, (b + 1) * 1024) into one; launched until one record is left, and
 // that launch writes the caller's record (the empty maxima as 0.0 / -1).  No atomics; plain vector stores only.
 //
-// This translation unit holds copies of the reduction helpers it needs; it shares no kernel with the other entry points.
+// The (value, index) combine and the wave reductions are dlesm_wave_reduce.h's, shared with dlesm_flow_courant.hip; this
+// translation unit shares no kernel with the other entry points.
 #include <climits>
 
 #include "dlesm_nemolite.h"
+#include "dlesm_wave_reduce.h"
 
 namespace dlesm {
 
@@ -30,6 +32,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
+using namespace wavered;
 
 constexpr int TILE_CHUNKS = 63;       // chunks (2 columns) a wave owns; lane 63 only loads
 constexpr int LEVEL_CHUNK = 1024;     // records per workgroup of a level
@@ -52,14 +55,6 @@ struct Acc {
 __device__ __forceinline__ Acc acc_identity() { return Acc{-1.0, -1.0, NO_INDEX, NO_INDEX, 0, 0, 0, 0}; }
 
 __device__ __forceinline__ bool valid(double x) { return x >= 0.0 && x <= BIGGEST; }   // false for a NaN
-
-// (value, index) pairs under "the larger value, then the lower index"
-__device__ __forceinline__ void take(double &m, long long &at, double x, long long ix)
-{
-    const bool better = x > m || (x == m && ix < at);
-    m = better ? x : m;
-    at = better ? ix : at;
-}
 
 // one wet cell of the box (section 6.14); ix = its 0-based linear index.  The maxima go into a; what the cell adds to the four
 // counts comes back in one word, a byte each: wet | bad << 8 | (m >= face_limit) << 16 | (o >= outflow_limit) << 24
@@ -85,57 +80,6 @@ __device__ __forceinline__ int acc_cell(Acc &a, bool wet, long long ix, const Tr
 __device__ __forceinline__ void add_counts(Acc &a, int c)
 {
     a.wet += c & 0xff, a.bad += (c >> 8) & 0xff, a.over_f += (c >> 16) & 0xff, a.over_o += (c >> 24) & 0xff;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ long long dpp_i64(long long v)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(v & 0xffffffffLL), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, false);
-    return ((long long)hi << 32) | lo;
-}
-
-// A fixed reduction over the 64 lanes on the VALU (dlesm_stats.hip): within each row of 16 lanes a butterfly by DPP (xor 1,
-// xor 2, the half-row and row mirrors), then the four rows' values read into scalars.  The result is the same in every lane.
-__device__ __forceinline__ double wave_max_f64(double v)
-{
-    auto mx = [](double a, double b) { return b > a ? b : a; };      // no NaN gets here
-    v = mx(v, dpp_f64<0xB1>(v));                                       // quad_perm [1,0,3,2]
-    v = mx(v, dpp_f64<0x4E>(v));                                       // quad_perm [2,3,0,1]
-    v = mx(v, dpp_f64<0x141>(v));                                      // row_half_mirror
-    v = mx(v, dpp_f64<0x140>(v));                                      // row_mirror
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto row = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)); };
-    return mx(mx(row(0), row(16)), mx(row(32), row(48)));
-}
-template <bool MIN>
-__device__ __forceinline__ long long wave_i64(long long v)
-{
-    auto op = [](long long a, long long b) { return MIN ? (b < a ? b : a) : a + b; };
-    v = op(v, dpp_i64<0xB1>(v));
-    v = op(v, dpp_i64<0x4E>(v));
-    v = op(v, dpp_i64<0x141>(v));
-    v = op(v, dpp_i64<0x140>(v));
-    const int lo = (int)(v & 0xffffffffLL), hi = (int)(v >> 32);
-    auto row = [&](int l) {
-        return ((long long)__builtin_amdgcn_readlane(hi, l) << 32) | (unsigned)__builtin_amdgcn_readlane(lo, l);
-    };
-    return op(op(row(0), row(16)), op(row(32), row(48)));
-}
-__device__ __forceinline__ int wave_add_i32(int v)
-{
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, false);
-    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
 }
 
 // the maxima and their lowest indices over the wave; every lane must be active

@@ -1,0 +1,85 @@
+// The reduction pieces the two Courant checks share (dlesm_courant.hip; dlesm_flow_courant.hip,
+// section 6.15): (value, index) pairs under "the larger value, then the lower index", and fixed reductions over the 64 lanes
+// of a wave on the VALU (dlesm_stats.hip's scheme: within each row of 16 lanes a butterfly by DPP -- xor 1, xor 2, the
+// half-row and row mirrors -- then the four rows' values read into scalars).  The result is the same in every lane; every lane
+// of the wave must be active.  Everything here is exact (maxima, minima, integer sums), so the order plays no part.
+#ifndef DLESM_WAVE_REDUCE_H
+#define DLESM_WAVE_REDUCE_H
+
+#include <hip/hip_runtime.h>
+
+namespace dlesm {
+
+namespace wavered {
+
+// (value, index) pairs under "the larger value, then the lower index"
+__device__ __forceinline__ void take(double &m, long long &at, double x, long long ix)
+{
+    const bool better = x > m || (x == m && ix < at);
+    m = better ? x : m;
+    at = better ? ix : at;
+}
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false),
+                            __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false));
+}
+template <int CTRL>
+__device__ __forceinline__ long long dpp_i64(long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(v & 0xffffffffLL), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, false);
+    return ((long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ double wave_max_f64(double v)
+{
+    auto mx = [](double a, double b) { return b > a ? b : a; };      // no NaN gets here
+    v = mx(v, dpp_f64<0xB1>(v));                                       // quad_perm [1,0,3,2]
+    v = mx(v, dpp_f64<0x4E>(v));                                       // quad_perm [2,3,0,1]
+    v = mx(v, dpp_f64<0x141>(v));                                      // row_half_mirror
+    v = mx(v, dpp_f64<0x140>(v));                                      // row_mirror
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    auto row = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)); };
+    return mx(mx(row(0), row(16)), mx(row(32), row(48)));
+}
+template <bool MIN>
+__device__ __forceinline__ long long wave_i64(long long v)
+{
+    auto op = [](long long a, long long b) { return MIN ? (b < a ? b : a) : a + b; };
+    v = op(v, dpp_i64<0xB1>(v));
+    v = op(v, dpp_i64<0x4E>(v));
+    v = op(v, dpp_i64<0x141>(v));
+    v = op(v, dpp_i64<0x140>(v));
+    const int lo = (int)(v & 0xffffffffLL), hi = (int)(v >> 32);
+    auto row = [&](int l) {
+        return ((long long)__builtin_amdgcn_readlane(hi, l) << 32) | (unsigned)__builtin_amdgcn_readlane(lo, l);
+    };
+    return op(op(row(0), row(16)), op(row(32), row(48)));
+}
+// the sum of a word of packed counts: a wave tile owns at most 126 cells, so a byte holds each count's sum
+__device__ __forceinline__ int wave_add_i32(int v)
+{
+    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false);
+    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false);
+    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, false);
+    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, false);
+    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
+           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
+
+// a (maximum, lowest index) pair over the wave: `none` is the index of a lane that does not hold the maximum
+__device__ __forceinline__ void wave_pair(double &m, long long &at, long long none)
+{
+    const double top = wave_max_f64(m);
+    at = wave_i64<true>(m == top ? at : none);
+    m = top;
+}
+
+} // namespace wavered
+
+} // namespace dlesm
+
+#endif

@@ -71,6 +71,14 @@ module dlesm_hip_mod
      integer(c_int64_t) :: face_index, outflow_index, face_over, outflow_over, invalid, wet
   end type tracer_courant_type
 
+  !> struct dlesm_flow_courant (DESIGN.md section 6.15): 128 bytes.  The indices are 0-based linear, (j-1)*ld + (i-1); -1: none
+  type, bind(C) :: flow_courant_type
+     real(c_double) :: gravity_max, advective_max, viscous_max, depth_min
+     integer(c_int64_t) :: gravity_index, advective_index, viscous_index, depth_index
+     integer(c_int64_t) :: gravity_over, advective_over, viscous_over, shallow, invalid, wet
+     integer(c_int64_t) :: reserved(2)
+  end type flow_courant_type
+
   interface
      ! ---- host-side index maps -------------------------------------------
      function dlesm_alignment_from_env(alignment) bind(C, name="dlesm_alignment_from_env") result(rc)
@@ -901,6 +909,30 @@ module dlesm_hip_mod
        type(c_ptr), value :: tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v
        real(c_double), value :: face_limit, outflow_limit
        type(tracer_courant_type), intent(out) :: result_host
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     ! ---- the flow step's own stability check (DESIGN.md section 6.15)
+     function dlesm_flow_courant_async_f64(rdt, g, visc, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, ht, &
+          sshn_t, gravity_limit, advective_limit, viscous_limit, depth_limit, &
+          result_dev, stream) bind(C, name="dlesm_flow_courant_async_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       real(c_double), value :: rdt, g, visc
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn, ht, sshn_t
+       real(c_double), value :: gravity_limit, advective_limit, viscous_limit, depth_limit
+       type(c_ptr), value :: result_dev, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_flow_courant_f64(rdt, g, visc, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, ht, &
+          sshn_t, gravity_limit, advective_limit, viscous_limit, depth_limit, &
+          result_host, stream) bind(C, name="dlesm_flow_courant_f64") result(rc)
+       import :: c_int, c_ptr, c_double, flow_courant_type
+       real(c_double), value :: rdt, g, visc
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn, ht, sshn_t
+       real(c_double), value :: gravity_limit, advective_limit, viscous_limit, depth_limit
+       type(flow_courant_type), intent(out) :: result_host
        type(c_ptr), value :: stream
        integer(c_int) :: rc
      end function

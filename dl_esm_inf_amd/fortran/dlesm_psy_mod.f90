@@ -59,6 +59,7 @@ module dlesm_psy_mod
   public :: invoke_tracer_step_hancock, invoke_tracer_step_hancock_dm
   public :: invoke_nemolite_coupled_step_dm
   public :: tracer_courant, tracer_courant_type
+  public :: flow_courant, flow_courant_type
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -801,6 +802,93 @@ contains
       n = nint(x, c_int64_t)
     end subroutine total
   end subroutine tracer_courant
+
+  !> "May the flow step take this rdt" (dlesm_flow_courant_f64, DESIGN.md section 6.15): one read-only sweep over the level-n
+  !! flow, over the T internal region with the grid's mask, dx_t and dy_t.  res, the same on every rank: the largest
+  !! gravity-wave, advective and viscous number of a wet cell and the smallest water column, how many wet cells reach
+  !! gravity_limit (default 1), advective_limit (1) and viscous_limit (0.25), how many are no deeper than depth_limit (0), how
+  !! many are invalid and how many are wet.  g defaults to 9.80665 and visc to 0 -- pass the flow step's own.  The four indices
+  !! are those of the owning rank -- the lowest rank (1-based, get_rank) that holds a cell with the extreme, returned in
+  !! gravity_rank .. depth_rank (0: none, index -1) -- 0-based linear in its local arrays: i = mod(index, nx) + 1,
+  !! j = index / nx + 1.  Synchronous.  On a decomposed grid the fields need valid depth-1 halos; collective there.
+  subroutine flow_courant(rdt, un, vn, ht, sshn_t, res, g, visc, gravity_limit, advective_limit, viscous_limit, depth_limit, &
+                          gravity_rank, advective_rank, viscous_rank, depth_rank)
+    use parallel_utils_mod, only: DIST_MEM_ENABLED, get_rank
+    real(go_wp), intent(in) :: rdt
+    type(r2d_field), intent(inout), target :: un, vn, ht, sshn_t
+    type(flow_courant_type), intent(out) :: res
+    real(go_wp), optional, intent(in) :: g, visc, gravity_limit, advective_limit, viscous_limit, depth_limit
+    integer, optional, intent(out) :: gravity_rank, advective_rank, viscous_rank, depth_rank
+    real(c_double) :: gv, nu, gl, al, vl, dl, deep
+    integer(c_int) :: rc
+    integer :: gr, ar, vr, dr
+    gv = 9.80665_c_double;  nu = 0.0_c_double
+    gl = 1.0_c_double;  al = 1.0_c_double;  vl = 0.25_c_double;  dl = 0.0_c_double
+    if (present(g)) gv = real(g, c_double)
+    if (present(visc)) nu = real(visc, c_double)
+    if (present(gravity_limit)) gl = real(gravity_limit, c_double)
+    if (present(advective_limit)) al = real(advective_limit, c_double)
+    if (present(viscous_limit)) vl = real(viscous_limit, c_double)
+    if (present(depth_limit)) dl = real(depth_limit, c_double)
+    call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(sshn_t)
+    call grid_to_device(sshn_t%grid)
+    rc = dlesm_flow_courant_f64(real(rdt, c_double), gv, nu, int(sshn_t%grid%nx, c_int), int(sshn_t%grid%ny, c_int), &
+                                int(sshn_t%internal%xstart, c_int), int(sshn_t%internal%xstop, c_int), &
+                                int(sshn_t%internal%ystart, c_int), int(sshn_t%internal%ystop, c_int), &
+                                sshn_t%grid%tmask_device, sshn_t%grid%dx_t_device, sshn_t%grid%dy_t_device, &
+                                field_device_data(un), field_device_data(vn), field_device_data(ht), &
+                                field_device_data(sshn_t), gl, al, vl, dl, res, c_null_ptr)
+    if (rc /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
+    gr = 0;  ar = 0;  vr = 0;  dr = 0
+    if (res%gravity_index >= 0) gr = get_rank()
+    if (res%advective_index >= 0) ar = get_rank()
+    if (res%viscous_index >= 0) vr = get_rank()
+    if (res%depth_index >= 0) dr = get_rank()
+    if (DIST_MEM_ENABLED) then
+       call place(res%gravity_max, res%gravity_index, gr)
+       call place(res%advective_max, res%advective_index, ar)
+       call place(res%viscous_max, res%viscous_index, vr)
+       deep = -res%depth_min                                                     ! the minimum as the maximum of -d
+       call place(deep, res%depth_index, dr)
+       res%depth_min = -deep
+       call total(res%gravity_over);  call total(res%advective_over);  call total(res%viscous_over)
+       call total(res%shallow);  call total(res%invalid);  call total(res%wet)
+    end if
+    if (present(gravity_rank)) gravity_rank = gr
+    if (present(advective_rank)) advective_rank = ar
+    if (present(viscous_rank)) viscous_rank = vr
+    if (present(depth_rank)) depth_rank = dr
+  contains
+    ! the maximum over the ranks, the lowest rank that attains it and that rank's index (no NaN enters these collectives)
+    subroutine place(top, index, owner)
+      real(c_double), intent(inout) :: top
+      integer(c_int64_t), intent(inout) :: index
+      integer, intent(inout) :: owner
+      real(c_double) :: x, mine
+      logical :: have
+      x = top
+      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
+      have = index >= 0 .and. top == x
+      top = x
+      mine = -1.0e9_c_double
+      if (have) mine = -real(get_rank(), c_double)
+      if (dlesm_global_max_f64(mine) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
+      owner = 0
+      if (mine > -1.0e9_c_double) owner = nint(-mine)
+      x = 0.0_c_double
+      if (have .and. owner == get_rank()) x = real(index, c_double)            ! exact below 2**53
+      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
+      index = -1
+      if (owner > 0) index = nint(x, c_int64_t)
+    end subroutine place
+    subroutine total(n)
+      integer(c_int64_t), intent(inout) :: n
+      real(c_double) :: x
+      x = real(n, c_double)                                                    ! exact below 2**53
+      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
+      n = nint(x, c_int64_t)
+    end subroutine total
+  end subroutine flow_courant
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

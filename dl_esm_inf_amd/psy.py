@@ -452,6 +452,126 @@ def tracer_courant_check(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_l
     raise _cabi.DlesmError(_cabi.EABORT, "tracer_courant_check: %s; rdt_limit = %r" % (why, r.rdt_limit))
 
 
+FlowCourantResult = collections.namedtuple(
+    "FlowCourantResult", "gravity_max advective_max viscous_max depth_min gravity_at advective_at viscous_at depth_at "
+    "gravity_over advective_over viscous_over shallow invalid wet rdt_limit")
+
+
+def _flow_constants(who, g, visc, params):
+    """g and visc where the momentum wrappers take theirs: the caller's momentum_params, unless given by keyword"""
+    if g is None and params is not None:
+        g = params.g
+    if visc is None and params is not None:
+        visc = params.visc
+    if g is None or visc is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: g and visc, or params = psy.momentum_params(...)" % who)
+    return float(g), float(visc)
+
+
+def flow_courant(rdt, un, vn, ht, sshn_t, g=None, visc=None, gravity_limit=1.0, advective_limit=1.0, viscous_limit=0.25,
+                 depth_limit=0.0, params=None, stream=None):
+    """"may the flow step take this rdt" (dlesm_flow_courant_async_f64): one read-only sweep over the
+    level-n flow, over the T internal region with the grid's mask, dx_t and dy_t.  g and visc default to those of `params`, the
+    momentum_params the flow step is called with.  Returns a FlowCourantResult, the same on every rank:
+      gravity_max   the largest gravity-wave number rdt * sqrt(g d) * sqrt(1/dx^2 + 1/dy^2) of a wet cell, d = ht + sshn_t;
+      advective_max the largest advective number rdt * (max|u| / dx + max|v| / dy) over a cell's faces that do not touch land;
+      viscous_max   the largest viscous number rdt * visc * (1/dx^2 + 1/dy^2);  depth_min: the smallest water column d;
+      gravity_at .. depth_at   (rank, i, j) of a cell that attains each: the lowest rank (1-based, parallel_mod.get_rank) that
+                    holds one and the local 1-based indices of its first such cell, or None;
+      gravity_over, advective_over, viscous_over   wet cells with the number >= its limit;  shallow: with d <= depth_limit;
+      invalid       wet cells with a column that is not finite and > 0 or a number that is not finite and >= 0 (they enter
+                    nothing else);  wet: the wet cells;
+      rdt_limit     rdt * min(limit / maximum) over the three maxima that are not 0, inf when all are -- an ESTIMATE of the
+                    largest rdt that keeps the three limits: the numbers are linear in rdt only up to rounding.
+    On a decomposed grid the fields need valid depth-1 halos; collective there."""
+    import torch
+
+    from . import parallel_mod
+    gv, nu = _flow_constants("flow_courant", g, visc, params)
+    grid, it = sshn_t.grid, sshn_t.internal
+    L = _cabi.lib()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    limits = (float(gravity_limit), float(advective_limit), float(viscous_limit))
+    with torch.cuda.stream(s):                              # (device memory on the caller's stream: see field_mod.field_stats)
+        res = torch.empty(16, dtype=torch.float64, device=sshn_t.data.device)
+        check(L.dlesm_flow_courant_async_f64(
+            float(rdt), gv, nu, grid.nx, grid.ny, it.xstart, it.xstop, it.ystart, it.ystop, grid.tmask_device_ptr,
+            C.c_void_p(grid.dx_t_device.data_ptr()), C.c_void_p(grid.dy_t_device.data_ptr()),
+            *[f.device_ptr for f in (un, vn, ht, sshn_t)], *limits, float(depth_limit), C.c_void_p(res.data_ptr()),
+            _stream_ptr(s)))
+        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
+    r = _cabi.FlowCourant.from_buffer_copy(host.tobytes())
+    rank, many = parallel_mod.get_rank(), parallel_mod.get_num_ranks() > 1
+
+    def glob(fn, v):
+        if not many:
+            return v
+        val = C.c_double(v)
+        check(fn(C.byref(val)))
+        return val.value
+
+    def place(local_top, index):
+        """the global maximum and (rank, i, j) of the lowest rank that attains it (tracer_courant's rule)"""
+        top = glob(L.dlesm_global_max_f64, local_top)       # (no NaN enters these collectives)
+        mine = index >= 0 and local_top == top
+        owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if mine else -1.0e9))
+        i = int(glob(L.dlesm_global_sum_f64, float(index % grid.nx + 1) if mine and rank == owner else 0.0))
+        j = int(glob(L.dlesm_global_sum_f64, float(index // grid.nx + 1) if mine and rank == owner else 0.0))
+        return top, ((owner, i, j) if owner < 1.0e9 else None)
+
+    tops, ats = [], []
+    for top, index in ((r.gravity_max, r.gravity_index), (r.advective_max, r.advective_index),
+                       (r.viscous_max, r.viscous_index), (-r.depth_min, r.depth_index)):   # the minimum as a maximum of -d
+        top, at = place(top, index)
+        tops.append(top), ats.append(at)
+    tops[3] = -tops[3]
+    counts = [int(glob(L.dlesm_global_sum_f64, float(c)))   # exact below 2**53
+              for c in (r.gravity_over, r.advective_over, r.viscous_over, r.shallow, r.invalid, r.wet)]
+    ratio = min(lim / top if top > 0.0 else math.inf for lim, top in zip(limits, tops[:3]))
+    return FlowCourantResult(*tops, *ats, *counts, float(rdt) * ratio if ratio != math.inf else math.inf)
+
+
+def flow_courant_check(rdt, un, vn, ht, sshn_t, g=None, visc=None, gravity_limit=1.0, advective_limit=1.0,
+                       viscous_limit=0.25, depth_limit=0.0, params=None, stream=None):
+    """flow_courant, and DlesmError -- on every rank -- when a wet cell is invalid, reaches one of the three limits or is no
+    deeper than depth_limit.  The message names which, the value, and the rank and local 1-based (i, j) of the cell that
+    holds the extreme (an invalid cell enters no extreme: its count is all the record has).  Returns the FlowCourantResult
+    otherwise."""
+    r = flow_courant(rdt, un, vn, ht, sshn_t, g, visc, gravity_limit, advective_limit, viscous_limit, depth_limit, params,
+                     stream)
+
+    def where(at):
+        return "at local (i, j) = (%d, %d) on rank %d" % (at[1], at[2], at[0]) if at else "nowhere"
+    if r.invalid > 0:
+        why = "invalid: %d wet cell(s) hold a water column that is not finite and > 0 or a number that is not finite and " \
+              ">= 0 (rdt = %r)" % (r.invalid, float(rdt))
+    elif r.gravity_over > 0:
+        why = "gravity_over: %d wet cell(s) reach gravity_limit = %r; gravity_max = %r %s" % (
+            r.gravity_over, float(gravity_limit), r.gravity_max, where(r.gravity_at))
+    elif r.advective_over > 0:
+        why = "advective_over: %d wet cell(s) reach advective_limit = %r; advective_max = %r %s" % (
+            r.advective_over, float(advective_limit), r.advective_max, where(r.advective_at))
+    elif r.viscous_over > 0:
+        why = "viscous_over: %d wet cell(s) reach viscous_limit = %r; viscous_max = %r %s" % (
+            r.viscous_over, float(viscous_limit), r.viscous_max, where(r.viscous_at))
+    elif r.shallow > 0:
+        why = "shallow: %d wet cell(s) are no deeper than depth_limit = %r; depth_min = %r %s" % (
+            r.shallow, float(depth_limit), r.depth_min, where(r.depth_at))
+    else:
+        return r
+    raise _cabi.DlesmError(_cabi.EABORT, "flow_courant_check: %s; rdt_limit = %r" % (why, r.rdt_limit))
+
+
+def step_rdt_limit(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, g=None, visc=None, gravity_limit=1.0, advective_limit=1.0,
+                   viscous_limit=0.25, face_limit=0.5, outflow_limit=1.0, params=None, stream=None):
+    """the one call an adaptive time loop needs: flow_courant and tracer_courant on the same level-n fields, and the smaller
+    of their two rdt_limit estimates (inf when the flow is at rest on a grid without gravity waves to resolve: never, in
+    practice).  Nothing is raised for a limit that `rdt` itself passes; collective on a decomposed grid."""
+    flow = flow_courant(rdt, un, vn, ht, sshn_t, g, visc, gravity_limit, advective_limit, viscous_limit, 0.0, params, stream)
+    tracer = tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit, outflow_limit, stream)
+    return min(flow.rdt_limit, tracer.rdt_limit)
+
+
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
 
 

@@ -1116,6 +1116,55 @@ int dlesm_tracer_courant_f64(double rdt, int ld, int ny, int xstart, int xstop, 
                              double face_limit, double outflow_limit,
                              dlesm_tracer_courant *result_host, void *stream);
 
+/* The flow step's own stability check: "may the flow step take this rdt".  One read-only sweep over
+ * the level-n flow that evaluates, in every wet T cell (T = tmask > 0) of the 1-based inclusive box, every operation rounded
+ * in double in the order the parentheses give, sqrt and the two divisions correctly rounded, choices by select:
+ *     valid(x) = x >= 0.0 && x <= DBL_MAX                             (a NaN, an infinity and a negative number fail it)
+ *     d   = ht(i,j) + sshn_t(i,j)                                     the water column momentum and continuity use
+ *     ix  = 1.0 / dx_t(i,j)          iy = 1.0 / dy_t(i,j)             k2 = ix*ix + iy*iy
+ *     gw  = (rdt * sqrt(g * d)) * sqrt(k2)                            the gravity-wave number, both directions at once
+ *     on1 = T(i+1,j) != 0   on2 = T(i-1,j) != 0   on3 = T(i,j+1) != 0   on4 = T(i,j-1) != 0       (open faces count)
+ *     a1 = on1 ? fabs(un(i,j)) : 0.0      a2 = on2 ? fabs(un(i-1,j)) : 0.0
+ *     a3 = on3 ? fabs(vn(i,j)) : 0.0      a4 = on4 ? fabs(vn(i,j-1)) : 0.0
+ *     um = a1 >= a2 ? a1 : a2             vm = a3 >= a4 ? a3 : a4
+ *     adv = (rdt * um) * ix + (rdt * vm) * iy                         the advective number of the cell
+ *     vis = (rdt * visc) * k2                                         the viscous number (0.0 when visc == 0)
+ *     bad = !(d > 0.0 && d <= DBL_MAX) || !valid(a1) || !valid(a2) || !valid(a3) || !valid(a4)
+ *           || !valid(gw) || !valid(adv) || !valid(vis)
+ * and reduces them to the record below.  A bad wet cell adds to invalid and wet only, every other wet cell to every member.
+ * Every member is exact: the record does not depend on the kernel form, the launch shape, alignment, the stream or repeats,
+ * and what land holds (a NaN in un / vn on a face that touches land, anything in ht, sshn_t, dx_t, dy_t of a land cell)
+ * changes no member.  An empty box and a box without a wet cell give {0, 0, 0, +inf, -1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0}
+ * and read nothing. */
+typedef struct dlesm_flow_courant {     /* 128 bytes, no padding */
+    double  gravity_max, advective_max, viscous_max;    /* maxima over the wet, not-bad cells; 0.0 if none; compared by value */
+    double  depth_min;                                  /* min of d over the same cells; +infinity if none */
+    int64_t gravity_index, advective_index, viscous_index, depth_index;   /* lowest 0-based (j-1)*ld+(i-1) holding the extreme; -1 if none */
+    int64_t gravity_over, advective_over, viscous_over; /* cells with the number >= its limit */
+    int64_t shallow;                                    /* cells with d <= depth_limit */
+    int64_t invalid, wet;
+    int64_t reserved[2];                                /* written as 0 */
+} dlesm_flow_courant;
+/* The arrays are device memory, ny x ld, the box with a one-cell ring inside the array.  *result_dev (device memory) is
+ * written when `stream` gets there; the scratch is stream-ordered, nothing else is written, there are no atomics of any kind
+ * and the host is not synchronised.  DLESM_EINVAL before anything is launched: a null pointer, a double array not 8-byte
+ * aligned or a mask not 4-byte aligned, a box that does not fit with its ring, rdt, g or one of the three number limits NaN or
+ * <= 0, visc or depth_limit NaN or < 0, a result_dev inside an input array, a stream that is being captured.  Even ld with
+ * 16-byte bases (8-byte for the mask) takes the wave-tile kernel, anything else -- and the HOOK key flow_courant_kernel = 1 --
+ * the one-cell-per-thread kernel.  There is no plan argument: the sweep exchanges nothing; on a decomposed grid the inputs
+ * need valid depth-1 halos and the caller combines the ranks' records. */
+int dlesm_flow_courant_async_f64(double rdt, double g, double visc, int ld, int ny, int xstart, int xstop, int ystart,
+                                 int ystop, const int *tmask, const double *dx_t, const double *dy_t,
+                                 const double *un, const double *vn, const double *ht, const double *sshn_t,
+                                 double gravity_limit, double advective_limit, double viscous_limit, double depth_limit,
+                                 dlesm_flow_courant *result_dev, void *stream);
+/* The synchronous twin: the same record in host memory; returns when it is there. */
+int dlesm_flow_courant_f64(double rdt, double g, double visc, int ld, int ny, int xstart, int xstop, int ystart,
+                           int ystop, const int *tmask, const double *dx_t, const double *dy_t,
+                           const double *un, const double *vn, const double *ht, const double *sshn_t,
+                           double gravity_limit, double advective_limit, double viscous_limit, double depth_limit,
+                           dlesm_flow_courant *result_host, void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
