@@ -19,6 +19,8 @@ DIRS_ALL, DIRS_NO_DIAGONALS = 0xF, 0x10
 NORM_MAX, NORM_SUMSQ = 0, 1           # dlesm_stencil5_resid_f64
 STATS_MAX_FIELDS = 8                  # dlesm_field_stats_async_f64
 TRACER_MAX = 8                        # DLESM_TRACER_MAX (dlesm_tracer_step_f64)
+OUT_SSH, OUT_UT, OUT_VT, OUT_SPEED, OUT_KE, OUT_VORT, OUT_COUNT = range(7)   # DLESM_OUT_* (dlesm_flow_output_f64)
+OUT_SET, OUT_ADD = 0, 1
 TRACER_UPWIND, TRACER_MUSCL, TRACER_HANCOCK = 0, 1, 2   # scheme of dlesm_nemolite_coupled_step_dm
 LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
@@ -290,6 +292,7 @@ PROTOTYPES = {
     "dlesm_tracer_courant_f64": (_i, [_d, _i, _i, _i, _i, _i, _i] + [_vp] * 10 + [_d, _d, C.POINTER(TracerCourant), _vp]),
     "dlesm_flow_courant_async_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, _vp, _vp]),
     "dlesm_flow_courant_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, C.POINTER(FlowCourant), _vp]),
+    "dlesm_flow_output_f64": (_i, [_i, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [C.POINTER(_vp), _vp]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

@@ -150,6 +150,36 @@ __device__ __forceinline__ double tracer_point_hancock(const TracerFlow &f, cons
     return (f.h_old * c + (((F2 - F1) + F4) - F3) * f.q) / f.h_new;
 }
 
+// The model's output fields (dlesm_flow_output.hip) of a wet T cell, by DLESM_OUT_* number: the
+// sea-surface height, the velocities brought to the T point through section 6.10's face switches, their speed, the kinetic
+// energy of the column and the relative vorticity at the cell's NE corner.  u, v = un, vn at (i, j); _w, _e operands at
+// (i-1, j), (i+1, j), _s, _n at (i, j-1), (i, j+1); t_e .. t_s = tmask at the four neighbours, t_ne at (i+1, j+1).  `corner`
+// says whether v[5] may be stored: with the three neighbours non-land all four faces of the circulation are live.  VORT =
+// false leaves v[5] at 0.0 and reads none of v_e, u_n, t_ne, dxv, dxv_e, dyu, dyu_n.  Selects, never blends.
+struct FlowOutput {
+    double v[6];
+    bool corner;
+};
+template <bool VORT>
+__device__ __forceinline__ FlowOutput flow_output_point(double u, double u_w, double v, double v_s, double v_e, double u_n,
+                                                        double ht, double st, double dxv, double dxv_e, double dyu,
+                                                        double dyu_n, int t_e, int t_w, int t_n, int t_s, int t_ne)
+{
+    const double e = t_e != 0 ? u : 0.0, w = t_w != 0 ? u_w : 0.0;
+    const double n = t_n != 0 ? v : 0.0, s = t_s != 0 ? v_s : 0.0;
+    const double ut = 0.5 * (w + e), vt = 0.5 * (s + n);
+    const double q = ut * ut + vt * vt;
+    const double d = ht + st;
+    FlowOutput r{{st, ut, vt, sqrt(q), (0.5 * d) * q, 0.0}, false};
+    if constexpr (VORT) {
+        const double dvdx = (v_e - v) / (0.5 * (dxv + dxv_e));
+        const double dudy = (u_n - u) / (0.5 * (dyu + dyu_n));
+        r.v[5] = dvdx - dudy;
+        r.corner = t_e != 0 && t_n != 0 && t_ne != 0;
+    }
+    return r;
+}
+
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,
 // 1 = the one east (north) of it; ax = area_u (area_v) of the face
 __device__ __forceinline__ double ssh_point(long long t0, long long t1, double a0, double a1, double s0, double s1, double ax)

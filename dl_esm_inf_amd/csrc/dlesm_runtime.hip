@@ -59,7 +59,7 @@ static const struct { const char *key; int cls; } kKeys[] = {
     {"cont_nt", KEY_HOOK}, {"sw_smooth_ntl", KEY_HOOK},
     // ---- HOOK: fall-back kernels (unaligned bases, odd pitches, thin boxes) and the forms DLESM_DM_SAFE / a capture select
     {"j5_variant", KEY_HOOK}, {"sw_kernel", KEY_HOOK}, {"swk_kernel", KEY_HOOK}, {"s9_kernel", KEY_HOOK}, {"j5m_kernel", KEY_HOOK},
-    {"cont_kernel", KEY_HOOK}, {"mom_kernel", KEY_HOOK}, {"nemo_step_kernel", KEY_HOOK}, {"nemo_wet_form", KEY_HOOK}, {"tracer_kernel", KEY_HOOK}, {"tracer_muscl_kernel", KEY_HOOK}, {"tracer_hancock_kernel", KEY_HOOK}, {"tracer_courant_kernel", KEY_HOOK}, {"flow_courant_kernel", KEY_HOOK}, {"sw_wrap_fused", KEY_HOOK}, {"sw_smooth_fused", KEY_HOOK},
+    {"cont_kernel", KEY_HOOK}, {"mom_kernel", KEY_HOOK}, {"nemo_step_kernel", KEY_HOOK}, {"nemo_wet_form", KEY_HOOK}, {"tracer_kernel", KEY_HOOK}, {"tracer_muscl_kernel", KEY_HOOK}, {"tracer_hancock_kernel", KEY_HOOK}, {"tracer_courant_kernel", KEY_HOOK}, {"flow_courant_kernel", KEY_HOOK}, {"flow_output_kernel", KEY_HOOK}, {"sw_wrap_fused", KEY_HOOK}, {"sw_smooth_fused", KEY_HOOK},
     {"sw_x2_fused", KEY_HOOK}, {"sw_x2_dm_overlap", KEY_HOOK},
     {"util_rowseg", KEY_HOOK}, {"util_rowlinear", KEY_HOOK}, {"util_gather_linear", KEY_HOOK},
     {"j5_dm_fused", KEY_HOOK}, {"sw_dm_fused", KEY_HOOK}, {"s9_dm_fused", KEY_HOOK}, {"j5_dm_chain", KEY_HOOK}, {"sw_dm_chain", KEY_HOOK},

@@ -936,6 +936,19 @@ module dlesm_hip_mod
        type(c_ptr), value :: stream
        integer(c_int) :: rc
      end function
+     ! ---- the model's output fields (DESIGN.md section 6.16): mode 0 stores, 1 adds weight * value; out: six device pointers
+     !      in the order SSH, UT, VT, SPEED, KE, VORT, c_null_ptr = not wanted
+     function dlesm_flow_output_f64(mode, weight, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_v, dy_u, un, vn, ht, &
+          sshn_t, out, stream) bind(C, name="dlesm_flow_output_f64") result(rc)
+       import :: c_int, c_ptr, c_double
+       integer(c_int), value :: mode
+       real(c_double), value :: weight
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_v, dy_u, un, vn, ht, sshn_t
+       type(c_ptr), intent(in) :: out(*)
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)
      function dlesm_nemolite_coupled_step_dm(plan, wet, scheme, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, &
           vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, c_in, c_out, ntracers, stream) &

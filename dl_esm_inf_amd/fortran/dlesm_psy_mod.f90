@@ -60,6 +60,7 @@ module dlesm_psy_mod
   public :: invoke_nemolite_coupled_step_dm
   public :: tracer_courant, tracer_courant_type
   public :: flow_courant, flow_courant_type
+  public :: flow_output
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -889,6 +890,50 @@ contains
       n = nint(x, c_int64_t)
     end subroutine total
   end subroutine flow_courant
+
+  !> The model's output fields in one sweep (dlesm_flow_output_f64, DESIGN.md section 6.16): of the level-n flow, into the
+  !! T-point fields given -- ssh (sshn_t itself), ut and vt (the velocities brought to the T point, a face on land carrying
+  !! nothing), speed (their modulus), ke (0.5 * (ht + sshn_t) * (ut**2 + vt**2)) and vort (dv/dx - du/dy at the cell's NE
+  !! corner, stored only where the cells east, north and north-east are not land).  Without weight the values are stored; with
+  !! it weight * value is added to what the fields hold (a time mean over nsteps: weight = 1 / nsteps into zeroed fields).
+  !! Over the T internal region with the grid's mask, dx_v and dy_u; land and open cells and every halo keep their content.
+  !! Asynchronous on the default stream.  On a decomposed grid un, vn and the mask need valid depth-1 halos, corners included
+  !! (exchange_mask_halos fills the mask's); nothing is exchanged and the call is not collective.
+  subroutine flow_output(un, vn, ht, sshn_t, ssh, ut, vt, speed, ke, vort, weight)
+    type(r2d_field), intent(inout), target :: un, vn, ht, sshn_t
+    type(r2d_field), optional, intent(inout), target :: ssh, ut, vt, speed, ke, vort
+    real(go_wp), optional, intent(in) :: weight
+    type(c_ptr) :: out(6)
+    integer(c_int) :: rc, mode
+    real(c_double) :: w
+    out = c_null_ptr
+    if (present(ssh)) call want(ssh, 1)
+    if (present(ut)) call want(ut, 2)
+    if (present(vt)) call want(vt, 3)
+    if (present(speed)) call want(speed, 4)
+    if (present(ke)) call want(ke, 5)
+    if (present(vort)) call want(vort, 6)
+    mode = 0_c_int;  w = 0.0_c_double
+    if (present(weight)) then
+       mode = 1_c_int;  w = real(weight, c_double)
+    end if
+    call need_device(un);  call need_device(vn);  call need_device(ht);  call need_device(sshn_t)
+    call grid_to_device(sshn_t%grid)
+    rc = dlesm_flow_output_f64(mode, w, int(sshn_t%grid%nx, c_int), int(sshn_t%grid%ny, c_int), &
+                               int(sshn_t%internal%xstart, c_int), int(sshn_t%internal%xstop, c_int), &
+                               int(sshn_t%internal%ystart, c_int), int(sshn_t%internal%ystop, c_int), &
+                               sshn_t%grid%tmask_device, sshn_t%grid%dx_v_device, sshn_t%grid%dy_u_device, &
+                               field_device_data(un), field_device_data(vn), field_device_data(ht), &
+                               field_device_data(sshn_t), out, c_null_ptr)
+    if (rc /= 0) call gocean_stop('flow_output: ' // dlesm_error_text())
+  contains
+    subroutine want(f, k)
+      type(r2d_field), intent(inout), target :: f
+      integer, intent(in) :: k
+      call need_device(f)
+      out(k) = field_device_data(f)
+    end subroutine want
+  end subroutine flow_output
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

@@ -8,7 +8,7 @@ import math
 
 from . import _cabi, grid_mod
 from ._cabi import SwParams, check
-from .field_mod import _stream_ptr
+from .field_mod import GO_T_POINTS, _stream_ptr
 
 
 def invoke_jacobi5(out_fld, in_fld, stream=None):
@@ -570,6 +570,39 @@ def step_rdt_limit(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, g=None, visc
     flow = flow_courant(rdt, un, vn, ht, sshn_t, g, visc, gravity_limit, advective_limit, viscous_limit, 0.0, params, stream)
     tracer = tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit, outflow_limit, stream)
     return min(flow.rdt_limit, tracer.rdt_limit)
+
+
+def flow_output(un, vn, ht, sshn_t, ssh=None, ut=None, vt=None, speed=None, ke=None, vort=None, weight=None, stream=None):
+    """the model's output fields in one sweep (dlesm_flow_output_f64): of the level-n flow, into the
+    T-point fields given -- ssh (sshn_t itself), ut and vt (the velocities brought to the T point, a face on land carrying
+    nothing), speed (their modulus), ke (0.5 * (ht + sshn_t) * (ut^2 + vt^2)) and vort (dv/dx - du/dy at the cell's NE corner,
+    stored only where the cells east, north and north-east are not land).  weight = None stores the values; a number adds
+    weight * value to what the fields hold (a time mean over nsteps: weight = 1 / nsteps into zeroed fields).  Over the T
+    internal region with the grid's mask, dx_v and dy_u; land and open cells and every halo keep their content.  ht may be
+    None unless ke is wanted, sshn_t unless ssh or ke is.  On a decomposed grid un, vn and the mask need valid depth-1 halos,
+    corners included (grid_mod.exchange_mask_halos fills the mask's); nothing is exchanged and the call is not collective."""
+    who = "flow_output"
+    outs = (ssh, ut, vt, speed, ke, vort)
+    first = next((f for f in outs if f is not None), None)
+    if first is None:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: no output field" % who)
+    g, it = first.grid, first.internal
+    for f in outs:
+        if f is not None and (f.grid is not g or f.defined_on != GO_T_POINTS):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: the outputs are T-point fields of one grid" % who)
+    if un.grid is not g or vn.grid is not g:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un, vn and the outputs are fields of one grid" % who)
+    pout = (C.c_void_p * _cabi.OUT_COUNT)(*[f.device_ptr if f is not None else None for f in outs])
+    need_st, need_ht = ssh is not None or ke is not None, ke is not None
+    if (need_st and sshn_t is None) or (need_ht and ht is None):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ke needs ht and sshn_t, ssh needs sshn_t" % who)
+    metric = vort is not None
+    check(_cabi.lib().dlesm_flow_output_f64(
+        _cabi.OUT_SET if weight is None else _cabi.OUT_ADD, 0.0 if weight is None else float(weight), g.nx, g.ny, it.xstart,
+        it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+        C.c_void_p(g.dx_v_device.data_ptr()) if metric else None, C.c_void_p(g.dy_u_device.data_ptr()) if metric else None,
+        un.device_ptr, vn.device_ptr, ht.device_ptr if need_ht else None, sshn_t.device_ptr if need_st else None, pout,
+        _stream_ptr(stream)))
 
 
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}

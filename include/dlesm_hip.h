@@ -1165,6 +1165,40 @@ int dlesm_flow_courant_f64(double rdt, double g, double visc, int ld, int ny, in
                            double gravity_limit, double advective_limit, double viscous_limit, double depth_limit,
                            dlesm_flow_courant *result_host, void *stream);
 
+/* The model's output fields: what NEMOLite2D's model_write puts out -- the sea-surface height and
+ * the velocities brought to the T points -- and what every user derives from them, in one sweep over the level-n flow.  In
+ * every wet T cell (T = tmask > 0) of the 1-based inclusive box, every operation rounded in double in the order the
+ * parentheses give, sqrt and the two divisions correctly rounded, choices by select:
+ *     e = T(i+1,j) != 0 ? un(i,j)   : 0.0      w = T(i-1,j) != 0 ? un(i-1,j) : 0.0     (section 6.10's face switches)
+ *     n = T(i,j+1) != 0 ? vn(i,j)   : 0.0      s = T(i,j-1) != 0 ? vn(i,j-1) : 0.0
+ *     ut = 0.5 * (w + e)      vt = 0.5 * (s + n)      q = ut*ut + vt*vt      d = ht(i,j) + sshn_t(i,j)
+ *     corner = T(i+1,j) != 0 && T(i,j+1) != 0 && T(i+1,j+1) != 0
+ *     dvdx = (vn(i+1,j) - vn(i,j)) / (0.5 * (dx_v(i,j) + dx_v(i+1,j)))
+ *     dudy = (un(i,j+1) - un(i,j)) / (0.5 * (dy_u(i,j) + dy_u(i,j+1)))
+ *     SSH = sshn_t(i,j)   UT = ut   VT = vt   SPEED = sqrt(q)   KE = (0.5 * d) * q   VORT = dvdx - dudy  (only where corner)
+ * DLESM_OUT_SET stores out[k](i,j) = value[k]; DLESM_OUT_ADD stores out[k](i,j) = out[k](i,j) + weight * value[k], two rounded
+ * operations (a time mean: weight = 1/nsteps into a zeroed array).  Land and open cells are never written, VORT neither in a
+ * wet cell with land to the east, north or north-east, and nothing outside the box: such a cell keeps its content.  A NaN in
+ * un / vn on a face that touches land and anything in ht, sshn_t, dx_v, dy_u of a land cell reaches no written cell (VORT
+ * reads dx_v(i+1,j) and dy_u(i,j+1), and stores, only under corner); a special value in a wet cell's own operands goes where
+ * IEEE sends it; a face between two open cells is read as it is.
+ * out: a HOST array of DLESM_OUT_COUNT device pointers, NULL = not wanted; passed to the kernel by value.  The arrays are
+ * device memory, ny x ld, the box with a one-cell ring inside the array.  An array no wanted output reads is not read and may
+ * be NULL: ht serves KE, sshn_t SSH and KE, dx_v and dy_u VORT; tmask, un and vn are always needed.  weight is ignored by SET.
+ * Asynchronous on `stream`, no scratch, no host state: the call may be captured into a graph.  There is no plan argument: the
+ * sweep exchanges nothing; on a decomposed grid the inputs and the mask need valid depth-1 halos, corners included.  An empty
+ * box launches nothing and returns 0.  Any 8-byte-aligned bases and any ld give the same bits: even ld with 16-byte bases
+ * (8-byte for the mask) takes the wave-tile kernel, anything else -- and the HOOK key flow_output_kernel = 1 -- the
+ * one-cell-per-thread kernel.  DLESM_EINVAL before anything is launched: a mode other than the two, DLESM_OUT_ADD with a NaN
+ * or infinite weight, a null out or every entry of it null, a needed input null, a double array not 8-byte aligned or a mask
+ * not 4-byte aligned, a box that does not fit with its ring, an out[k] that overlaps the mask, an input that is not NULL or
+ * another out entry. */
+enum { DLESM_OUT_SSH = 0, DLESM_OUT_UT, DLESM_OUT_VT, DLESM_OUT_SPEED, DLESM_OUT_KE, DLESM_OUT_VORT, DLESM_OUT_COUNT };
+enum { DLESM_OUT_SET = 0, DLESM_OUT_ADD = 1 };
+int dlesm_flow_output_f64(int mode, double weight, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                          const int *tmask, const double *dx_v, const double *dy_u, const double *un, const double *vn,
+                          const double *ht, const double *sshn_t, double *const *out, void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
