@@ -21,6 +21,8 @@ STATS_MAX_FIELDS = 8                  # dlesm_field_stats_async_f64
 TRACER_MAX = 8                        # DLESM_TRACER_MAX (dlesm_tracer_step_f64)
 OUT_SSH, OUT_UT, OUT_VT, OUT_SPEED, OUT_KE, OUT_VORT, OUT_COUNT = range(7)   # DLESM_OUT_* (dlesm_flow_output_f64)
 OUT_SET, OUT_ADD = 0, 1
+DRIFTER_ACTIVE, DRIFTER_LEFT, DRIFTER_OPEN, DRIFTER_GROUNDED = range(4)      # DLESM_DRIFTER_* (dlesm_drifter_step_f64)
+DRIFTER_MAX_SUB, DRIFTER_MAX_FIELDS = 1024, 8
 TRACER_UPWIND, TRACER_MUSCL, TRACER_HANCOCK = 0, 1, 2   # scheme of dlesm_nemolite_coupled_step_dm
 LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
@@ -293,6 +295,13 @@ PROTOTYPES = {
     "dlesm_flow_courant_async_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, _vp, _vp]),
     "dlesm_flow_courant_f64": (_i, [_d, _d, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_d, _d, _d, _d, C.POINTER(FlowCourant), _vp]),
     "dlesm_flow_output_f64": (_i, [_i, _d, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [C.POINTER(_vp), _vp]),
+    "dlesm_drifter_step_f64": (_i, [_d, _i, _i, _i, _i, _i, _i, _i] + [_vp] * 5 + [C.c_longlong] + [_vp] * 4),
+    "dlesm_drifter_sample_f64": (_i, [_i] * 6 + [C.c_longlong] + [_vp] * 3 + [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
+    "dlesm_drifters_create": (_i, [C.c_longlong, C.POINTER(_vp)]),
+    "dlesm_drifters_put": (_i, [_vp, _vp, _vp, _vp]),
+    "dlesm_drifters_get": (_i, [_vp, _vp, _vp, _vp]),
+    "dlesm_drifters_arrays": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "dlesm_drifters_destroy": (_i, [_vp]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

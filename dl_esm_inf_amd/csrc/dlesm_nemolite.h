@@ -1,6 +1,7 @@
 // The point expressions of the NEMOLite2D-class kernels (DESIGN.md sections 5.10 and 6.5), shared by every entry that
 // evaluates them -- continuity (dlesm_continuity.hip), momentum and next_ssh* (dlesm_momentum.hip), the one-sweep time
-// step (dlesm_nemolite_step.hip) and tracer transport (dlesm_tracer.hip) -- so that the entries cannot drift apart.  Every
+// step (dlesm_nemolite_step.hip), tracer transport (dlesm_tracer.hip), the output fields (dlesm_flow_output.hip) and the
+// drifters (dlesm_drifter.hip) -- so that the entries cannot drift apart.  Every
 // operation is rounded in double precision in the order the parentheses give: the sources that include this header are
 // built with -ffp-contract=off and no expression here replaces a division by a reciprocal.
 #pragma once
@@ -178,6 +179,63 @@ __device__ __forceinline__ FlowOutput flow_output_point(double u, double u_w, do
         r.corner = t_e != 0 && t_n != 0 && t_ne != 0;
     }
     return r;
+}
+
+// Drifters (dlesm_drifter.hip).  A particle's position (x, y) is in local index coordinates: T cell
+// (i, j), 1-based, covers [i, i+1) x [j, j+1); un(i-1, j) and un(i, j) live on its west and east face, vn(i, j-1) and
+// vn(i, j) on its south and north face.  DrifterBox holds the box's bounds as doubles: inbox is evaluated in double BEFORE
+// any conversion to an integer, so a NaN or an infinity is "not in the box" and is never cast.
+struct DrifterBox {
+    double x_lo, x_hi, y_lo, y_hi;            // xstart, xstop + 1, ystart, ystop + 1
+    __host__ __device__ bool has(double x, double y) const { return x >= x_lo && x < x_hi && y >= y_lo && y < y_hi; }
+};
+// what one velocity evaluation reads of cell (i, j): the four neighbour masks, the four faces, the two metrics
+struct DrifterCell {
+    int t_e, t_w, t_n, t_s;
+    double u_e, u_w, v_n, v_s, dx, dy;
+};
+struct DrifterMove {
+    double kx, ky;
+};
+// the displacement of one substep of h seconds, in cells, at (x, y) inside cell (i, j): section 6.10's face switches (the
+// ones flow_output_point uses), linear between the faces.  Selects, never blends: a face that touches land carries nothing.
+__device__ __forceinline__ DrifterMove drifter_vel(double h, double x, double y, int i, int j, const DrifterCell &c)
+{
+    const double ue = c.t_e != 0 ? c.u_e : 0.0, uw = c.t_w != 0 ? c.u_w : 0.0;
+    const double vn = c.t_n != 0 ? c.v_n : 0.0, vs = c.t_s != 0 ? c.v_s : 0.0;
+    const double a = x - (double)i, b = y - (double)j;
+    const double up = uw + (ue - uw) * a, vp = vs + (vn - vs) * b;
+    return DrifterMove{(h * up) / c.dx, (h * vp) / c.dy};
+}
+// One substep of a particle at (x, y) in the wet cell (i, j): the midpoint rule with an Euler fallback where the midpoint is
+// outside the box or not on a wet cell.  cell(i, j) loads the DrifterCell of a cell of the box -- every load of it issued
+// before any is used --, mask(i, j) loads T there.  On return status says what became of the particle; (x, y) and (i, j) are
+// the new position and its cell unless the move ended on land (GROUNDED keeps the last wet position).  The destination's
+// mask is the next substep's own-cell mask: ACTIVE on return means (i, j) is wet.
+template <class CF, class TF>
+__device__ __forceinline__ int drifter_substep(double h, const DrifterBox &box, double &x, double &y, int &i, int &j, CF cell,
+                                               TF mask)
+{
+    const DrifterMove k1 = drifter_vel(h, x, y, i, j, cell(i, j));
+    const double xm = x + 0.5 * k1.kx, ym = y + 0.5 * k1.ky;
+    const bool in_m = box.has(xm, ym);
+    // a midpoint outside the box is evaluated at the particle's own place (always a cell of the box) and then not used
+    const double xe = in_m ? xm : x, ye = in_m ? ym : y;
+    const int im = (int)floor(xe), jm = (int)floor(ye);
+    const int tm = mask(im, jm);
+    const DrifterMove km = drifter_vel(h, xe, ye, im, jm, cell(im, jm));
+    const bool mid = in_m && tm > 0;
+    const double k2x = mid ? km.kx : k1.kx, k2y = mid ? km.ky : k1.ky;
+    const double xn = x + k2x, yn = y + k2y;
+    if (!box.has(xn, yn)) {
+        x = xn, y = yn;
+        return DLESM_DRIFTER_LEFT;
+    }
+    const int in = (int)floor(xn), jn = (int)floor(yn);
+    const int tn = mask(in, jn);
+    if (tn == 0) return DLESM_DRIFTER_GROUNDED;
+    x = xn, y = yn, i = in, j = jn;
+    return tn < 0 ? DLESM_DRIFTER_OPEN : DLESM_DRIFTER_ACTIVE;
 }
 
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,

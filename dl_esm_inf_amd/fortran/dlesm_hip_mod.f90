@@ -79,6 +79,15 @@ module dlesm_hip_mod
      integer(c_int64_t) :: reserved(2)
   end type flow_courant_type
 
+  !> A set of drifters on the device (DESIGN.md section 6.17): the number of particles and the dlesm_drifters handle that
+  !! owns their positions and statuses (dlesm_psy_mod: drifters_create, drifters_get, drifters_free, drifter_step)
+  type :: drifters_type
+     integer(c_long_long) :: n = 0
+     type(c_ptr) :: handle = c_null_ptr
+  end type drifters_type
+  integer(c_int), parameter :: DLESM_DRIFTER_ACTIVE = 0, DLESM_DRIFTER_LEFT = 1, DLESM_DRIFTER_OPEN = 2, &
+                               DLESM_DRIFTER_GROUNDED = 3
+
   interface
      ! ---- host-side index maps -------------------------------------------
      function dlesm_alignment_from_env(alignment) bind(C, name="dlesm_alignment_from_env") result(rc)
@@ -947,6 +956,59 @@ module dlesm_hip_mod
        type(c_ptr), value :: tmask, dx_v, dy_u, un, vn, ht, sshn_t
        type(c_ptr), intent(in) :: out(*)
        type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     ! ---- drifters (DESIGN.md section 6.17): particles carried through the level-n flow, status 0 ACTIVE, 1 LEFT, 2 OPEN,
+     !      3 GROUNDED; px, py, status: device arrays of n elements (dlesm_drifters_arrays gives those of a set)
+     function dlesm_drifter_step_f64(h, nsub, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, n, px, py, &
+          status, stream) bind(C, name="dlesm_drifter_step_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       real(c_double), value :: h
+       integer(c_int), value :: nsub, ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: px, py, status, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_drifter_sample_f64(ld, ny, xstart, xstop, ystart, ystop, n, px, py, status, fields, out, nfields, &
+          stream) bind(C, name="dlesm_drifter_sample_f64") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: px, py, status
+       type(c_ptr), intent(in) :: fields(*), out(*)
+       integer(c_int), value :: nfields
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     ! the owner of the three arrays: create (status zeroed = all ACTIVE), put host -> device (status c_null_ptr = all
+     ! ACTIVE), get device -> host after waiting (c_null_ptr = skip), arrays (the device pointers), destroy
+     function dlesm_drifters_create(n, set) bind(C, name="dlesm_drifters_create") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       integer(c_long_long), value :: n
+       type(c_ptr), intent(out) :: set
+       integer(c_int) :: rc
+     end function
+     function dlesm_drifters_put(set, px, py, status) bind(C, name="dlesm_drifters_put") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: set, px, py, status
+       integer(c_int) :: rc
+     end function
+     function dlesm_drifters_get(set, px, py, status) bind(C, name="dlesm_drifters_get") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: set, px, py, status
+       integer(c_int) :: rc
+     end function
+     function dlesm_drifters_arrays(set, n, px, py, status) bind(C, name="dlesm_drifters_arrays") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       type(c_ptr), value :: set
+       integer(c_long_long), intent(out) :: n
+       type(c_ptr), intent(out) :: px, py, status
+       integer(c_int) :: rc
+     end function
+     function dlesm_drifters_destroy(set) bind(C, name="dlesm_drifters_destroy") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: set
        integer(c_int) :: rc
      end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)

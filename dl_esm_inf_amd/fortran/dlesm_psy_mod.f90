@@ -61,6 +61,8 @@ module dlesm_psy_mod
   public :: tracer_courant, tracer_courant_type
   public :: flow_courant, flow_courant_type
   public :: flow_output
+  public :: drifters_type, drifters_create, drifters_get, drifters_free, drifter_step
+  public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h
@@ -934,6 +936,95 @@ contains
       out(k) = field_device_data(f)
     end subroutine want
   end subroutine flow_output
+
+  !> A set of drifters on the device (DESIGN.md section 6.17): n particles at px, py in local index coordinates (T cell
+  !! (i, j) covers [i, i+1) x [j, j+1)), all ACTIVE unless status (0 ACTIVE, 1 LEFT, 2 OPEN, 3 GROUNDED) says otherwise.
+  subroutine drifters_create(set, px, py, status)
+    type(drifters_type), intent(inout) :: set
+    real(go_wp), intent(in), target :: px(:), py(:)
+    integer(c_int), optional, intent(in), target :: status(:)
+    real(c_double), allocatable, target :: x(:), y(:)
+    integer(c_int), allocatable, target :: s(:)
+    integer(c_int) :: rc
+    type(c_ptr) :: ps
+    if (c_associated(set%handle)) call drifters_free(set)
+    if (size(py) /= size(px)) call gocean_stop('drifters_create: px and py differ in size')
+    set%n = size(px, kind=c_long_long)
+    rc = dlesm_drifters_create(set%n, set%handle)
+    if (rc /= 0) call gocean_stop('drifters_create: ' // dlesm_error_text())
+    allocate(x(size(px)), y(size(px)))                    ! contiguous copies, whatever section the caller passed
+    x = real(px, c_double);  y = real(py, c_double)
+    ps = c_null_ptr
+    if (present(status)) then
+       if (size(status) /= size(px)) call gocean_stop('drifters_create: px and status differ in size')
+       allocate(s(size(px)))
+       s = status
+       ps = c_loc(s)
+    end if
+    rc = dlesm_drifters_put(set%handle, c_loc(x), c_loc(y), ps)
+    if (rc /= 0) call gocean_stop('drifters_create: ' // dlesm_error_text())
+  end subroutine drifters_create
+
+  !> The set's positions and statuses on the host, after waiting for the device
+  subroutine drifters_get(set, px, py, status)
+    type(drifters_type), intent(in) :: set
+    real(go_wp), intent(out) :: px(:), py(:)
+    integer(c_int), intent(out) :: status(:)
+    real(c_double), allocatable, target :: x(:), y(:)
+    integer(c_int), allocatable, target :: s(:)
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('drifters_get: the set has not been created')
+    if (size(px) /= set%n .or. size(py) /= set%n .or. size(status) /= set%n) &
+         call gocean_stop('drifters_get: px, py and status hold one element per particle')
+    allocate(x(set%n), y(set%n), s(set%n))
+    rc = dlesm_drifters_get(set%handle, c_loc(x), c_loc(y), c_loc(s))
+    if (rc /= 0) call gocean_stop('drifters_get: ' // dlesm_error_text())
+    px = real(x, go_wp);  py = real(y, go_wp);  status = s
+  end subroutine drifters_get
+
+  subroutine drifters_free(set)
+    type(drifters_type), intent(inout) :: set
+    integer(c_int) :: rc
+    if (c_associated(set%handle)) then
+       rc = dlesm_drifters_destroy(set%handle)
+       if (rc /= 0) call gocean_stop('drifters_free: ' // dlesm_error_text())
+    end if
+    set%handle = c_null_ptr
+    set%n = 0
+  end subroutine drifters_free
+
+  !> Carry the set through the level-n flow (dlesm_drifter_step_f64, DESIGN.md section 6.17): nsub substeps of h seconds by
+  !! the midpoint rule, in place, over the T internal region of un's grid with the grid's mask, dx_t and dy_t.  A particle
+  !! that leaves the region becomes LEFT and one that reaches an open cell OPEN, both at their new position; one whose move
+  !! would end on land becomes GROUNDED at its last wet position.  Asynchronous on the default stream.  On a decomposed grid
+  !! un, vn and the mask need valid depth-1 halos; nothing is exchanged and the call is not collective.
+  subroutine drifter_step(set, h, nsub, un, vn)
+    type(drifters_type), intent(inout) :: set
+    real(go_wp), intent(in) :: h
+    integer, intent(in) :: nsub
+    type(r2d_field), intent(inout), target :: un, vn
+    type(c_region) :: sub, box, whole
+    type(c_ptr) :: px, py, status
+    integer(c_long_long) :: n
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('drifter_step: the set has not been created')
+    call need_device(un);  call need_device(vn)
+    call grid_to_device(un%grid)
+    associate (g => un%grid)
+      associate (s => g%subdomain%internal)
+        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+      end associate
+      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
+                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
+      if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
+      rc = dlesm_drifters_arrays(set%handle, n, px, py, status)
+      if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
+      rc = dlesm_drifter_step_f64(real(h, c_double), int(nsub, c_int), int(g%nx, c_int), int(g%ny, c_int), box%xstart, &
+                                  box%xstop, box%ystart, box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, &
+                                  field_device_data(un), field_device_data(vn), n, px, py, status, c_null_ptr)
+    end associate
+    if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
+  end subroutine drifter_step
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

@@ -8,7 +8,7 @@ import math
 
 from . import _cabi, grid_mod
 from ._cabi import SwParams, check
-from .field_mod import GO_T_POINTS, _stream_ptr
+from .field_mod import GO_T_POINTS, _stream_ptr, field_bounds
 
 
 def invoke_jacobi5(out_fld, in_fld, stream=None):
@@ -603,6 +603,71 @@ def flow_output(un, vn, ht, sshn_t, ssh=None, ut=None, vt=None, speed=None, ke=N
         C.c_void_p(g.dx_v_device.data_ptr()) if metric else None, C.c_void_p(g.dy_u_device.data_ptr()) if metric else None,
         un.device_ptr, vn.device_ptr, ht.device_ptr if need_ht else None, sshn_t.device_ptr if need_st else None, pout,
         _stream_ptr(stream)))
+
+
+def _drifter_arrays(who, px, py, status):
+    import torch
+    if not (px.is_cuda and py.is_cuda and status.is_cuda and px.is_contiguous() and py.is_contiguous() and
+            status.is_contiguous()):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: px, py and status are contiguous CUDA tensors" % who)
+    if px.dtype != torch.float64 or py.dtype != torch.float64 or status.dtype != torch.int32:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: px and py are float64, status is int32" % who)
+    n = px.numel()
+    if py.numel() != n or status.numel() != n:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: px, py and status hold one element per particle" % who)
+    return n
+
+
+def drifter_step(h, px, py, status, un, vn, nsub=1, stream=None):
+    """carry particles through the level-n C-grid flow (dlesm_drifter_step_f64): nsub substeps of h
+    seconds by the midpoint rule, in place.  px, py: contiguous float64 CUDA tensors, positions in local index coordinates (T
+    cell (i, j), 1-based, covers [i, i+1) x [j, j+1)); status: a contiguous int32 CUDA tensor of _cabi.DRIFTER_* numbers, only
+    DRIFTER_ACTIVE particles are read or written.  A particle that leaves the T internal region becomes DRIFTER_LEFT and one
+    that reaches an open cell DRIFTER_OPEN, both at their new position; one whose move would end on land becomes
+    DRIFTER_GROUNDED at its last wet position.  Over the T internal region of un.grid with the grid's tmask, dx_t and dy_t.
+    Asynchronous.  On a decomposed grid un, vn and the mask need valid depth-1 halos; nothing is exchanged and the call is
+    not collective."""
+    who = "drifter_step"
+    n = _drifter_arrays(who, px, py, status)
+    g = un.grid
+    if vn.grid is not g:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
+    it = field_bounds(g, GO_T_POINTS)[0]
+    check(_cabi.lib().dlesm_drifter_step_f64(
+        float(h), int(nsub), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
+        C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()), un.device_ptr, vn.device_ptr, n,
+        C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+
+
+def drifter_sample(px, py, status, fields, out=None, stream=None):
+    """T-point fields at the particles (dlesm_drifter_sample_f64): for every DRIFTER_ACTIVE particle
+    inside the T internal region, out[k][p] = fields[k] in the particle's cell, for 1 to 8 T-point r2d_fields of one grid;
+    every other out[k][p] keeps its content.  out: a list of contiguous float64 CUDA tensors of one element per particle, or
+    None for new ones filled with NaN.  Returns the list.  Asynchronous; nothing is exchanged."""
+    import torch
+    who = "drifter_sample"
+    n = _drifter_arrays(who, px, py, status)
+    fields = list(fields)
+    if not 1 <= len(fields) <= _cabi.DRIFTER_MAX_FIELDS:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: 1 to %d fields" % (who, _cabi.DRIFTER_MAX_FIELDS))
+    g = fields[0].grid
+    if any(f.grid is not g or f.defined_on != GO_T_POINTS for f in fields):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: the fields are T-point fields of one grid" % who)
+    if out is None:
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            out = [torch.full((n,), float("nan"), dtype=torch.float64, device=px.device) for _ in fields]
+    out = list(out)
+    if len(out) != len(fields) or any(not (o.is_cuda and o.is_contiguous() and o.dtype == torch.float64 and o.numel() == n)
+                                      for o in out):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: out holds one contiguous float64 CUDA tensor of n elements per field" % who)
+    it = fields[0].internal
+    pf = (C.c_void_p * len(fields))(*[f.device_ptr for f in fields])
+    po = (C.c_void_p * len(fields))(*[o.data_ptr() for o in out])
+    check(_cabi.lib().dlesm_drifter_sample_f64(
+        g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, n, C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()),
+        C.c_void_p(status.data_ptr()), pf, po, len(fields), _stream_ptr(stream)))
+    return out
 
 
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}

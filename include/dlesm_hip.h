@@ -1199,6 +1199,60 @@ int dlesm_flow_output_f64(int mode, double weight, int ld, int ny, int xstart, i
                           const int *tmask, const double *dx_v, const double *dy_u, const double *un, const double *vn,
                           const double *ht, const double *sshn_t, double *const *out, void *stream);
 
+/* Drifters: Lagrangian particles carried through the level-n C-grid flow, on the device.  A particle
+ * has a position (x, y) in local index coordinates, as doubles: T cell (i, j), 1-based as the box, covers [i, i+1) x
+ * [j, j+1); its west face x = i carries un(i-1,j), its east face x = i+1 un(i,j), its south and north faces vn(i,j-1) and
+ * vn(i,j).  cell(x, y) = (floor(x), floor(y)); inbox(x, y) = x >= xstart && x < xstop + 1 && y >= ystart && y < ystop + 1,
+ * evaluated in double before any conversion to an integer (a NaN or an infinity is not in the box and is never cast).  With
+ * T = tmask (wet > 0, land == 0, open < 0), h the seconds per substep, every operation rounded in double in the order the
+ * parentheses give, both divisions correctly rounded, choices by select:
+ *     ue = T(i+1,j) != 0 ? un(i,j) : 0.0     uw = T(i-1,j) != 0 ? un(i-1,j) : 0.0      (section 6.10's face switches)
+ *     vn_ = T(i,j+1) != 0 ? vn(i,j) : 0.0    vs = T(i,j-1) != 0 ? vn(i,j-1) : 0.0
+ *     a = x - (double)i      b = y - (double)j      up = uw + (ue - uw) * a      vp = vs + (vn_ - vs) * b
+ *     kx = (h * up) / dx_t(i,j)              ky = (h * vp) / dy_t(i,j)
+ * dlesm_drifter_step_f64, for every particle p < n whose status is DLESM_DRIFTER_ACTIVE (any other is neither read further
+ * nor written), with (x, y) = (px[p], py[p]):
+ *     entry:  !inbox(x,y) -> LEFT;  T(cell) < 0 -> OPEN;  T(cell) == 0 -> GROUNDED       (position unchanged, done)
+ *     repeat nsub times:
+ *         (k1x, k1y) = vel(cell(x,y), x, y);   xm = x + 0.5 * k1x;  ym = y + 0.5 * k1y
+ *         (k2x, k2y) = inbox(xm,ym) && T(cell(xm,ym)) > 0 ? vel(cell(xm,ym), xm, ym) : (k1x, k1y)
+ *         xn = x + k2x;  yn = y + k2y
+ *         !inbox(xn,yn)       -> (x,y) = (xn,yn), LEFT, stop
+ *         T(cell(xn,yn)) == 0 -> GROUNDED, stop                  (the last wet position is kept)
+ *         (x,y) = (xn,yn);  T(cell(x,y)) < 0 -> OPEN, stop
+ *     (px[p], py[p]) = (x, y)
+ * One call with nsub = k equals k calls with nsub = 1 bit for bit.  A NaN on a face that touches land reaches no particle and
+ * what land holds changes no bit.  LEFT and OPEN store where the particle went, GROUNDED does not store the rejected move.  A
+ * step longer than one cell passes over cells without seeing them: the advective number of dlesm_flow_courant_f64 is the
+ * check.  dlesm_drifter_sample_f64: for every ACTIVE particle with inbox(px, py), out[k][p] = fields[k](cell(px, py)) for
+ * each of the nfields T-point arrays; every other out[k][p] keeps its content.
+ * All arrays are device memory: the fields ny x ld with the box and its one-cell ring inside the array, px, py, status and
+ * every out[k] of n elements.  fields and out are HOST arrays of nfields device pointers, passed to the kernel by value.
+ * Asynchronous on `stream`, no plan, no scratch, no atomics: both calls may be captured into a graph.  On a decomposed grid
+ * the flow and the mask need valid depth-1 halos; nothing is exchanged.  n == 0 or an empty box launches nothing and returns
+ * 0 with every status unchanged.  DLESM_EINVAL before anything is launched: a null pointer, a double array not 8-byte
+ * aligned or an int array not 4-byte aligned, n < 0, nsub outside 1..DLESM_DRIFTER_MAX_SUB, a non-finite h, nfields outside
+ * 1..DLESM_DRIFTER_MAX_FIELDS, a box that does not fit with its ring, px, py or status overlapping each other or an input,
+ * an out[k] overlapping an input, px, py, status or another out.  Read-only inputs may share arrays. */
+enum { DLESM_DRIFTER_ACTIVE = 0, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED };
+enum { DLESM_DRIFTER_MAX_SUB = 1024, DLESM_DRIFTER_MAX_FIELDS = 8 };
+int dlesm_drifter_step_f64(double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                           const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
+                           long long n, double *px, double *py, int *status, void *stream);
+int dlesm_drifter_sample_f64(int ld, int ny, int xstart, int xstop, int ystart, int ystop, long long n,
+                             const double *px, const double *py, const int *status,
+                             const double *const *fields, double *const *out, int nfields, void *stream);
+/* An owner of the three particle arrays of section 6.17 on the device, for callers (Fortran, plain C) that have no device
+ * arrays other than fields.  create: n >= 0 particles, status zeroed (all ACTIVE), positions not set.  put: host -> device,
+ * status NULL = all ACTIVE.  get: device -> host after waiting for the device, NULL = skip that array.  arrays: the device
+ * pointers, to hand to the two entries above (any of the four results may be NULL).  destroy(NULL) is accepted. */
+typedef struct dlesm_drifters dlesm_drifters;
+int dlesm_drifters_create(long long n, dlesm_drifters **set);
+int dlesm_drifters_put(dlesm_drifters *set, const double *px, const double *py, const int *status);
+int dlesm_drifters_get(dlesm_drifters *set, double *px, double *py, int *status);
+int dlesm_drifters_arrays(dlesm_drifters *set, long long *n, double **px, double **py, int **status);
+int dlesm_drifters_destroy(dlesm_drifters *set);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
