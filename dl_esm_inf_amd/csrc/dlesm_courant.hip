@@ -5,24 +5,22 @@
 // number that is not a finite non-negative one, and how many are wet.  Maxima, integers and lowest indices: every member is
 // exact and independent of the order of the reduction, so the record does not depend on the kernel form or the launch shape.
 //
+// This file holds the check's own part: the per-cell rule, the record, the loads of the two sweep forms and the entry's
+// refusals (the policy TracerCheck).  The kernel bodies around them, the launch shape, the levels and the copy-back are
+// dlesm_record_reduce.h's, shared with dlesm_flow_courant.hip; the wave reductions are dlesm_wave_reduce.h's.
+//
 // courant_tile: tracer_tile's wave shape (dlesm_tracer.hip) -- 64 lanes x 2 columns x 1 row in 16-byte lanes, operands at
 // i-1 / i+1 (the u-face operands, the mask and w) from the neighbouring lane by a DPP wave shift, lane 0 fetches the column
 // west of the wave without a branch, lane 63 only loads, waves step by 63 chunks.  w of rows j-1 and j+1 comes from six more
 // row pairs a lane, asked for first, as in the Hancock tile.  A wave that owns no wet cell of the box leaves after its mask
-// row and contributes the identity.  Within the wave the reduction runs on the VALU (DPP butterflies and four readlanes, as
-// in dlesm_stats.hip), across the waves of a workgroup through LDS: one record per workgroup.
+// row and contributes the identity.  Within the wave the reduction runs on the VALU, across the waves of a workgroup through
+// LDS: one record per workgroup.
 //
 // courant_direct: one cell per thread -- odd leading dimensions, unaligned bases and the HOOK key tracer_courant_kernel = 1.
 //
 // courant_level: workgroup b combines records [b * 1024, (b + 1) * 1024) into one; launched until one record is left, and
 // that launch writes the caller's record (the empty maxima as 0.0 / -1).  No atomics; plain vector stores only.
-//
-// The (value, index) combine and the wave reductions are dlesm_wave_reduce.h's, shared with dlesm_flow_courant.hip; this
-// translation unit shares no kernel with the other entry points.
-#include <climits>
-
-#include "dlesm_nemolite.h"
-#include "dlesm_wave_reduce.h"
+#include "dlesm_record_reduce.h"
 
 namespace dlesm {
 
@@ -33,11 +31,7 @@ typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
 using namespace wavered;
-
-constexpr int TILE_CHUNKS = 63;       // chunks (2 columns) a wave owns; lane 63 only loads
-constexpr int LEVEL_CHUNK = 1024;     // records per workgroup of a level
-constexpr double BIGGEST = 1.7976931348623157e308;
-constexpr long long NO_INDEX = LLONG_MAX;
+using namespace recred;
 
 struct CourantArgs {
     const int *tmask;
@@ -45,220 +39,173 @@ struct CourantArgs {
     double rdt, face_limit, outflow_limit;
 };
 
-// what one thread, one wave or one workgroup has seen.  A maximum of -1.0 (with NO_INDEX) stands for "none yet": every
-// value that competes is >= 0.  In the scratch records the same convention holds; only the last level writes 0.0 / -1.
-struct Acc {
-    double fm, om;
-    long long fi, oi;
-    long long over_f, over_o, bad, wet;
-};
-__device__ __forceinline__ Acc acc_identity() { return Acc{-1.0, -1.0, NO_INDEX, NO_INDEX, 0, 0, 0, 0}; }
+struct TracerCheck {
+    using Args = CourantArgs;
+    using Record = dlesm_tracer_courant;
+    // the four counts of a cell or a wave tile, a byte each: wet | bad << 8 | (m >= face_limit) << 16 |
+    // (o >= outflow_limit) << 24 (two cells a lane, 126 a wave: a byte holds each sum, so the four share one 32-bit reduction)
+    using Counts = int;
 
-__device__ __forceinline__ bool valid(double x) { return x >= 0.0 && x <= BIGGEST; }   // false for a NaN
+    // what one thread, one wave or one workgroup has seen.  A maximum of -1.0 (with NO_INDEX) stands for "none yet": every
+    // value that competes is >= 0.  In the scratch records the same convention holds; only the last level writes 0.0 / -1.
+    struct Acc {
+        double fm, om;
+        long long fi, oi;
+        long long over_f, over_o, bad, wet;
+    };
+    static __device__ __forceinline__ Acc identity() { return Acc{-1.0, -1.0, NO_INDEX, NO_INDEX, 0, 0, 0, 0}; }
 
-// one wet cell of the box (section 6.14); ix = its 0-based linear index.  The maxima go into a; what the cell adds to the four
-// counts comes back in one word, a byte each: wet | bad << 8 | (m >= face_limit) << 16 | (o >= outflow_limit) << 24
-__device__ __forceinline__ int acc_cell(Acc &a, bool wet, long long ix, const TracerFlow &f, const TracerNumbers &n, double w,
-                                         double face_limit, double outflow_limit)
-{
-    double m = -1.0;
-    m = (f.e && valid(n.n1) && n.n1 > m) ? n.n1 : m;
-    m = (f.w && valid(n.n2) && n.n2 > m) ? n.n2 : m;
-    m = (f.n && valid(n.n3) && n.n3 > m) ? n.n3 : m;
-    m = (f.s && valid(n.n4) && n.n4 > m) ? n.n4 : m;
-    const double o1 = (f.e && f.r1 > 0.0) ? f.r1 : 0.0, o2 = (f.w && f.r2 < 0.0) ? -f.r2 : 0.0;
-    const double o3 = (f.n && f.r3 > 0.0) ? f.r3 : 0.0, o4 = (f.s && f.r4 < 0.0) ? -f.r4 : 0.0;
-    const double o = (((o1 + o2) + o3) + o4) * w;
-    const bool bad = !(w > 0.0 && w <= BIGGEST) || (f.e && !valid(n.n1)) || (f.w && !valid(n.n2)) ||
-                     (f.n && !valid(n.n3)) || (f.s && !valid(n.n4)) || !valid(o);
-    const bool has_m = wet && m >= 0.0, has_o = wet && valid(o);
-    if (has_m) take(a.fm, a.fi, m, ix);
-    if (has_o) take(a.om, a.oi, o, ix);
-    return (int)wet | ((int)(wet && bad) << 8) | ((int)(has_m && m >= face_limit) << 16) |
-           ((int)(has_o && o >= outflow_limit) << 24);
-}
-__device__ __forceinline__ void add_counts(Acc &a, int c)
-{
-    a.wet += c & 0xff, a.bad += (c >> 8) & 0xff, a.over_f += (c >> 16) & 0xff, a.over_o += (c >> 24) & 0xff;
-}
-
-// the maxima and their lowest indices over the wave; every lane must be active
-__device__ __forceinline__ void wave_pairs(Acc &a)
-{
-    const double fm = wave_max_f64(a.fm), om = wave_max_f64(a.om);
-    a.fi = wave_i64<true>(a.fm == fm ? a.fi : NO_INDEX);
-    a.oi = wave_i64<true>(a.om == om ? a.oi : NO_INDEX);
-    a.fm = fm, a.om = om;
-}
-// ... and the four counts as 64-bit sums (the one-cell-per-thread kernel, whose threads walk many rows, and the levels)
-__device__ __forceinline__ void wave_reduce(Acc &a)
-{
-    wave_pairs(a);
-    a.wet = wave_i64<false>(a.wet);
-    a.bad = wave_i64<false>(a.bad);
-    a.over_f = wave_i64<false>(a.over_f);
-    a.over_o = wave_i64<false>(a.over_o);
-}
-
-__device__ __forceinline__ void merge(Acc &a, const Acc &b)
-{
-    take(a.fm, a.fi, b.fm, b.fi);
-    take(a.om, a.oi, b.om, b.oi);
-    a.over_f += b.over_f, a.over_o += b.over_o, a.bad += b.bad, a.wet += b.wet;
-}
-
-__device__ __forceinline__ dlesm_tracer_courant to_record(const Acc &a)
-{
-    return dlesm_tracer_courant{a.fm, a.om, a.fi, a.oi, a.over_f, a.over_o, a.bad, a.wet};
-}
-__device__ __forceinline__ Acc from_record(const dlesm_tracer_courant &r)
-{
-    return Acc{r.face_max, r.outflow_max, r.face_index, r.outflow_index, r.face_over, r.outflow_over, r.invalid, r.wet};
-}
-
-// the waves of a workgroup through LDS, in wave order; thread 0 returns with the workgroup's value in `a`.  Every thread of
-// the workgroup calls it.
-__device__ __forceinline__ void block_reduce(Acc &a, Acc *wv)
-{
-    const int nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int k = 1; k < nw; k++) merge(a, wv[k]);
-}
-
-// one wave tile of row j (0-based); lane 0 of the tile holds chunk c0.  cn: the lane's counts in acc_cell's packing (two cells
-// a lane, 126 a wave: a byte holds each sum, so the four share one 32-bit reduction)
-__device__ __forceinline__ void tile_row(const CourantArgs &f, int ld, int x0, int x1, int j, int c0, int lane, Acc &acc,
-                                         int &cn)
-{
-    const int c = c0 + lane;                             // this lane's chunk (2 columns); lane 63 = the next wave's lane 0
-    const int c_ld = ld / 2 - 1, cl = c < c_ld ? c : c_ld;
-    const bool own = lane != 63;                         // lane 63 only loads: its chunk is the east column of lane 62
-    const bool m0 = own && c * 2 >= x0 && c * 2 <= x1, m1 = own && c * 2 + 1 >= x0 && c * 2 + 1 <= x1;
-    const size_t row = (size_t)j * ld, o = row + (size_t)cl * 2, os = o - ld, on = o + ld;
-
-    // the land exit: the mask of the row first; a wave that owns no wet cell of the box contributes the identity
-    const i2 t = *(const i2 *)(f.tmask + o);
-    const bool wet0 = m0 && t.x > 0, wet1 = m1 && t.y > 0;
-    if (__ballot(wet0 || wet1) == 0) return;
-
-    // w of the lane's two columns on rows j-1 and j+1, asked for in front of everything else (the Hancock tile's order)
-    const d2 ar_s = *(const d2 *)(f.area_t + os), ht_s = *(const d2 *)(f.ht + os), st_s = *(const d2 *)(f.sshn_t + os);
-    const d2 ar_n = *(const d2 *)(f.area_t + on), ht_n = *(const d2 *)(f.ht + on), st_n = *(const d2 *)(f.sshn_t + on);
-    const d2 ws = d2{tracer_weight(f.rdt, ar_s.x, ht_s.x, st_s.x), tracer_weight(f.rdt, ar_s.y, ht_s.y, st_s.y)};
-    const d2 wn = d2{tracer_weight(f.rdt, ar_n.x, ht_n.x, st_n.x), tracer_weight(f.rdt, ar_n.y, ht_n.y, st_n.y)};
-
-    // the west column this wave cannot get from a lane (no branch, LAB_NOTES.md section 5.10)
-    const size_t ow = row + (size_t)((lane == 0 && m0) ? c * 2 - 1 : cl * 2);
-    const i2 ts = *(const i2 *)(f.tmask + os), tn = *(const i2 *)(f.tmask + on);
-    int tw = f.tmask[ow];
-    const d2 su = *(const d2 *)(f.sshn_u + o), hu = *(const d2 *)(f.hu + o), un = *(const d2 *)(f.un + o);
-    double su_w = f.sshn_u[ow], hu_w = f.hu[ow], un_w = f.un[ow];
-    const d2 sv = *(const d2 *)(f.sshn_v + o), hv = *(const d2 *)(f.hv + o), vn = *(const d2 *)(f.vn + o);
-    const d2 sv_s = *(const d2 *)(f.sshn_v + os), hv_s = *(const d2 *)(f.hv + os), vn_s = *(const d2 *)(f.vn + os);
-    const d2 ht = *(const d2 *)(f.ht + o), st = *(const d2 *)(f.sshn_t + o), ar = *(const d2 *)(f.area_t + o);
-    double w_w = tracer_weight(f.rdt, f.area_t[ow], f.ht[ow], f.sshn_t[ow]);
-
-    const double w0 = tracer_weight(f.rdt, ar.x, ht.x, st.x), w1 = tracer_weight(f.rdt, ar.y, ht.y, st.y);
+    // one wet cell of the box (section 6.14); ix = its 0-based linear index.  The maxima go into a; what the cell adds to the
+    // four counts comes back
+    static __device__ __forceinline__ int acc_cell(Acc &a, bool wet, long long ix, const TracerFlow &f, const TracerNumbers &n,
+                                                   double w, double face_limit, double outflow_limit)
     {
-        const double s1 = from_lower<true>(su.y), h1 = from_lower<true>(hu.y), u1 = from_lower<true>(un.y);
-        const double wl = from_lower<true>(w1);
-        const int t1 = __builtin_amdgcn_mov_dpp(t.y, 0x138, 0xf, 0xf, true);
-        if (lane != 0) su_w = s1, hu_w = h1, un_w = u1, w_w = wl, tw = t1;
+        double m = -1.0;
+        m = (f.e && valid(n.n1) && n.n1 > m) ? n.n1 : m;
+        m = (f.w && valid(n.n2) && n.n2 > m) ? n.n2 : m;
+        m = (f.n && valid(n.n3) && n.n3 > m) ? n.n3 : m;
+        m = (f.s && valid(n.n4) && n.n4 > m) ? n.n4 : m;
+        const double o1 = (f.e && f.r1 > 0.0) ? f.r1 : 0.0, o2 = (f.w && f.r2 < 0.0) ? -f.r2 : 0.0;
+        const double o3 = (f.n && f.r3 > 0.0) ? f.r3 : 0.0, o4 = (f.s && f.r4 < 0.0) ? -f.r4 : 0.0;
+        const double o = (((o1 + o2) + o3) + o4) * w;
+        const bool bad = !(w > 0.0 && w <= BIGGEST) || (f.e && !valid(n.n1)) || (f.w && !valid(n.n2)) ||
+                         (f.n && !valid(n.n3)) || (f.s && !valid(n.n4)) || !valid(o);
+        const bool has_m = wet && m >= 0.0, has_o = wet && valid(o);
+        if (has_m) take(a.fm, a.fi, m, ix);
+        if (has_o) take(a.om, a.oi, o, ix);
+        return (int)wet | ((int)(wet && bad) << 8) | ((int)(has_m && m >= face_limit) << 16) |
+               ((int)(has_o && o >= outflow_limit) << 24);
     }
-    const int te = __builtin_amdgcn_mov_dpp(t.x, 0x130, 0xf, 0xf, true);      // (lane 63: 0, never used)
-    const double w_e = from_upper<true>(w0);                                   // (the same)
-    // tracer_flow's ssha operand only makes h_new, which nothing here reads: sshn_t stands in for it
-    const TracerFlow f0 = tracer_flow(f.rdt, su.x, su_w, sv.x, sv_s.x, hu.x, hu_w, hv.x, hv_s.x, un.x, un_w, vn.x, vn_s.x,
-                                      ar.x, ht.x, st.x, st.x, t.y, tw, tn.x, ts.x);
-    const TracerFlow f1 = tracer_flow(f.rdt, su.y, su.x, sv.y, sv_s.y, hu.y, hu.x, hv.y, hv_s.y, un.y, un.x, vn.y, vn_s.y,
-                                      ar.y, ht.y, st.y, st.y, te, t.x, tn.y, ts.y);
-    const TracerNumbers n0 = tracer_numbers(f0, w0, w1, w_w, wn.x, ws.x);
-    const TracerNumbers n1 = tracer_numbers(f1, w1, w_e, w0, wn.y, ws.y);
-    const long long ix = (long long)row + (long long)c * 2;
-    cn = acc_cell(acc, wet0, ix, f0, n0, w0, f.face_limit, f.outflow_limit) +
-         acc_cell(acc, wet1, ix + 1, f1, n1, w1, f.face_limit, f.outflow_limit);
-}
+    static __device__ __forceinline__ void add_counts(Acc &a, int c)
+    {
+        a.wet += c & 0xff, a.bad += (c >> 8) & 0xff, a.over_f += (c >> 16) & 0xff, a.over_o += (c >> 24) & 0xff;
+    }
+    static __device__ __forceinline__ int wave_counts(int c) { return wave_add_i32(c); }
 
-// (x0:x1, y0:y1) = the box (0-based); nxw tiles per row, tile 0 begins at chunk c_first; rec[blockIdx.x] = the workgroup's
-// record.  No thread leaves before the reductions: the DPP butterflies and the barrier want every lane.
+    // the maxima and their lowest indices over the wave; every lane must be active
+    static __device__ __forceinline__ void wave_pairs(Acc &a)
+    {
+        const double fm = wave_f64<OP_MAX>(a.fm), om = wave_f64<OP_MAX>(a.om);
+        a.fi = wave_i64<OP_MIN>(a.fm == fm ? a.fi : NO_INDEX);
+        a.oi = wave_i64<OP_MIN>(a.om == om ? a.oi : NO_INDEX);
+        a.fm = fm, a.om = om;
+    }
+    // ... and the four counts as 64-bit sums (the one-cell-per-thread kernel, whose threads walk many rows, and the levels)
+    static __device__ __forceinline__ void wave_reduce(Acc &a)
+    {
+        wave_pairs(a);
+        a.wet = wave_i64<OP_ADD>(a.wet);
+        a.bad = wave_i64<OP_ADD>(a.bad);
+        a.over_f = wave_i64<OP_ADD>(a.over_f);
+        a.over_o = wave_i64<OP_ADD>(a.over_o);
+    }
+
+    static __device__ __forceinline__ void merge(Acc &a, const Acc &b)
+    {
+        take(a.fm, a.fi, b.fm, b.fi);
+        take(a.om, a.oi, b.om, b.oi);
+        a.over_f += b.over_f, a.over_o += b.over_o, a.bad += b.bad, a.wet += b.wet;
+    }
+
+    static __device__ __forceinline__ Record to_record(const Acc &a)
+    {
+        return Record{a.fm, a.om, a.fi, a.oi, a.over_f, a.over_o, a.bad, a.wet};
+    }
+    static __device__ __forceinline__ Acc from_record(const Record &r)
+    {
+        return Acc{r.face_max, r.outflow_max, r.face_index, r.outflow_index, r.face_over, r.outflow_over, r.invalid, r.wet};
+    }
+    // the caller's record: "none" reads 0.0 / -1
+    static __device__ __forceinline__ void finish(Acc &acc)
+    {
+        if (acc.fi == NO_INDEX) acc.fm = 0.0, acc.fi = -1;
+        if (acc.oi == NO_INDEX) acc.om = 0.0, acc.oi = -1;
+    }
+
+    // one wave tile of row j (0-based); lane 0 of the tile holds chunk c0.  cn: the lane's counts
+    static __device__ __forceinline__ void tile_row(const Args &f, int ld, int x0, int x1, int j, int c0, int lane, Acc &acc,
+                                                    int &cn)
+    {
+        const int c = c0 + lane;                         // this lane's chunk (2 columns); lane 63 = the next wave's lane 0
+        const int c_ld = ld / 2 - 1, cl = c < c_ld ? c : c_ld;
+        const bool own = lane != 63;                     // lane 63 only loads: its chunk is the east column of lane 62
+        const bool m0 = own && c * 2 >= x0 && c * 2 <= x1, m1 = own && c * 2 + 1 >= x0 && c * 2 + 1 <= x1;
+        const size_t row = (size_t)j * ld, o = row + (size_t)cl * 2, os = o - ld, on = o + ld;
+
+        // the land exit: the mask of the row first; a wave that owns no wet cell of the box contributes the identity
+        const i2 t = *(const i2 *)(f.tmask + o);
+        const bool wet0 = m0 && t.x > 0, wet1 = m1 && t.y > 0;
+        if (__ballot(wet0 || wet1) == 0) return;
+
+        // w of the lane's two columns on rows j-1 and j+1, asked for in front of everything else (the Hancock tile's order)
+        const d2 ar_s = *(const d2 *)(f.area_t + os), ht_s = *(const d2 *)(f.ht + os), st_s = *(const d2 *)(f.sshn_t + os);
+        const d2 ar_n = *(const d2 *)(f.area_t + on), ht_n = *(const d2 *)(f.ht + on), st_n = *(const d2 *)(f.sshn_t + on);
+        const d2 ws = d2{tracer_weight(f.rdt, ar_s.x, ht_s.x, st_s.x), tracer_weight(f.rdt, ar_s.y, ht_s.y, st_s.y)};
+        const d2 wn = d2{tracer_weight(f.rdt, ar_n.x, ht_n.x, st_n.x), tracer_weight(f.rdt, ar_n.y, ht_n.y, st_n.y)};
+
+        // the west column this wave cannot get from a lane (no branch, LAB_NOTES.md section 5.10)
+        const size_t ow = row + (size_t)((lane == 0 && m0) ? c * 2 - 1 : cl * 2);
+        const i2 ts = *(const i2 *)(f.tmask + os), tn = *(const i2 *)(f.tmask + on);
+        int tw = f.tmask[ow];
+        const d2 su = *(const d2 *)(f.sshn_u + o), hu = *(const d2 *)(f.hu + o), un = *(const d2 *)(f.un + o);
+        double su_w = f.sshn_u[ow], hu_w = f.hu[ow], un_w = f.un[ow];
+        const d2 sv = *(const d2 *)(f.sshn_v + o), hv = *(const d2 *)(f.hv + o), vn = *(const d2 *)(f.vn + o);
+        const d2 sv_s = *(const d2 *)(f.sshn_v + os), hv_s = *(const d2 *)(f.hv + os), vn_s = *(const d2 *)(f.vn + os);
+        const d2 ht = *(const d2 *)(f.ht + o), st = *(const d2 *)(f.sshn_t + o), ar = *(const d2 *)(f.area_t + o);
+        double w_w = tracer_weight(f.rdt, f.area_t[ow], f.ht[ow], f.sshn_t[ow]);
+
+        const double w0 = tracer_weight(f.rdt, ar.x, ht.x, st.x), w1 = tracer_weight(f.rdt, ar.y, ht.y, st.y);
+        {
+            const double s1 = from_lower<true>(su.y), h1 = from_lower<true>(hu.y), u1 = from_lower<true>(un.y);
+            const double wl = from_lower<true>(w1);
+            const int t1 = __builtin_amdgcn_mov_dpp(t.y, 0x138, 0xf, 0xf, true);
+            if (lane != 0) su_w = s1, hu_w = h1, un_w = u1, w_w = wl, tw = t1;
+        }
+        const int te = __builtin_amdgcn_mov_dpp(t.x, 0x130, 0xf, 0xf, true);      // (lane 63: 0, never used)
+        const double w_e = from_upper<true>(w0);                                   // (the same)
+        // tracer_flow's ssha operand only makes h_new, which nothing here reads: sshn_t stands in for it
+        const TracerFlow f0 = tracer_flow(f.rdt, su.x, su_w, sv.x, sv_s.x, hu.x, hu_w, hv.x, hv_s.x, un.x, un_w, vn.x, vn_s.x,
+                                          ar.x, ht.x, st.x, st.x, t.y, tw, tn.x, ts.x);
+        const TracerFlow f1 = tracer_flow(f.rdt, su.y, su.x, sv.y, sv_s.y, hu.y, hu.x, hv.y, hv_s.y, un.y, un.x, vn.y, vn_s.y,
+                                          ar.y, ht.y, st.y, st.y, te, t.x, tn.y, ts.y);
+        const TracerNumbers n0 = tracer_numbers(f0, w0, w1, w_w, wn.x, ws.x);
+        const TracerNumbers n1 = tracer_numbers(f1, w1, w_e, w0, wn.y, ws.y);
+        const long long ix = (long long)row + (long long)c * 2;
+        cn = acc_cell(acc, wet0, ix, f0, n0, w0, f.face_limit, f.outflow_limit) +
+             acc_cell(acc, wet1, ix + 1, f1, n1, w1, f.face_limit, f.outflow_limit);
+    }
+
+    // the cell at linear offset o, one thread's
+    static __device__ __forceinline__ void direct_cell(const Args &f, int ld, size_t o, Acc &acc)
+    {
+        if (f.tmask[o] <= 0) return;
+        const TracerFlow fl = tracer_flow(f.rdt, f.sshn_u[o], f.sshn_u[o - 1], f.sshn_v[o], f.sshn_v[o - ld], f.hu[o],
+                                          f.hu[o - 1], f.hv[o], f.hv[o - ld], f.un[o], f.un[o - 1], f.vn[o], f.vn[o - ld],
+                                          f.area_t[o], f.ht[o], f.sshn_t[o], f.sshn_t[o], f.tmask[o + 1], f.tmask[o - 1],
+                                          f.tmask[o + ld], f.tmask[o - ld]);
+        auto W = [&](size_t p) { return tracer_weight(f.rdt, f.area_t[p], f.ht[p], f.sshn_t[p]); };
+        const double w = W(o);
+        const TracerNumbers n = tracer_numbers(fl, w, W(o + 1), W(o - 1), W(o + ld), W(o - ld));
+        add_counts(acc, acc_cell(acc, true, (long long)o, fl, n, w, f.face_limit, f.outflow_limit));
+    }
+};
+
 __global__ __launch_bounds__(256, 4) void courant_tile(const CourantArgs a, int ld, int x0, int x1, int y0, int y1, int c_first,
                                                     int nxw, dlesm_tracer_courant *__restrict__ rec)
 {
-    __shared__ Acc wv[4];
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int xw = (int)(w % nxw);
-    const long long j = y0 + w / nxw;
-    const int c0 = c_first + xw * TILE_CHUNKS;
-    Acc acc = acc_identity();
-    int cn = 0;
-    if (j <= y1 && c0 <= x1 / 2) tile_row(a, ld, x0, x1, (int)j, c0, lane, acc, cn);   // (else: an idle padding tile)
-    wave_pairs(acc);
-    add_counts(acc, wave_add_i32(cn));
-    block_reduce(acc, wv);
-    if (threadIdx.x == 0) rec[blockIdx.x] = to_record(acc);
+    tile_body<TracerCheck>(a, ld, x0, x1, y0, y1, c_first, nxw, rec);
 }
-
-// one cell per thread: odd leading dimensions, unaligned bases, the HOOK key tracer_courant_kernel.  A thread walks its
-// column by rows y0 + blockIdx.y, + gridDim.y, ...; rec[blockIdx.y * gridDim.x + blockIdx.x] = the workgroup's record.
 __global__ __launch_bounds__(256) void courant_direct(const CourantArgs f, int ld, int x0, int x1, int y0, int y1,
                                                       dlesm_tracer_courant *__restrict__ rec)
 {
-    __shared__ Acc wv[4];
-    const int i = x0 + blockIdx.x * blockDim.x + threadIdx.x;
-    Acc acc = acc_identity();
-    if (i <= x1) {
-        for (long long j = (long long)y0 + blockIdx.y; j <= y1; j += gridDim.y) {
-            const size_t o = (size_t)j * ld + i;
-            if (f.tmask[o] <= 0) continue;
-            const TracerFlow fl = tracer_flow(f.rdt, f.sshn_u[o], f.sshn_u[o - 1], f.sshn_v[o], f.sshn_v[o - ld], f.hu[o],
-                                              f.hu[o - 1], f.hv[o], f.hv[o - ld], f.un[o], f.un[o - 1], f.vn[o], f.vn[o - ld],
-                                              f.area_t[o], f.ht[o], f.sshn_t[o], f.sshn_t[o], f.tmask[o + 1], f.tmask[o - 1],
-                                              f.tmask[o + ld], f.tmask[o - ld]);
-            auto W = [&](size_t p) { return tracer_weight(f.rdt, f.area_t[p], f.ht[p], f.sshn_t[p]); };
-            const double w = W(o);
-            const TracerNumbers n = tracer_numbers(fl, w, W(o + 1), W(o - 1), W(o + ld), W(o - ld));
-            add_counts(acc, acc_cell(acc, true, (long long)o, fl, n, w, f.face_limit, f.outflow_limit));
-        }
-    }
-    wave_reduce(acc);
-    block_reduce(acc, wv);
-    if (threadIdx.x == 0) rec[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = to_record(acc);
+    direct_body<TracerCheck>(f, ld, x0 + blockIdx.x * blockDim.x + threadIdx.x, x1, y0, y1,
+                             rec + ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
 }
-
-// One level: workgroup b combines src[b * LEVEL_CHUNK .. (b + 1) * LEVEL_CHUNK) into dst[b] (n = 0: the identity).  `last`:
-// dst is the caller's record, in which "none" reads 0.0 / -1.
 __global__ __launch_bounds__(256) void courant_level(const dlesm_tracer_courant *__restrict__ src, long long n,
                                                      dlesm_tracer_courant *__restrict__ dst, int last)
 {
-    __shared__ Acc wv[4];
-    const long long lo = (long long)blockIdx.x * LEVEL_CHUNK, hi = lo + LEVEL_CHUNK < n ? lo + LEVEL_CHUNK : n;
-    Acc acc = acc_identity();
-    for (long long k = lo + threadIdx.x; k < hi; k += 256) merge(acc, from_record(src[k]));
-    wave_reduce(acc);
-    block_reduce(acc, wv);
-    if (threadIdx.x == 0) {
-        if (last) {
-            if (acc.fi == NO_INDEX) acc.fm = 0.0, acc.fi = -1;
-            if (acc.oi == NO_INDEX) acc.om = 0.0, acc.oi = -1;
-        }
-        dst[blockIdx.x] = to_record(acc);
-    }
+    level_body<TracerCheck>(src, n, dst, last);
 }
-
-bool capturing(hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return st != hipStreamCaptureStatusNone;
-}
-
-long long level_groups(long long n) { return (n + LEVEL_CHUNK - 1) / LEVEL_CHUNK; }
 
 } // namespace
 
@@ -266,8 +213,7 @@ long long level_groups(long long n) { return (n + LEVEL_CHUNK - 1) / LEVEL_CHUNK
 
 using namespace dlesm;
 
-// Both forms of the entry.  result_host == nullptr: the asynchronous one, *result_dev written when `s` gets there; otherwise
-// the record lands behind the scratch records and comes back by a copy on `s` that the host waits for.
+// Both forms of the entry (recred::run): the refusals, in their order, then the sweep
 static int tracer_courant_run(const char *who, double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
                               const int *tmask, const double *area_t, const double *un, const double *vn, const double *hu,
                               const double *hv, const double *ht, const double *sshn_t, const double *sshn_u,
@@ -279,85 +225,20 @@ static int tracer_courant_run(const char *who, double rdt, int ld, int ny, int x
     const double *const ins[9] = {area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v};
     static const char *const in_name[9] = {"area_t", "un", "vn", "hu", "hv", "ht", "sshn_t", "sshn_u", "sshn_v"};
     DLESM_REQUIRE(result_dev != nullptr || result_host != nullptr, "%s: null result", who);
-    DLESM_REQUIRE(tmask != nullptr, "%s: null tmask", who);
-    DLESM_REQUIRE((uintptr_t)tmask % 4 == 0, "%s: tmask is not 4-byte aligned", who);
-    for (int k = 0; k < 9; k++) {
-        DLESM_REQUIRE(ins[k] != nullptr, "%s: null %s", who, in_name[k]);
-        DLESM_REQUIRE((uintptr_t)ins[k] % 8 == 0, "%s: %s is not 8-byte aligned", who, in_name[k]);
-    }
+    if (int rc = check_arrays(who, tmask, ins, in_name, 9)) return rc;
     DLESM_REQUIRE(ld >= 1 && ny >= 1, "%s: array extents %dx%d", who, ld, ny);
     const bool empty = xstop < xstart || ystop < ystart;
     if (!empty)
         if (int rc = check_box(who, ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
     DLESM_REQUIRE(face_limit > 0.0, "%s: face_limit %g (a positive number)", who, face_limit);
     DLESM_REQUIRE(outflow_limit > 0.0, "%s: outflow_limit %g (a positive number)", who, outflow_limit);
-    const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
-    if (result_dev) {
-        DLESM_REQUIRE(!overlap(result_dev, sizeof *result_dev, tmask, nb / 2), "%s: result_dev lies inside tmask", who);
-        for (int k = 0; k < 9; k++)
-            DLESM_REQUIRE(!overlap(result_dev, sizeof *result_dev, ins[k], nb), "%s: result_dev lies inside %s", who,
-                          in_name[k]);
-    }
+    if (int rc = check_result_apart(who, result_dev, sizeof *result_dev, ld, ny, tmask, ins, in_name, 9)) return rc;
     DLESM_REQUIRE(!capturing(s), "%s: not callable under stream capture", who);
 
     const CourantArgs a{tmask, area_t, un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v, rdt, face_limit, outflow_limit};
-    const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
-    const long long h = empty ? 0 : (long long)y1 - y0 + 1;
-    bool tile = ld % 2 == 0 && (uintptr_t)tmask % 8 == 0 && tuning("tracer_courant_kernel", 0) == 0;
-    for (int k = 0; k < 9; k++) tile = tile && (uintptr_t)ins[k] % 16 == 0;
-
-    // the sweep's launch shape = its number of records
-    int c_first = 0, nxw = 0, tpb = 4, gx = 0, gy = 0;
-    long long nrec = 0;
-    if (!empty) {
-        if (tile) {
-            c_first = (x0 / 2) & ~7;                     // tiles anchored on a 128-byte line of the row
-            nxw = (x1 / 2 - c_first + TILE_CHUNKS) / TILE_CHUNKS;
-            choose_block_shape(&nxw, &tpb, 4);
-            if (tpb > 4) tpb = 4;                        // __launch_bounds__(256)
-            nrec = ((long long)nxw * h + tpb - 1) / tpb;
-        } else {
-            gx = (x1 - x0 + 256) / 256, gy = (int)(h > 4096 ? 4096 : h);
-            nrec = (long long)gx * gy;
-        }
-    }
-    DLESM_REQUIRE(nrec <= INT_MAX, "%s: %lld workgroups in one sweep (at most %d)", who, nrec, INT_MAX);
-    long long above = 0;
-    for (long long n = level_groups(nrec); n > 1; n = level_groups(n)) above += n;
-
-    dlesm_tracer_courant *scratch = nullptr;
-    DLESM_HIP_TRY(scratch_alloc_async((void **)&scratch, (size_t)(nrec + above + 1) * sizeof(dlesm_tracer_courant), s));
-    if (!result_dev) result_dev = scratch + nrec + above;
-    if (nrec > 0) {
-        if (tile)
-            hipLaunchKernelGGL(courant_tile, dim3((unsigned)nrec), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, c_first, nxw,
-                               scratch);
-        else
-            hipLaunchKernelGGL(courant_direct, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, a, ld, x0, x1, y0, y1,
-                               scratch);
-    }
-    // levels of LEVEL_CHUNK until one record is left, that one into *result_dev
-    const dlesm_tracer_courant *src = scratch;
-    dlesm_tracer_courant *next = scratch + nrec;
-    for (long long n = nrec;;) {
-        const long long groups = n > LEVEL_CHUNK ? level_groups(n) : 1;
-        const bool last = groups == 1;
-        hipLaunchKernelGGL(courant_level, dim3((unsigned)groups), dim3(256), 0, s, src, n, last ? result_dev : next,
-                           last ? 1 : 0);
-        if (last) break;
-        src = next, next += groups, n = groups;
-    }
-    hipError_t err = hipGetLastError();
-    dlesm_tracer_courant host;
-    if (result_host && err == hipSuccess)
-        err = hipMemcpyAsync(&host, result_dev, sizeof host, hipMemcpyDeviceToHost, s);
-    DLESM_HIP_TRY(hipFreeAsync(scratch, s));
-    DLESM_HIP_TRY(err);
-    if (result_host) {
-        DLESM_HIP_TRY(hipStreamSynchronize(s));
-        *result_host = host;
-    }
-    return DLESM_OK;
+    const bool tile = lanes16_fit(ld, tmask, ins, 9) && tuning("tracer_courant_kernel", 0) == 0;
+    return run<TracerCheck>(who, {courant_tile, courant_direct, courant_level}, a, ld, xstart - 1, xstop - 1, ystart - 1, ystop - 1, empty,
+                  tile, result_dev, result_host, s);
 }
 
 extern "C" int dlesm_tracer_courant_async_f64(double rdt, int ld, int ny, int xstart, int xstop, int ystart, int ystop,

@@ -539,19 +539,10 @@ extern "C" int dlesm_halo_plan_describe(const dlesm_comm_tables *tables, int ld,
     return DLESM_OK;
 }
 
-// A stream that is being captured into a hipGraph (hipStreamBeginCapture): the steps then take
+// A stream that is being captured into a hipGraph (capturing(), dlesm_internal.h): the steps then take
 // their event form only -- fork to the side stream and join back are graph edges, every replay
 // runs the same nodes -- because the one-launch forms hand over through sequence numbers that are
 // baked into kernel arguments and advance per call on the host.
-static bool capturing(hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return st != hipStreamCaptureStatusNone;
-}
 
 // Pack buffers hold one slot set per field of a multi-field exchange.
 static int ensure_buffers(dlesm_halo_plan *p, int nfields, hipStream_t s)

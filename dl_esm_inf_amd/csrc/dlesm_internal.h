@@ -38,6 +38,15 @@ int ensure_device();
 // hipMallocAsync for a reduction's intermediate records (give them back with hipFreeAsync): stream-ordered as ever, from a
 // pool of the library's own on the bound device that keeps its freed blocks (dlesm_runtime.hip)
 hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s);
+// records (or partials) of the levels above the first of a reduction tree over n of them, `chunk` to a workgroup
+inline long long tree_records(long long n, long long chunk)
+{
+    long long need = 0;
+    for (n = (n + chunk - 1) / chunk; n > 1; n = (n + chunk - 1) / chunk) need += n;
+    return need;
+}
+// is `s` being captured into a hipGraph (hipStreamBeginCapture)?  (dlesm_runtime.hip)
+bool capturing(hipStream_t s);
 hipStream_t side_stream();     // created by ensure_device()
 hipStream_t transfer_stream(); // for the non-blocking sync callbacks
 int tuning(const char *key, int fallback);

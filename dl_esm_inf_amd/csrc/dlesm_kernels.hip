@@ -2032,12 +2032,7 @@ static void enqueue_resid_tree(const double *partial, long n, double *next, doub
     }
 }
 
-static long resid_tree_doubles(long n)
-{
-    long need = 0;
-    for (n = (n + 4095) / 4096; n > 1; n = (n + 4095) / 4096) need += n;
-    return need;
-}
+static long resid_tree_doubles(long n) { return tree_records(n, 4096); }
 
 // The Jacobi step with its residual: jacobi5_tile with the residual compiled in writes one partial
 // per (box row, 64-lane column group), and a fixed tree reduces them into *result_dev -- all on `stream`, scratch

@@ -179,6 +179,16 @@ hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s)
     return g_scratch_pool ? hipMallocFromPoolAsync(p, bytes, g_scratch_pool, s) : hipMallocAsync(p, bytes, s);
 }
 
+bool capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return st != hipStreamCaptureStatusNone;
+}
+
 int *wait_timed_out_word() { return g_wait_timed_out; }
 hipStream_t side_stream() { return g_side; }
 hipStream_t transfer_stream() { return g_xfer; }

@@ -9,10 +9,13 @@
 // into workgroups depends on (ld, box, base alignment) alone and every field has its own records and its own tree, so
 // the bits of a field's sums do not depend on what else is in the call.  No floating-point atomics anywhere.
 //
-// This translation unit holds copies of the helpers it needs; it shares no kernel with the other entry points.
+// The wave reductions are dlesm_wave_reduce.h's -- their fixed order is part of what makes a field's sums reproducible -- and
+// the copy-back tail is dlesm_record_reduce.h's, both shared with the two Courant checks; the multi-field level loop, which
+// puts every field's level into one launch, is this file's own.
 #include <climits>
 
 #include "dlesm_device.h"
+#include "dlesm_record_reduce.h"
 
 namespace dlesm {
 
@@ -20,6 +23,8 @@ namespace {
 
 typedef double d2u __attribute__((ext_vector_type(2)));
 typedef int i2u __attribute__((ext_vector_type(2), aligned(4)));   // a mask row starts on any int
+
+using namespace wavered;
 
 constexpr int SCALAR_SEG = 2048;      // elements per workgroup of the 8-byte form (eight per thread)
 constexpr int TREE_CHUNK = 4096;      // records per workgroup of a tree level
@@ -58,65 +63,6 @@ __device__ __forceinline__ void acc_cell(Acc &a, double x, bool counted)
     a.mn = (fin && x < a.mn) ? x : a.mn;
     a.mx = (fin && x > a.mx) ? x : a.mx;
     a.cn += (int)counted + ((int)(counted && !fin) << 16);
-}
-
-enum { OP_MIN, OP_MAX, OP_ADD };
-template <int OP>
-__device__ __forceinline__ double combine(double a, double b)
-{
-    if constexpr (OP == OP_MIN) return b < a ? b : a;      // no NaN gets here
-    else if constexpr (OP == OP_MAX) return b > a ? b : a;
-    else return a + b;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ long long dpp_i64(long long v)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(v & 0xffffffffLL), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, false);
-    return ((long long)hi << 32) | lo;
-}
-
-// A fixed reduction over the 64 lanes on the VALU: within each row of 16 lanes a butterfly by DPP (xor 1, xor 2, the
-// half-row and row mirrors: every lane of a row ends with the same bits, as a + b == b + a), then the four rows' values
-// read into scalars and combined as (row 0 . row 1) . (row 2 . row 3).  The result is the same in every lane.
-template <int OP>
-__device__ __forceinline__ double wave_f64(double v)
-{
-    v = combine<OP>(v, dpp_f64<0xB1>(v));                  // quad_perm [1,0,3,2]
-    v = combine<OP>(v, dpp_f64<0x4E>(v));                  // quad_perm [2,3,0,1]
-    v = combine<OP>(v, dpp_f64<0x141>(v));                 // row_half_mirror
-    v = combine<OP>(v, dpp_f64<0x140>(v));                 // row_mirror
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    auto row = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)); };
-    return combine<OP>(combine<OP>(row(0), row(16)), combine<OP>(row(32), row(48)));
-}
-__device__ __forceinline__ int wave_i32(int v)
-{
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, false);
-    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
-__device__ __forceinline__ long long wave_i64(long long v)
-{
-    v += dpp_i64<0xB1>(v);
-    v += dpp_i64<0x4E>(v);
-    v += dpp_i64<0x141>(v);
-    v += dpp_i64<0x140>(v);
-    const int lo = (int)(v & 0xffffffffLL), hi = (int)(v >> 32);
-    auto row = [&](int l) {
-        return ((long long)__builtin_amdgcn_readlane(hi, l) << 32) | (unsigned)__builtin_amdgcn_readlane(lo, l);
-    };
-    return (row(0) + row(16)) + (row(32) + row(48));
 }
 
 // the segment's cells, 16-byte lanes: the pairs of rowseg_pair, all loads of a lane issued before the first use.  A
@@ -178,7 +124,7 @@ __device__ __forceinline__ void sweep_cells(const SweepField &fd, int ld, int jr
 }
 
 // One workgroup = one row segment of one field; its record goes to rec[blockIdx.x].  Per lane the cells in index order,
-// then the lanes by the wave reduction above, then the four waves as (0 . 1) . (2 . 3).
+// then the lanes by the wave reduction (dlesm_wave_reduce.h), then the four waves as (0 . 1) . (2 . 3).
 __global__ __launch_bounds__(256) void field_stats_sweep(const SweepJob job)
 {
     __shared__ Acc wv[4];
@@ -200,7 +146,7 @@ __global__ __launch_bounds__(256) void field_stats_sweep(const SweepJob job)
     a.mx = wave_f64<OP_MAX>(a.mx);
     a.s = wave_f64<OP_ADD>(a.s);
     a.q = wave_f64<OP_ADD>(a.q);
-    a.cn = wave_i32(a.cn);
+    a.cn = wave_add_i32(a.cn);
     if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -239,8 +185,8 @@ __global__ __launch_bounds__(256) void field_stats_level(const TreeJob job)
     a.max = wave_f64<OP_MAX>(a.max);
     a.sum = wave_f64<OP_ADD>(a.sum);
     a.sumsq = wave_f64<OP_ADD>(a.sumsq);
-    a.count = wave_i64(a.count);
-    a.nonfinite = wave_i64(a.nonfinite);
+    a.count = wave_i64<OP_ADD>(a.count);
+    a.nonfinite = wave_i64<OP_ADD>(a.nonfinite);
     if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -272,24 +218,6 @@ __global__ __launch_bounds__(256) void field_locate_k(const double *__restrict__
         if (hit && e < mine) mine = e;
     }
     if (mine != ~0ULL) atomicMin(best, mine);
-}
-
-bool capturing(hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return st != hipStreamCaptureStatusNone;
-}
-
-// records of the levels above the first for a field of n sweep records
-long tree_records(long n)
-{
-    long need = 0;
-    for (n = (n + TREE_CHUNK - 1) / TREE_CHUNK; n > 1; n = (n + TREE_CHUNK - 1) / TREE_CHUNK) need += n;
-    return need;
 }
 
 } // namespace
@@ -340,7 +268,7 @@ static int field_stats_run(const char *who, const double *const *fields, const i
         }
         nrec[k] = empty ? 0 : (long)fd.segs * (b.ystop - b.ystart + 1);
         total += nrec[k];
-        above += tree_records(nrec[k]);
+        above += tree_records(nrec[k], TREE_CHUNK);
     }
     DLESM_REQUIRE(total <= INT_MAX, "%s: %ld row segments in one call (at most %d)", who, total, INT_MAX);
     job.n = nfields, job.ld = ld;
@@ -373,17 +301,7 @@ static int field_stats_run(const char *who, const double *const *fields, const i
             else t.src = t.dst, t.n = t.nb, more = true;
         }
     }
-    hipError_t err = hipGetLastError();
-    dlesm_field_stats host[DLESM_STATS_MAX_FIELDS];
-    if (result_host && err == hipSuccess)
-        err = hipMemcpyAsync(host, result_dev, (size_t)nfields * sizeof(dlesm_field_stats), hipMemcpyDeviceToHost, s);
-    DLESM_HIP_TRY(hipFreeAsync(scratch, s));
-    DLESM_HIP_TRY(err);
-    if (result_host) {
-        DLESM_HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < nfields; k++) result_host[k] = host[k];
-    }
-    return DLESM_OK;
+    return recred::copy_back<dlesm_field_stats, DLESM_STATS_MAX_FIELDS>(scratch, result_dev, result_host, nfields, s);
 }
 
 extern "C" int dlesm_field_stats_async_f64(const double *const *fields, const int *const *masks, const dlesm_region *boxes,

@@ -1,7 +1,8 @@
 """GPU test (-m gpu): dlesm_field_stats_async_f64 / dlesm_field_stats_f64 / dlesm_field_locate_f64 on
 whole sentinel-filled arrays, numpy on the host copy as the yardstick.
 - min, max, count and nonfinite are exactly numpy's over the box: pitches 256 and 131, box starts at every column mod 16,
-  one-row / one-column / one-cell boxes, boxes that touch the array's edges, a base at 16 bytes and 8 bytes off 16;
+  one-row / one-column / one-cell boxes, boxes that touch the array's edges, a base at 16 bytes and 8 bytes off 16, and a
+  narrow box of 4200 rows whose 4200 records take two levels of the tree;
 - |sum - fsum(x)| <= n 2^-52 fsum(|x|) and |sumsq - fsum(x^2)| <= n 2^-52 fsum(x^2): the worst-case bound of ANY order of
   n - 1 additions (each adds a relative error of at most 2^-53 to a partial sum that is at most fsum(|x|); first order
   (n - 1) 2^-53) with a factor 2 of slack for the higher-order terms; data in [-0.5, 0.5);
@@ -106,6 +107,8 @@ def _cases():
                 (ld, ny, 1, 1, 1, ny), (ld, ny, ld, ld, 1, ny), (ld, ny, ld - 2, ld, 1, ny), (ld, ny, 1, 4, 1, ny), (ld, ny, ld - 4, ld, ny, ny)]
     out.append((4500, 5, 1, 4500, 1, 5))                   # several segments per row, in both lane widths
     out.append((4499, 5, 3, 4499, 1, 5))
+    # a two-level tree: one record a row in either lane form, 4200 records a field -- more than one level's 4096 (TREE_CHUNK)
+    out.append((6, 4200, 2, 5, 1, 4200))
     return out
 
 

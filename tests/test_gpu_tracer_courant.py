@@ -22,7 +22,7 @@ from tracer_numpy import same
 pytestmark = pytest.mark.gpu
 EINVAL = -1             # DLESM_EINVAL
 SENTINEL = -7.0
-LEVEL_CHUNK = 1024      # records one workgroup of a reduction level combines (dlesm_courant.hip)
+LEVEL_CHUNK = 1024      # records one workgroup of a reduction level combines (dlesm_record_reduce.h)
 
 
 @pytest.fixture(scope="module")
