@@ -137,29 +137,23 @@ extern "C" int dlesm_continuity_f64(double rdt, int ld, int ny, int xstart, int 
     if (int rc = check_box("dlesm_continuity_f64", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
     DLESM_REQUIRE(sshn_t && sshn_u && sshn_v && hu && hv && un && vn && area_t && ssha, "continuity: null pointer");
     const ContFields f{sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t, ssha};
-    bool aligned = ld % 2 == 0;
-    for (const double *q : {sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t, (const double *)ssha})
-        aligned = aligned && (uintptr_t)q % 16 == 0;
+    const bool aligned = lanes16_fit(ld, nullptr, {sshn_t, sshn_u, sshn_v, hu, hv, un, vn, area_t, ssha});
     DLESM_REQUIRE(ssha != sshn_u && ssha != sshn_v && ssha != hu && ssha != hv && ssha != un && ssha != vn,
                   "continuity: ssha aliases an input that is read at a neighbouring point");
     hipStream_t s = (hipStream_t)stream;
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
     if (aligned && tuning("cont_kernel", 0) == 0) {
-        const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;  // tiles anchored on 128-byte lines of the row
-        int nxw = (c_last - c_first + 64) / 64, tpb = 4;
-        shape_for_tile_sweep(ld, x0, x1, y0, y1, &nxw, &tpb);
-        const int strips = (y1 - y0 + R) / R;
-        const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
+        TilePlan p;
+        if (int rc = tile_plan("dlesm_continuity_f64", ld, x0, x1, y0, y1, CHUNKS_ALL, R, SHAPE_PLANNED, 16, &p)) return rc;
         switch (tuning("cont_nt", 2) & 3) {
-        case 1: hipLaunchKernelGGL(continuity_tile<1>, dim3(grid), dim3(64 * tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, c_first, nxw); break;
-        case 2: hipLaunchKernelGGL(continuity_tile<2>, dim3(grid), dim3(64 * tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, c_first, nxw); break;
-        case 3: hipLaunchKernelGGL(continuity_tile<3>, dim3(grid), dim3(64 * tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, c_first, nxw); break;
-        default: hipLaunchKernelGGL(continuity_tile<0>, dim3(grid), dim3(64 * tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, c_first, nxw); break;
+        case 1: hipLaunchKernelGGL(continuity_tile<1>, dim3(p.grid), dim3(64 * p.tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, p.c_first, p.nxw); break;
+        case 2: hipLaunchKernelGGL(continuity_tile<2>, dim3(p.grid), dim3(64 * p.tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, p.c_first, p.nxw); break;
+        case 3: hipLaunchKernelGGL(continuity_tile<3>, dim3(p.grid), dim3(64 * p.tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, p.c_first, p.nxw); break;
+        default: hipLaunchKernelGGL(continuity_tile<0>, dim3(p.grid), dim3(64 * p.tpb), 0, s, f, rdt, ld, x0, x1, y0, y1, p.c_first, p.nxw); break;
         }
     } else {
-        const int h = y1 - y0 + 1;
-        hipLaunchKernelGGL(continuity_direct, dim3((x1 - x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, s, f, rdt, ld,
-                           x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL(continuity_direct, dim3(g.x, g.y), dim3(256), 0, s, f, rdt, ld, x0, x1, y0, y1);
     }
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;

@@ -15,7 +15,6 @@
 //
 // flow_output_direct<VORT, ADD>: one cell per thread -- odd leading dimensions, unaligned bases and the HOOK key
 // flow_output_kernel = 1.
-#include <climits>
 #include <cmath>
 
 #include "dlesm_nemolite.h"
@@ -29,7 +28,7 @@ typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
 
-constexpr int TILE_CHUNKS = 63;       // chunks (2 columns) a wave owns; lane 63 only loads
+constexpr int TILE_CHUNKS = CHUNKS_EAST;      // chunks (2 columns) a wave owns; lane 63 only loads
 constexpr int NOUT = DLESM_OUT_COUNT;
 
 struct OutArgs {
@@ -158,19 +157,13 @@ __global__ __launch_bounds__(256) void flow_output_direct(const OutArgs a, int l
 template <bool VORT, bool ADD>
 int launch(bool tile, const OutArgs &a, int ld, int x0, int x1, int y0, int y1, hipStream_t s)
 {
-    const long long h = (long long)y1 - y0 + 1;
     if (tile) {
-        const int c_first = (x0 / 2) & ~7;               // tiles anchored on a 128-byte line of the row
-        int nxw = (x1 / 2 - c_first + TILE_CHUNKS) / TILE_CHUNKS, tpb = 4;
-        choose_block_shape(&nxw, &tpb, 4);
-        if (tpb > 4) tpb = 4;                            // __launch_bounds__(256)
-        const long long nblk = ((long long)nxw * h + tpb - 1) / tpb;
-        DLESM_REQUIRE(nblk <= INT_MAX, "dlesm_flow_output_f64: %lld workgroups in one sweep (at most %d)", nblk, INT_MAX);
-        hipLaunchKernelGGL((flow_output_tile<VORT, ADD>), dim3((unsigned)nblk), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, c_first,
-                           nxw);
+        TilePlan p;                                      // (4 waves: __launch_bounds__(256))
+        if (int rc = tile_plan("dlesm_flow_output_f64", ld, x0, x1, y0, y1, TILE_CHUNKS, 1, SHAPE_FOUR, 4, &p)) return rc;
+        hipLaunchKernelGGL((flow_output_tile<VORT, ADD>), dim3(p.grid), dim3(64 * p.tpb), 0, s, a, ld, x0, x1, y0, y1, p.c_first, p.nxw);
     } else {
-        hipLaunchKernelGGL((flow_output_direct<VORT, ADD>), dim3((unsigned)((x1 - x0 + 256) / 256), (unsigned)(h > 4096 ? 4096 : h)),
-                           dim3(256), 0, s, a, ld, x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL((flow_output_direct<VORT, ADD>), dim3(g.x, g.y), dim3(256), 0, s, a, ld, x0, x1, y0, y1);
     }
     return DLESM_OK;
 }
@@ -229,9 +222,9 @@ extern "C" int dlesm_flow_output_f64(int mode, double weight, int ld, int ny, in
 
     OutArgs a{tmask, need[0] ? dx_v : nullptr, need[1] ? dy_u : nullptr, un, vn, need[4] ? ht : nullptr,
               need[5] ? sshn_t : nullptr, {}, mode == DLESM_OUT_ADD ? weight : 0.0};
-    bool tile = ld % 2 == 0 && (uintptr_t)tmask % 8 == 0 && tuning("flow_output_kernel", 0) == 0;
-    for (int m = 0; m < 6; m++) tile = tile && (!need[m] || (uintptr_t)ins[m] % 16 == 0);
-    for (int k = 0; k < NOUT; k++) a.out[k] = out[k], tile = tile && (uintptr_t)out[k] % 16 == 0;
+    for (int k = 0; k < NOUT; k++) a.out[k] = out[k];
+    const bool tile = lanes16_fit(ld, tmask, {a.dx_v, a.dy_u, a.un, a.vn, a.ht, a.sshn_t}) && lanes16_fit(ld, nullptr, out, NOUT) &&
+                      tuning("flow_output_kernel", 0) == 0;
 
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
     const hipStream_t s = (hipStream_t)stream;

@@ -10,6 +10,7 @@
 
 #include "dlesm_error.h"
 #include "dlesm_hip.h"
+#include "dlesm_tile_plan.h"
 
 // the open-boundary plan (dlesm_open_bc.hip makes it; dlesm_nemolite_step.hip checks its extents)
 struct dlesm_obc {
@@ -166,16 +167,7 @@ struct SwFields {                        // the nine arrays of one leapfrog step
     const double *uold, *vold, *pold;    // level n-1 (the filtered forms also write it)
     double *unew, *vnew, *pnew;          // level n+1
 };
-// May a shallow-water launch use 16-byte lanes (the wave-tile kernels)?  The n bases are 16-byte aligned, and the leading
-// dimension is even (every row then starts on 16 bytes) or the last column the launch touches, east0 (0-based), lies inside
-// the last whole two-column chunk of a row.  east0 is the caller's to say: xstop - 1 for a box, xstop - 2 for the interior of
-// the framed step (launch_shallow_framed), xstop - 1 + ge for the grown box of the two-step distributed form.
-inline bool sw_lanes16_fit(int ld, int east0, const double *const *f, int n)
-{
-    bool ok = ld % 2 == 0 || east0 + 1 <= 2 * (ld / 2) - 1;
-    for (int k = 0; k < n; k++) ok = ok && ((uintptr_t)f[k] % 16 == 0);
-    return ok;
-}
+// the fit rule of the shallow-water launches (dlesm_tile_plan.h) over the nine arrays of a step
 inline bool sw_lanes16_fit(int ld, int east0, const SwFields &f)
 {
     const double *const nine[9] = {f.u, f.v, f.p, f.uold, f.vold, f.pold, f.unew, f.vnew, f.pnew};
@@ -326,10 +318,6 @@ int launch_stencil5_multi(const double *in, double *out, int ld, int ny, int nst
                           int ystart, int ystop, int exstart, int exstop, int eystart, int eystop, int gw,
                           int ge, int gs, int gn, hipStream_t s);
 
-// block shape (waves per workgroup, padded tiles per row) of a linear tile sweep
-void choose_block_shape(int *nxw_io, int *tpb_out, int prefer = 0);
-// the same for a sweep with the Jacobi tile geometry over the 0-based box: the planned Jacobi shape of that (ld, box) if there is one
-void shape_for_tile_sweep(int ld, int x0, int x1, int y0, int y1, int *nxw_io, int *tpb_out);
 int check_box(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, int ring);
 // two shallow-water steps per launch (dlesm_shallow_x2.hip): the overlap check of the twelve arrays, and the distributed form's
 // wave-tile conditions and launch (stage 1 computed on the box grown by gw..gn; see shallow_tile_x2_grown)

@@ -122,24 +122,14 @@ extern "C" int dlesm_stencil5_masked_f64(const double *in, double *out, const in
                   "masked stencil5: null or aliased arrays");
     hipStream_t s = (hipStream_t)stream;
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
-    const bool tile = ld % 2 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)tmask % 8 == 0 &&
-                      tuning("j5m_kernel", 0) == 0;
-    if (tile) {
-        const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;  // tiles anchored on 128-byte lines of the row
-        int nxw = (c_last - c_first + 64) / 64, tpb = 4;
-        shape_for_tile_sweep(ld, x0, x1, y0, y1, &nxw, &tpb);
-        const int strips = (y1 - y0 + R) / R;
-        const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
-        if (nt_stores_for(ld, y0, y1))
-            hipLaunchKernelGGL(jacobi5_masked_tile<true>, dim3(grid), dim3(64 * tpb), 0, s, in, out, tmask, ld, x0, x1, y0,
-                               y1, c_first, nxw);
-        else
-            hipLaunchKernelGGL(jacobi5_masked_tile<false>, dim3(grid), dim3(64 * tpb), 0, s, in, out, tmask, ld, x0, x1, y0,
-                               y1, c_first, nxw);
+    if (lanes16_fit(ld, tmask, {in, out}) && tuning("j5m_kernel", 0) == 0) {
+        TilePlan p;
+        if (int rc = tile_plan("dlesm_stencil5_masked_f64", ld, x0, x1, y0, y1, CHUNKS_ALL, R, SHAPE_PLANNED, 16, &p)) return rc;
+        const auto tile = nt_stores_for(ld, y0, y1) ? jacobi5_masked_tile<true> : jacobi5_masked_tile<false>;
+        hipLaunchKernelGGL(tile, dim3(p.grid), dim3(64 * p.tpb), 0, s, in, out, tmask, ld, x0, x1, y0, y1, p.c_first, p.nxw);
     } else {
-        const int h = y1 - y0 + 1;
-        hipLaunchKernelGGL(jacobi5_masked_direct, dim3((x1 - x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, s, in,
-                           out, tmask, ld, x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL(jacobi5_masked_direct, dim3(g.x, g.y), dim3(256), 0, s, in, out, tmask, ld, x0, x1, y0, y1);
     }
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;

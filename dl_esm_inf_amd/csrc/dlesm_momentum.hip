@@ -191,20 +191,17 @@ int momentum_launch(const char *who, const dlesm_momentum_params *p, const dlesm
                                        gr->dx_t, gr->dy_t, gr->dx_u, gr->dy_u, gr->dx_v, gr->dy_v, gr->area_u, gr->area_v,
                                        gr->fcor_u, gr->fcor_v};
     const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
-    bool aligned = ld % 2 == 0 && (uintptr_t)gr->tmask % 8 == 0;
     DLESM_REQUIRE(gr->tmask, "%s: null tmask", who);
     for (int f = 0; f < NF; f++) {
         if (!needed<WU, WV>(f)) continue;
         a.f[f] = f < 10 ? in[f] : grid_of[f];
         DLESM_REQUIRE(a.f[f], "%s: null pointer (operand %d)%s", who, f,
                       f == FU || f == FV ? ": the Coriolis parameter has not been set" : "");
-        aligned = aligned && (uintptr_t)a.f[f] % 16 == 0;
     }
     double *const outs[2] = {WU ? ua : nullptr, WV ? va : nullptr};
     DLESM_REQUIRE(!(WU && !ua) && !(WV && !va), "%s: null output", who);
     for (double *o : outs) {
         if (!o) continue;
-        aligned = aligned && (uintptr_t)o % 16 == 0;
         DLESM_REQUIRE(!overlap(o, nb, gr->tmask, nb / 2), "%s: an output overlaps tmask", who);
         for (int f = 0; f < NF; f++)
             DLESM_REQUIRE(!a.f[f] || !overlap(o, nb, a.f[f], nb), "%s: an output overlaps an input (operand %d)", who, f);
@@ -222,18 +219,13 @@ int momentum_launch(const char *who, const dlesm_momentum_params *p, const dlesm
     const int x0 = eu ? vb.x0 : ev ? ub.x0 : std::min(ub.x0, vb.x0), x1 = eu ? vb.x1 : ev ? ub.x1 : std::max(ub.x1, vb.x1);
     const int y0 = eu ? vb.y0 : ev ? ub.y0 : std::min(ub.y0, vb.y0), y1 = eu ? vb.y1 : ev ? ub.y1 : std::max(ub.y1, vb.y1);
     hipStream_t s = (hipStream_t)stream;
-    if (aligned && tuning("mom_kernel", 0) == 0) {
-        const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;  // tiles anchored on 128-byte lines of the row
-        int nxw = (c_last - c_first + 64) / 64, tpb = 4;
-        choose_block_shape(&nxw, &tpb, 4);
-        if (tpb > 4) tpb = 4;                               // __launch_bounds__(256)
-        const int strips = (y1 - y0 + MR) / MR;
-        const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
-        hipLaunchKernelGGL((momentum_tile<WU, WV>), dim3(grid), dim3(64 * tpb), 0, s, a, ld, ub, vb, x0, x1, y0, y1, c_first, nxw);
+    if (lanes16_fit(ld, gr->tmask, a.f, NF) && lanes16_fit(ld, nullptr, outs, 2) && tuning("mom_kernel", 0) == 0) {
+        TilePlan t;
+        if (int rc = tile_plan(who, ld, x0, x1, y0, y1, CHUNKS_ALL, MR, SHAPE_FOUR, 4, &t)) return rc;      // __launch_bounds__(256)
+        hipLaunchKernelGGL((momentum_tile<WU, WV>), dim3(t.grid), dim3(64 * t.tpb), 0, s, a, ld, ub, vb, x0, x1, y0, y1, t.c_first, t.nxw);
     } else {
-        const int h = y1 - y0 + 1;
-        hipLaunchKernelGGL((momentum_direct<WU, WV>), dim3((x1 - x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, s, a, ld,
-                           ub, vb, x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL((momentum_direct<WU, WV>), dim3(g.x, g.y), dim3(256), 0, s, a, ld, ub, vb, x0, x1, y0, y1);
     }
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;
@@ -251,9 +243,10 @@ int next_ssh_launch(const char *who, int ld, int ny, int xstart, int xstop, int 
     DLESM_REQUIRE(!overlap(out, nb, tmask, nb / 2) && !overlap(out, nb, area_t, nb) && !overlap(out, nb, area_x, nb) &&
                       !overlap(out, nb, sshn_t, nb),
                   "%s: the output overlaps an input", who);
-    const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1, h = y1 - y0 + 1;
-    hipLaunchKernelGGL((next_ssh<DI, DJ>), dim3((x1 - x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, (hipStream_t)stream,
-                       tmask, area_t, area_x, sshn_t, out, ld, x0, x1, y0, y1);
+    const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
+    const DirectGrid g = direct_grid(x0, x1, y0, y1);
+    hipLaunchKernelGGL((next_ssh<DI, DJ>), dim3(g.x, g.y), dim3(256), 0, (hipStream_t)stream, tmask, area_t, area_x, sshn_t, out,
+                       ld, x0, x1, y0, y1);
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;
 }

@@ -24,7 +24,7 @@
 // ssha on T == 0 cells; dlesm_nemolite_step_wet_f64 runs the same tile body on the others only -- one bit per tile read on a
 // wave-uniform address in today's launch, trimmed to the rows that hold an active tile (the flag map), or a grid of the
 // active tiles alone, each wave taking its tile from a row-major list (HOOK key nemo_wet_form = 1).  The plan and the
-// launcher take the tile geometry from step_tiles(), the one place it is written.
+// launcher take the tile geometry from dlesm_tile_plan.h, the one place it is written.
 #include <climits>
 #include <vector>
 
@@ -34,7 +34,7 @@
 struct dlesm_wet_plan {
     int ld, ny;
     dlesm_region box;         // the box it was made for (1-based inclusive, as given)
-    int c_first, chunks, nxt; // the tile geometry it was made for (step_tiles)
+    int c_first, chunks, nxt; // the tile geometry it was made for (tile_geometry)
     long long tiles, active;
     int row_lo, row_hi;       // the first and last row (0-based, relative to the box) that holds an active tile
     unsigned *bits;           // HBM: one bit per tile, row-major, tile t in word t / 32; NULL when tiles == 0
@@ -51,21 +51,8 @@ typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
 
-// The wave tiles of the sweep over a box: TILE_CHUNKS chunks of 2 columns x 1 row, anchored on a 128-byte line of the row.
-// The kernel, its launcher and the wet plan all take the geometry from here.
-constexpr int TILE_CHUNKS = 63;
-struct StepTiles {
-    int x0, x1, y0, y1;       // the box, 0-based inclusive
-    int c_first, nxt;         // the first chunk of tile 0; tiles per row
-    long long tiles() const { return (long long)nxt * (y1 - y0 + 1); }
-};
-StepTiles step_tiles(const dlesm_region *box)
-{
-    StepTiles g{box->xstart - 1, box->xstop - 1, box->ystart - 1, box->ystop - 1, 0, 0};
-    g.c_first = (g.x0 / 2) & ~7;
-    g.nxt = (g.x1 / 2 - g.c_first + TILE_CHUNKS) / TILE_CHUNKS;
-    return g;
-}
+// chunks (2 columns) a wave tile owns; the kernel, its launcher and the wet plan take the geometry from dlesm_tile_plan.h
+constexpr int TILE_CHUNKS = CHUNKS_EAST;
 
 // how a launch finds its tiles: FULL = every tile of the box (today's sweep), FLAGS = every tile of rows y0 .. that has its
 // bit set, LIST = the tiles of a list
@@ -262,7 +249,7 @@ int nemo::wet_check(const char *who, const dlesm_wet_plan *wet, int ld, int ny, 
                   wet->box.xstart, wet->box.xstop, wet->box.ystart, wet->box.ystop, tbox->xstart, tbox->xstop, tbox->ystart,
                   tbox->ystop);
     if (!empty(tbox)) {
-        const StepTiles g = step_tiles(tbox);
+        const TilePlan g = tile_geometry(tbox->xstart - 1, tbox->xstop - 1, tbox->ystart - 1, tbox->ystop - 1, TILE_CHUNKS, 1);
         DLESM_REQUIRE(wet->c_first == g.c_first && wet->chunks == TILE_CHUNKS && wet->nxt == g.nxt && wet->tiles == g.tiles(),
                       "%s: the wet plan was made for another tile geometry", who);
     }
@@ -292,9 +279,7 @@ int step_impl(const char *who, const dlesm_wet_plan *wet, const dlesm_momentum_p
                                    grid->fcor_v};
     double *const outs[5] = {ssha, ssha_u, ssha_v, ua, va};
 
-    bool aligned = ld % 2 == 0 && (uintptr_t)grid->tmask % 8 == 0;
-    for (const double *p : ins) aligned = aligned && (uintptr_t)p % 16 == 0;
-    for (const double *p : outs) aligned = aligned && (uintptr_t)p % 16 == 0;
+    const bool aligned = lanes16_fit(ld, grid->tmask, ins, 19) && lanes16_fit(ld, nullptr, outs, 5);
     hipStream_t st = (hipStream_t)stream;
     if (same_box(tbox, ubox) && same_box(tbox, vbox) && aligned && tuning("nemo_step_kernel", 0) == 0) {
         if (!empty(tbox)) {
@@ -308,25 +293,24 @@ int step_impl(const char *who, const dlesm_wet_plan *wet, const dlesm_momentum_p
             s.m.rdt = params->rdt, s.m.visc = params->visc, s.m.g = params->g;
             s.m.den = 1.0 + params->cbfr * params->rdt;
             s.area_t = area_t, s.ssha = ssha, s.ssha_u = ssha_u, s.ssha_v = ssha_v;
-            const StepTiles g = step_tiles(tbox);               // tiles anchored on 128-byte lines of the row
-            int nxw = g.nxt, tpb = 4;
-            choose_block_shape(&nxw, &tpb, 4);
-            if (tpb > 4) tpb = 4;                               // __launch_bounds__(256)
+            const int x0 = tbox->xstart - 1, x1 = tbox->xstop - 1, y0 = tbox->ystart - 1, y1 = tbox->ystop - 1;
+            TilePlan g;
+            if (int rc = tile_plan(who, ld, x0, x1, y0, y1, TILE_CHUNKS, 1, SHAPE_FOUR, 4, &g)) return rc;   // __launch_bounds__(256)
+            unsigned nblk;
             if (!wet || wet->active == wet->tiles) {            // every tile: today's kernel, today's launch shape
-                const unsigned nblk = (unsigned)(((long)nxw * (g.y1 - g.y0 + 1) + tpb - 1) / tpb);
-                hipLaunchKernelGGL(nemolite_step_tile<FULL>, dim3(nblk), dim3(64 * tpb), 0, st, s, ld, g.x0, g.x1, g.y0,
-                                   g.y1, g.c_first, nxw, WetArgs{});
+                hipLaunchKernelGGL(nemolite_step_tile<FULL>, dim3(g.grid), dim3(64 * g.tpb), 0, st, s, ld, x0, x1, y0, y1, g.c_first,
+                                   g.nxw, WetArgs{});
             } else if (wet->active == 0) {                      // all land: nothing to sweep
             } else if (tuning("nemo_wet_form", 0) == 1) {       // the compacted list: one wave per active tile
                 const WetArgs wa{nullptr, wet->list, 0, g.nxt, (int)wet->active};
-                const unsigned nblk = (unsigned)((wet->active + 3) / 4);
-                hipLaunchKernelGGL(nemolite_step_tile<LIST>, dim3(nblk), dim3(256), 0, st, s, ld, g.x0, g.x1, g.y0, g.y1,
-                                   g.c_first, g.nxt, wa);
+                if (int rc = sweep_grid(who, (wet->active + 3) / 4, &nblk)) return rc;
+                hipLaunchKernelGGL(nemolite_step_tile<LIST>, dim3(nblk), dim3(256), 0, st, s, ld, x0, x1, y0, y1, g.c_first,
+                                   g.nxt, wa);
             } else {                                            // the flag map: today's shape over the rows row_lo .. row_hi
                 const WetArgs wa{wet->bits, nullptr, (long long)wet->row_lo * g.nxt, g.nxt, 0};
-                const unsigned nblk = (unsigned)(((long)nxw * (wet->row_hi - wet->row_lo + 1) + tpb - 1) / tpb);
-                hipLaunchKernelGGL(nemolite_step_tile<FLAGS>, dim3(nblk), dim3(64 * tpb), 0, st, s, ld, g.x0, g.x1,
-                                   g.y0 + wet->row_lo, g.y1, g.c_first, nxw, wa);
+                if (int rc = sweep_grid(who, g.groups_for(wet->row_hi - wet->row_lo + 1), &nblk)) return rc;
+                hipLaunchKernelGGL(nemolite_step_tile<FLAGS>, dim3(nblk), dim3(64 * g.tpb), 0, st, s, ld, x0, x1, y0 + wet->row_lo,
+                                   y1, g.c_first, g.nxw, wa);
             }
             DLESM_HIP_TRY(hipGetLastError());
         }
@@ -367,7 +351,8 @@ extern "C" int dlesm_wet_plan_create(const int *tmask_host, int ld, int ny, cons
             delete p;
             return rc;
         }
-        const StepTiles g = step_tiles(box);
+        const int x0 = box->xstart - 1, x1 = box->xstop - 1, y0 = box->ystart - 1, y1 = box->ystop - 1;
+        const TilePlan g = tile_geometry(x0, x1, y0, y1, TILE_CHUNKS, 1);
         if (g.tiles() > INT_MAX) {
             delete p;
             return fail(DLESM_EINVAL, "%s: %lld tiles do not fit the plan's int32 tile index", who, g.tiles());
@@ -377,19 +362,19 @@ extern "C" int dlesm_wet_plan_create(const int *tmask_host, int ld, int ny, cons
         // One pass over the mask per tile row.  A tile is inactive only if the sweep would store nothing but ssha on T == 0
         // cells in it: no owned cell of the box has T(i,j) != 0, T(i+1,j) > 0 (its ssha_u is written) or T(i,j+1) > 0 (its
         // ssha_v is written).
-        for (int j = g.y0; j <= g.y1; j++) {
+        for (int j = y0; j <= y1; j++) {
             const int *t = tmask_host + (size_t)j * ld, *tn = t + ld;
             for (int xw = 0; xw < g.nxt; xw++) {
                 const int lo = (g.c_first + xw * TILE_CHUNKS) * 2, hi = lo + 2 * TILE_CHUNKS - 1;
                 bool on = false;
-                for (int i = lo < g.x0 ? g.x0 : lo; i <= (hi > g.x1 ? g.x1 : hi) && !on; i++)
+                for (int i = lo < x0 ? x0 : lo; i <= (hi > x1 ? x1 : hi) && !on; i++)
                     on = t[i] != 0 || t[i + 1] > 0 || tn[i] > 0;
                 if (!on) continue;
-                const long long k = (long long)(j - g.y0) * g.nxt + xw;
+                const long long k = (long long)(j - y0) * g.nxt + xw;
                 bits[(size_t)(k >> 5)] |= 1u << (k & 31);
                 list.push_back((int)k);
-                if (p->row_hi < 0) p->row_lo = j - g.y0;
-                p->row_hi = j - g.y0;
+                if (p->row_hi < 0) p->row_lo = j - y0;
+                p->row_hi = j - y0;
             }
         }
         p->active = (long long)list.size();

@@ -2,7 +2,7 @@
 // fixed tree of levels reduces the records to one, and that one goes to the caller, asynchronously or through a host copy.
 //
 // The two Courant checks (dlesm_courant.hip; dlesm_flow_courant.hip, section 6.15) take all of it: the
-// three kernel bodies, the sweep plan, the driver and the pointer checks.  Each supplies a policy type P:
+// three kernel bodies, the driver (its launch plan: dlesm_tile_plan.h) and the pointer checks.  Each supplies a policy type P:
 //   Args, Acc, Record, Counts        the kernel's operands, what a thread / wave / workgroup has seen, the caller's record, and
 //                                    the packed counts of a lane's cells of one wave tile
 //   identity(), merge(a, b)          Acc's "nothing seen yet" and its combine
@@ -29,7 +29,7 @@ namespace dlesm {
 
 namespace recred {
 
-constexpr int TILE_CHUNKS = 63;       // chunks (2 columns) a wave owns; lane 63 only loads
+constexpr int TILE_CHUNKS = CHUNKS_EAST;      // chunks (2 columns) a wave owns; lane 63 only loads
 constexpr int LEVEL_CHUNK = 1024;     // records per workgroup of a level
 constexpr double BIGGEST = 1.7976931348623157e308;
 constexpr long long NO_INDEX = LLONG_MAX;
@@ -133,37 +133,6 @@ inline int check_result_apart(const char *who, const void *result_dev, size_t by
         DLESM_REQUIRE(!nemo::overlap(result_dev, bytes, ins[k], nb), "%s: result_dev lies inside %s", who, name[k]);
     return DLESM_OK;
 }
-// may the sweep take 16-byte lanes (the wave-tile kernel)?
-inline bool lanes16_fit(int ld, const int *tmask, const double *const *ins, int n)
-{
-    bool ok = ld % 2 == 0 && (uintptr_t)tmask % 8 == 0;
-    for (int k = 0; k < n; k++) ok = ok && (uintptr_t)ins[k] % 16 == 0;
-    return ok;
-}
-
-// the sweep's launch shape = its number of records
-struct SweepPlan {
-    int c_first, nxw, tpb;            // the wave-tile kernel: first chunk, tiles per row, waves per workgroup
-    int gx, gy;                       // the one-cell-per-thread kernel: its grid
-    long long nrec;
-};
-// columns x0..x1 (0-based) of `rows` rows; rows = 0: an empty box, no record
-inline SweepPlan plan_sweep(int x0, int x1, long long rows, bool tile)
-{
-    SweepPlan p{0, 0, 4, 0, 0, 0};
-    if (rows <= 0) return p;
-    if (tile) {
-        p.c_first = (x0 / 2) & ~7;                       // tiles anchored on a 128-byte line of the row
-        p.nxw = (x1 / 2 - p.c_first + TILE_CHUNKS) / TILE_CHUNKS;
-        choose_block_shape(&p.nxw, &p.tpb, 4);
-        if (p.tpb > 4) p.tpb = 4;                        // __launch_bounds__(256)
-        p.nrec = ((long long)p.nxw * rows + p.tpb - 1) / p.tpb;
-    } else {
-        p.gx = (x1 - x0 + 256) / 256, p.gy = (int)(rows > 4096 ? 4096 : rows);
-        p.nrec = (long long)p.gx * p.gy;
-    }
-    return p;
-}
 
 // The tail of a record reduction, behind its last launch: n records from result_dev back through a copy on `s` that the host
 // waits for (result_host != nullptr; at most N of them), the scratch given back on every path, then the errors in the order
@@ -200,9 +169,14 @@ int run(const char *who, const Kernels<P> &k, const typename P::Args &a, int ld,
         bool tile, typename P::Record *result_dev, typename P::Record *result_host, hipStream_t s)
 {
     using Record = typename P::Record;
-    const SweepPlan p = plan_sweep(x0, x1, empty ? 0 : (long long)y1 - y0 + 1, tile);
-    const long long nrec = p.nrec;
-    DLESM_REQUIRE(nrec <= INT_MAX, "%s: %lld workgroups in one sweep (at most %d)", who, nrec, INT_MAX);
+    // the sweep's launch shape = its number of records; an empty box: no record
+    TilePlan p{};
+    DirectGrid g{};
+    if (!empty && !tile) g = direct_grid(x0, x1, y0, y1);
+    if (!empty && tile)
+        if (int rc = tile_plan(who, ld, x0, x1, y0, y1, TILE_CHUNKS, 1, SHAPE_FOUR, 4, &p)) return rc;   // __launch_bounds__(256)
+    unsigned nrec;
+    if (int rc = sweep_grid(who, tile ? p.grid : (long long)g.x * g.y, &nrec)) return rc;
     const long long above = tree_records(nrec, LEVEL_CHUNK);
 
     Record *scratch = nullptr;
@@ -210,10 +184,9 @@ int run(const char *who, const Kernels<P> &k, const typename P::Args &a, int ld,
     if (!result_dev) result_dev = scratch + nrec + above;
     if (nrec > 0) {
         if (tile)
-            hipLaunchKernelGGL(k.tile, dim3((unsigned)nrec), dim3(64 * p.tpb), 0, s, a, ld, x0, x1, y0, y1, p.c_first, p.nxw,
-                               scratch);
+            hipLaunchKernelGGL(k.tile, dim3(nrec), dim3(64 * p.tpb), 0, s, a, ld, x0, x1, y0, y1, p.c_first, p.nxw, scratch);
         else
-            hipLaunchKernelGGL(k.direct, dim3((unsigned)p.gx, (unsigned)p.gy), dim3(256), 0, s, a, ld, x0, x1, y0, y1, scratch);
+            hipLaunchKernelGGL(k.direct, dim3(g.x, g.y), dim3(256), 0, s, a, ld, x0, x1, y0, y1, scratch);
     }
     // levels of LEVEL_CHUNK until one record is left, that one into *result_dev
     const Record *src = scratch;

@@ -320,24 +320,19 @@ int launch_kernel(const char *who, const KArgs &a, int ld, int ny, int xstart, i
             DLESM_REQUIRE(!(K::W || K::E || K::S || K::N), "%s: the output aliases an input read at neighbouring points", who);
     hipStream_t s = (hipStream_t)stream;
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
-    // 16-byte lanes; on an odd leading dimension (rows alternately 8-byte aligned) only while every column read
-    // stays inside the last whole 2-column chunk of a row
-    bool aligned = ld % 2 == 0 || x1 + (K::E ? 1 : 0) <= 2 * (ld / 2) - 1;
-    aligned = aligned && (uintptr_t)a.out % 16 == 0;
-    for (int n = 0; n < K::NIN; n++) aligned = aligned && (uintptr_t)a.in[n] % 16 == 0;
+    // 16-byte lanes; on an odd leading dimension only while every column read stays inside the last whole 2-column chunk of
+    // a row: the rule reads column east0 + 1, here x1 + 1 for a kernel that reads its east neighbour and x1 for one that does not
+    const bool aligned = sw_lanes16_fit(ld, x1 - (K::E ? 0 : 1), a.in, K::NIN) && all_16_byte(&a.out, 1);
     const int nx = x1 - x0 + 1, h = y1 - y0 + 1;
     const bool thin = nx <= SW_THIN_BOX && h > 8;
     if (aligned && !thin && tuning("swk_kernel", 0) == 0) {
         constexpr int R = 2;
-        const int cb = (x0 / 2) & ~7, c_last = x1 / 2;        // tiles anchored on 128-byte lines of the row
-        int nxw = (c_last - cb + 64) / 64, tpb = 4;
         // 4 waves per group, a quarter of a group past / short of a multiple of 8 groups per row: measured at 8192^2
         // (scripts/shallow_r3_probe.py --what kernels,shapes: 65 tiles per row) every kernel of the set is fastest at
         // 4 waves x 65 tiles (16.25 groups per row), 1-2 points above 8 waves x 66 tiles, the Jacobi rule's choice
-        choose_block_shape(&nxw, &tpb, 4);
-        if (tpb > 8) tpb = 8;                                  // the kernel is bounded to 512 threads
-        const int strips = (h + R - 1) / R;
-        const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
+        TilePlan p;
+        if (int rc = tile_plan(who, ld, x0, x1, y0, y1, CHUNKS_ALL, R, SHAPE_FOUR, 8, &p)) return rc;   // bounded to 512 threads
+        const int cb = p.c_first, nxw = p.nxw, tpb = p.tpb;
         // Store policy: as the other sweeps, non-temporal once the arrays outgrow the Infinity Cache.  A kernel that updates
         // an array IN PLACE (time_smooth) writes the line it has just read: with ordinary loads that line sits in L2 when the
         // store arrives, and the kernel ran at 66-68 % of peak whatever the store policy; with non-temporal loads AND stores
@@ -349,12 +344,13 @@ int launch_kernel(const char *who, const KArgs &a, int ld, int ny, int xstart, i
         const int key = tuning("swk_nt", -1), lkey = tuning("swk_ntl", -1);
         const bool nts = key >= 0 ? key != 0 : nt_stores_for(ld, y0, y1) != 0;
         const bool ntl = lkey >= 0 ? lkey != 0 : (in_place && nts);
-        if (nts && ntl) hipLaunchKernelGGL((swk_tile<K, R, true, true>), dim3(grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
-        else if (nts) hipLaunchKernelGGL((swk_tile<K, R, true>), dim3(grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
-        else if (ntl) hipLaunchKernelGGL((swk_tile<K, R, false, true>), dim3(grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
-        else hipLaunchKernelGGL((swk_tile<K, R, false>), dim3(grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
+        if (nts && ntl) hipLaunchKernelGGL((swk_tile<K, R, true, true>), dim3(p.grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
+        else if (nts) hipLaunchKernelGGL((swk_tile<K, R, true>), dim3(p.grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
+        else if (ntl) hipLaunchKernelGGL((swk_tile<K, R, false, true>), dim3(p.grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
+        else hipLaunchKernelGGL((swk_tile<K, R, false>), dim3(p.grid), dim3(64 * tpb), 0, s, a, ld, x0, x1, y0, y1, cb, nxw);
     } else {
-        hipLaunchKernelGGL((swk_direct<K>), dim3((nx + 255) / 256, h > 4096 ? 4096 : h), dim3(256), 0, s, a, ld, x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL((swk_direct<K>), dim3(g.x, g.y), dim3(256), 0, s, a, ld, x0, x1, y0, y1);
     }
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;

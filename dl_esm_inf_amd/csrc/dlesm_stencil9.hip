@@ -199,24 +199,17 @@ int launch_stencil9_framed(const double *in, double *out, const double *coef, in
     if (int rc = check_box("dlesm_stencil9_step_dm", ld, ny, xstart, xstop, ystart, ystop, 1)) return rc;
     DLESM_REQUIRE(in != nullptr && out != nullptr && coef != nullptr && in != out, "stencil9: null or aliased arrays");
     DLESM_REQUIRE(job.counter != nullptr && job.flag != nullptr, "stencil9 framed: no signal words");
-    if (!(ld % 2 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && tuning("s9_kernel", 0) == 0)) return DLESM_OK;
+    if (!(lanes16_fit(ld, nullptr, {in, out}) && tuning("s9_kernel", 0) == 0)) return DLESM_OK;
     const Coef9 k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8]};
     job.fx0 = xstart - 1, job.fx1 = xstop - 1, job.fy0 = ystart - 1, job.fy1 = ystop - 1;
     const int x0 = xstart, x1 = xstop - 2, y0 = ystart, y1 = ystop - 2;      // the interior, 0-based
-    const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;
-    int nxw = (c_last - c_first + 64) / 64, tpb = 4;
-    choose_block_shape(&nxw, &tpb);
-    const int strips = (y1 - y0 + R) / R;
-    const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
+    TilePlan p;
+    if (int rc = tile_plan("dlesm_stencil9_step_dm", ld, x0, x1, y0, y1, CHUNKS_ALL, R, SHAPE_RULE, 16, &p)) return rc;
     const long cells = 2L * (job.fx1 - job.fx0 + 1) + 2L * (job.fy1 - job.fy0 + 1);
-    long nb = ((cells + 64 * tpb - 1) / (64 * tpb) + 7) & ~7L;               // a multiple of 8: tile groups keep their XCD
+    long nb = ((cells + 64 * p.tpb - 1) / (64 * p.tpb) + 7) & ~7L;           // a multiple of 8: tile groups keep their XCD
     job.nblocks = (int)(nb < 8 ? 8 : nb > 256 ? 256 : nb);
-    if (nt_stores_for(ld, y0, y1))
-        hipLaunchKernelGGL(stencil9_tile_framed<true>, dim3(grid + job.nblocks), dim3(64 * tpb), 0, s, in, out, k, ld, x0, x1,
-                           y0, y1, c_first, nxw, job);
-    else
-        hipLaunchKernelGGL(stencil9_tile_framed<false>, dim3(grid + job.nblocks), dim3(64 * tpb), 0, s, in, out, k, ld, x0, x1,
-                           y0, y1, c_first, nxw, job);
+    const auto tile = nt_stores_for(ld, y0, y1) ? stencil9_tile_framed<true> : stencil9_tile_framed<false>;
+    hipLaunchKernelGGL(tile, dim3(p.grid + job.nblocks), dim3(64 * p.tpb), 0, s, in, out, k, ld, x0, x1, y0, y1, p.c_first, p.nxw, job);
     DLESM_HIP_TRY(hipGetLastError());
     *fused = true;
     return DLESM_OK;
@@ -230,21 +223,14 @@ int launch_stencil9(const double *in, double *out, const double *coef, int ld, i
     DLESM_REQUIRE(in != nullptr && out != nullptr && coef != nullptr && in != out, "stencil9: null or aliased arrays");
     const Coef9 k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8]};
     const int x0 = xstart - 1, x1 = xstop - 1, y0 = ystart - 1, y1 = ystop - 1;
-    const bool tile = ld % 2 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && tuning("s9_kernel", 0) == 0;
-    if (tile) {
-        const int c_first = (x0 / 2) & ~7, c_last = x1 / 2;  // tiles anchored on 128-byte lines of the row
-        int nxw = (c_last - c_first + 64) / 64, tpb = 4;
-        shape_for_tile_sweep(ld, x0, x1, y0, y1, &nxw, &tpb);
-        const int strips = (y1 - y0 + R) / R;
-        const unsigned grid = (unsigned)(((long)nxw * strips + tpb - 1) / tpb);
-        if (nt_stores_for(ld, y0, y1))
-            hipLaunchKernelGGL(stencil9_tile<true>, dim3(grid), dim3(64 * tpb), 0, s, in, out, k, ld, x0, x1, y0, y1, c_first, nxw);
-        else
-            hipLaunchKernelGGL(stencil9_tile<false>, dim3(grid), dim3(64 * tpb), 0, s, in, out, k, ld, x0, x1, y0, y1, c_first, nxw);
+    if (lanes16_fit(ld, nullptr, {in, out}) && tuning("s9_kernel", 0) == 0) {
+        TilePlan p;
+        if (int rc = tile_plan("dlesm_stencil9_f64", ld, x0, x1, y0, y1, CHUNKS_ALL, R, SHAPE_PLANNED, 16, &p)) return rc;
+        const auto tile = nt_stores_for(ld, y0, y1) ? stencil9_tile<true> : stencil9_tile<false>;
+        hipLaunchKernelGGL(tile, dim3(p.grid), dim3(64 * p.tpb), 0, s, in, out, k, ld, x0, x1, y0, y1, p.c_first, p.nxw);
     } else {
-        const int h = y1 - y0 + 1;
-        hipLaunchKernelGGL(stencil9_direct, dim3((x1 - x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, s, in, out, k,
-                           ld, x0, x1, y0, y1);
+        const DirectGrid g = direct_grid(x0, x1, y0, y1);
+        hipLaunchKernelGGL(stencil9_direct, dim3(g.x, g.y), dim3(256), 0, s, in, out, k, ld, x0, x1, y0, y1);
     }
     DLESM_HIP_TRY(hipGetLastError());
     return DLESM_OK;

@@ -45,7 +45,7 @@ typedef int i2 __attribute__((ext_vector_type(2)));
 
 using namespace nemo;
 
-constexpr int TILE_CHUNKS = 63;       // chunks (2 columns) a wave owns; lane 63 only loads
+constexpr int TILE_CHUNKS = CHUNKS_EAST;      // chunks (2 columns) a wave owns; lane 63 only loads
 constexpr int NT_MAX = 4;             // tracers per launch
 
 template <int NT> struct TracerArgs {
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void tracer_direct(TracerArgs<NT> a, int ld, i
 
 // ---- second-order limited transport ----------------------------------------------------------
 
-constexpr int MUSCL_CHUNKS = 62;      // chunks a wave owns; lanes 0 and 63 only load
+constexpr int MUSCL_CHUNKS = CHUNKS_BOTH;     // chunks a wave owns; lanes 0 and 63 only load
 
 // what one tracer's update reads: rows j-2 .. j+2 of the lane's two columns
 struct MusclRows {
@@ -334,7 +334,8 @@ enum Scheme { SCHEME_UPWIND = 0, SCHEME_MUSCL = 1, SCHEME_HANCOCK = 2 };    // s
 struct Launch {
     bool tile;
     Scheme scheme;
-    int ld, ny, x0, x1, y0, y1, c_first, nxw, tpb;
+    int ld, ny, x0, x1, y0, y1;
+    TilePlan p;               // tile: its plan
     hipStream_t st;
 };
 
@@ -344,25 +345,21 @@ void launch(const Launch &l, double rdt, const TracerFields &f, const double *co
     TracerArgs<NT> a{};
     a.f = f, a.rdt = rdt;
     for (int k = 0; k < NT; k++) a.c_in[k] = c_in[k], a.c_out[k] = c_out[k];
-    const int h = l.y1 - l.y0 + 1;
+    const DirectGrid g = direct_grid(l.x0, l.x1, l.y0, l.y1);
     if (l.scheme != SCHEME_UPWIND) {
         if (l.tile) {
-            const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
             const auto tile = l.scheme == SCHEME_HANCOCK ? tracer_muscl_tile<NT, true> : tracer_muscl_tile<NT, false>;
-            hipLaunchKernelGGL(tile, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1, l.c_first,
-                               l.nxw);
+            hipLaunchKernelGGL(tile, dim3(l.p.grid), dim3(64 * l.p.tpb), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1,
+                               l.p.c_first, l.p.nxw);
         } else {
             const auto direct = l.scheme == SCHEME_HANCOCK ? tracer_muscl_direct<NT, true> : tracer_muscl_direct<NT, false>;
-            hipLaunchKernelGGL(direct, dim3((l.x1 - l.x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, l.st, a, l.ld, l.ny,
-                               l.x0, l.x1, l.y0, l.y1);
+            hipLaunchKernelGGL(direct, dim3(g.x, g.y), dim3(256), 0, l.st, a, l.ld, l.ny, l.x0, l.x1, l.y0, l.y1);
         }
     } else if (l.tile) {
-        const unsigned nblk = (unsigned)(((long)l.nxw * h + l.tpb - 1) / l.tpb);
-        hipLaunchKernelGGL(tracer_tile<NT>, dim3(nblk), dim3(64 * l.tpb), 0, l.st, a, l.ld, l.x0, l.x1, l.y0, l.y1, l.c_first,
-                           l.nxw);
+        hipLaunchKernelGGL(tracer_tile<NT>, dim3(l.p.grid), dim3(64 * l.p.tpb), 0, l.st, a, l.ld, l.x0, l.x1, l.y0, l.y1,
+                           l.p.c_first, l.p.nxw);
     } else {
-        hipLaunchKernelGGL(tracer_direct<NT>, dim3((l.x1 - l.x0 + 256) / 256, h > 4096 ? 4096 : h), dim3(256), 0, l.st, a,
-                           l.ld, l.x0, l.x1, l.y0, l.y1);
+        hipLaunchKernelGGL(tracer_direct<NT>, dim3(g.x, g.y), dim3(256), 0, l.st, a, l.ld, l.x0, l.x1, l.y0, l.y1);
     }
 }
 
@@ -409,10 +406,8 @@ int tracer_step(const char *who, Scheme scheme, double rdt, int ld, int ny, int 
     if (int rc = tracer_check(who, ld, ny, xstart, xstop, ystart, ystop, f, c_in, c_out, ntracers)) return rc;
     if (xstop < xstart || ystop < ystart) return DLESM_OK;   // empty box: a zero-trip loop nest
 
-    bool aligned = ld % 2 == 0 && (uintptr_t)f.tmask % 8 == 0;
-    for (const double *p : {f.area_t, f.un, f.vn, f.hu, f.hv, f.ht, f.sshn_t, f.sshn_u, f.sshn_v, f.ssha})
-        aligned = aligned && (uintptr_t)p % 16 == 0;
-    for (int k = 0; k < ntracers; k++) aligned = aligned && (uintptr_t)c_in[k] % 16 == 0 && (uintptr_t)c_out[k] % 16 == 0;
+    const bool aligned = lanes16_fit(ld, f.tmask, {f.area_t, f.un, f.vn, f.hu, f.hv, f.ht, f.sshn_t, f.sshn_u, f.sshn_v, f.ssha}) &&
+                         lanes16_fit(ld, nullptr, c_in, ntracers) && lanes16_fit(ld, nullptr, c_out, ntracers);
 
     Launch l{};
     static const char *const hook[3] = {"tracer_kernel", "tracer_muscl_kernel", "tracer_hancock_kernel"};
@@ -422,10 +417,7 @@ int tracer_step(const char *who, Scheme scheme, double rdt, int ld, int ny, int 
     l.st = (hipStream_t)stream;
     if (l.tile) {
         const int chunks = scheme != SCHEME_UPWIND ? MUSCL_CHUNKS : TILE_CHUNKS;
-        l.c_first = (l.x0 / 2) & ~7;                     // tiles anchored on a 128-byte line of the row
-        l.nxw = (l.x1 / 2 - l.c_first + chunks) / chunks, l.tpb = 4;
-        choose_block_shape(&l.nxw, &l.tpb, 4);
-        if (l.tpb > 4) l.tpb = 4;                        // __launch_bounds__(256)
+        if (int rc = tile_plan(who, ld, l.x0, l.x1, l.y0, l.y1, chunks, 1, SHAPE_FOUR, 4, &l.p)) return rc;   // __launch_bounds__(256)
     }
     // at most NT_MAX tracers per launch: 5..8 tracers are two launches, each loading the flow once
     for (int k = 0; k < ntracers; k += NT_MAX) {
