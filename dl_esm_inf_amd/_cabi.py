@@ -302,6 +302,11 @@ PROTOTYPES = {
     "dlesm_drifters_get": (_i, [_vp, _vp, _vp, _vp]),
     "dlesm_drifters_arrays": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "dlesm_drifters_destroy": (_i, [_vp]),
+    "dlesm_particle_order_scratch": (_i, [C.c_longlong, C.POINTER(C.c_longlong)]),
+    "dlesm_particle_order_f64": (_i, [_i] * 4 + [C.c_longlong] + [_vp] * 6 + [C.c_longlong, _vp]),
+    "dlesm_particle_permute": (_i, [C.c_longlong, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _vp]),
+    "dlesm_particle_sort_set": (_i, [_vp, _i, _i, _i, _i, _vp]),
+    "dlesm_particle_set_origin": (_i, [_vp, _vp, C.POINTER(C.c_longlong)]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

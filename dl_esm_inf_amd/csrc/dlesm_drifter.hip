@@ -191,15 +191,7 @@ extern "C" int dlesm_drifter_sample_f64(int ld, int ny, int xstart, int xstop, i
     return DLESM_OK;
 }
 
-// ---- the owner of the three arrays
-struct dlesm_drifters {
-    uint64_t magic;
-    long long n;
-    double *px, *py;
-    int *status;
-};
-static const uint64_t DLESM_DRIFTERS_MAGIC = 0x444c45534d445246ULL; // "DLESMDRF"
-
+// ---- the owner of the three arrays (the struct: dlesm_internal.h)
 static int drifters_ok(const char *who, const dlesm_drifters *set)
 {
     DLESM_REQUIRE(set != nullptr && set->magic == DLESM_DRIFTERS_MAGIC, "%s: not a drifter set", who);
@@ -213,8 +205,9 @@ extern "C" int dlesm_drifters_create(long long n, dlesm_drifters **set)
     DLESM_REQUIRE(set != nullptr, "%s: null set", who);
     *set = nullptr;
     DLESM_REQUIRE(n >= 0, "%s: %lld particles", who, n);
-    dlesm_drifters *d = new (std::nothrow) dlesm_drifters{DLESM_DRIFTERS_MAGIC, n, nullptr, nullptr, nullptr};
+    dlesm_drifters *d = new (std::nothrow) dlesm_drifters{};
     if (!d) return fail(DLESM_EHIP, "%s: out of host memory", who);
+    d->magic = DLESM_DRIFTERS_MAGIC, d->n = n;
     if (n > 0) {
         // one allocation: px | py | status (each 8-byte aligned)
         void *base = nullptr;
@@ -240,6 +233,7 @@ extern "C" int dlesm_drifters_put(dlesm_drifters *set, const double *px, const d
     DLESM_REQUIRE(px != nullptr && py != nullptr, "%s: null px or py", who);
     if (set->n == 0) return DLESM_OK;
     const size_t n = (size_t)set->n;
+    set->sorted = false;                                 // origin is the identity again (section 6.18)
     DLESM_HIP_TRY(hipMemcpy(set->px, px, n * 8, hipMemcpyHostToDevice));
     DLESM_HIP_TRY(hipMemcpy(set->py, py, n * 8, hipMemcpyHostToDevice));
     if (status) DLESM_HIP_TRY(hipMemcpy(set->status, status, n * 4, hipMemcpyHostToDevice));
@@ -276,6 +270,7 @@ extern "C" int dlesm_drifters_destroy(dlesm_drifters *set)
     if (int rc = drifters_ok("dlesm_drifters_destroy", set)) return rc;
     set->magic = 0;
     if (set->px) (void)hipFree(set->px);
+    if (set->sort_mem) (void)hipFree(set->sort_mem);
     delete set;
     return DLESM_OK;
 }

@@ -19,9 +19,24 @@ struct dlesm_obc {
     int *dev;         // one allocation: t[nt] | uf[nu] ui[nu] uo[nu] | vf[nv] vi[nv] vo[nv]; NULL when all lists are empty
 };
 
+// the owner of the particle arrays (dlesm_drifter.hip makes it; dlesm_particle_sort.hip orders it)
+struct dlesm_drifters {
+    uint64_t magic;
+    long long n;
+    double *px, *py;           // one allocation: px | py | status
+    int *status;
+    // made by the first dlesm_particle_sort_set: one allocation, px2 | py2 | status2 | origin2 | origin | perm | nlive | scratch
+    void *sort_mem;
+    int *origin, *perm, *nlive;
+    void *scratch;
+    long long scratch_bytes;
+    bool sorted;               // origin and nlive are those of a sort since the last put
+};
+static const uint64_t DLESM_DRIFTERS_MAGIC = 0x444c45534d445246ULL; // "DLESMDRF"
+
 namespace dlesm {
 
-#define DLESM_HIP_TRY(expr)                                                                 \
+#define DLESM_HIP_TRY(expr)                                                                \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
         if (_e != hipSuccess)                                                               \

@@ -80,7 +80,8 @@ module dlesm_hip_mod
   end type flow_courant_type
 
   !> A set of drifters on the device (DESIGN.md section 6.17): the number of particles and the dlesm_drifters handle that
-  !! owns their positions and statuses (dlesm_psy_mod: drifters_create, drifters_get, drifters_free, drifter_step)
+  !! owns their positions and statuses (dlesm_psy_mod: drifters_create, drifters_get, drifters_free, drifter_step,
+  !! particle_sort, particle_origin)
   type :: drifters_type
      integer(c_long_long) :: n = 0
      type(c_ptr) :: handle = c_null_ptr
@@ -1009,6 +1010,50 @@ module dlesm_hip_mod
      function dlesm_drifters_destroy(set) bind(C, name="dlesm_drifters_destroy") result(rc)
        import :: c_int, c_ptr
        type(c_ptr), value :: set
+       integer(c_int) :: rc
+     end function
+     ! ---- particles in cell order (DESIGN.md section 6.18): perm = the stable ascending order of the particles' cell keys,
+     !      the live ones in front (nlive: one int on the device, c_null_ptr = not wanted); the gather dst = src(perm) of 1..8
+     !      arrays of 4- or 8-byte elements; both for the owner, which keeps origin; origin and nlive on the host after waiting
+     function dlesm_particle_order_scratch(n, bytes) bind(C, name="dlesm_particle_order_scratch") result(rc)
+       import :: c_int, c_long_long
+       integer(c_long_long), value :: n
+       integer(c_long_long), intent(out) :: bytes
+       integer(c_int) :: rc
+     end function
+     function dlesm_particle_order_f64(xstart, xstop, ystart, ystop, n, px, py, status, perm, nlive, scratch, scratch_bytes, &
+          stream) bind(C, name="dlesm_particle_order_f64") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       integer(c_int), value :: xstart, xstop, ystart, ystop
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: px, py, status, perm, nlive, scratch
+       integer(c_long_long), value :: scratch_bytes
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_particle_permute(n, perm, narrays, src, dst, elem_bytes, &
+          stream) bind(C, name="dlesm_particle_permute") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: perm
+       integer(c_int), value :: narrays
+       type(c_ptr), intent(in) :: src(*), dst(*)
+       integer(c_int), intent(in) :: elem_bytes(*)
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_particle_sort_set(set, xstart, xstop, ystart, ystop, &
+          stream) bind(C, name="dlesm_particle_sort_set") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: set
+       integer(c_int), value :: xstart, xstop, ystart, ystop
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_particle_set_origin(set, origin, nlive) bind(C, name="dlesm_particle_set_origin") result(rc)
+       import :: c_int, c_ptr, c_long_long
+       type(c_ptr), value :: set, origin
+       integer(c_long_long), intent(out) :: nlive
        integer(c_int) :: rc
      end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)

@@ -62,6 +62,7 @@ module dlesm_psy_mod
   public :: flow_courant, flow_courant_type
   public :: flow_output
   public :: drifters_type, drifters_create, drifters_get, drifters_free, drifter_step
+  public :: particle_sort, particle_origin
   public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
@@ -1025,6 +1026,47 @@ contains
     end associate
     if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
   end subroutine drifter_step
+
+  !> Bring the set into cell order (dlesm_particle_sort_set, DESIGN.md section 6.18): the particles that are ACTIVE and inside
+  !! the T internal region of un's grid -- the box drifter_step uses -- come first, in the row-major order of their cells and,
+  !! within a cell, in their old order; every other particle follows in its old order.  drifter_step then reads the flow
+  !! nearly in order.  Asynchronous on the default stream; the first call on a set allocates its second buffers.
+  subroutine particle_sort(set, un)
+    type(drifters_type), intent(inout) :: set
+    type(r2d_field), intent(in) :: un
+    type(c_region) :: sub, box, whole
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('particle_sort: the set has not been created')
+    associate (g => un%grid)
+      associate (s => g%subdomain%internal)
+        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+      end associate
+      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
+                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
+    end associate
+    if (rc /= 0) call gocean_stop('particle_sort: ' // dlesm_error_text())
+    rc = dlesm_particle_sort_set(set%handle, box%xstart, box%xstop, box%ystart, box%ystop, c_null_ptr)
+    if (rc /= 0) call gocean_stop('particle_sort: ' // dlesm_error_text())
+  end subroutine particle_sort
+
+  !> Where the set's particles came from, after waiting for the device: origin(k) is the index (1-based), in the arrays
+  !! drifters_create was given, of the particle that drifters_get now returns in slot k; nlive is the number of particles the
+  !! last particle_sort put in front (-1 before the first sort).
+  subroutine particle_origin(set, origin, nlive)
+    type(drifters_type), intent(in) :: set
+    integer, intent(out) :: origin(:)
+    integer, intent(out) :: nlive
+    integer(c_int), allocatable, target :: o(:)
+    integer(c_long_long) :: live
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('particle_origin: the set has not been created')
+    if (size(origin) /= set%n) call gocean_stop('particle_origin: origin holds one element per particle')
+    allocate(o(set%n))
+    rc = dlesm_particle_set_origin(set%handle, c_loc(o), live)
+    if (rc /= 0) call gocean_stop('particle_origin: ' // dlesm_error_text())
+    origin = int(o) + 1
+    nlive = int(live)
+  end subroutine particle_origin
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

@@ -670,6 +670,80 @@ def drifter_sample(px, py, status, fields, out=None, stream=None):
     return out
 
 
+def _on(stream):
+    import torch
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
+
+def particle_order(px, py, status, grid, perm=None, stream=None):
+    """the particles' cell order (dlesm_particle_order_f64): perm, a contiguous int32 CUDA tensor of
+    one element per particle (made when None), becomes the stable ascending order of the keys
+    (floor(py) - ystart) * nxb + (floor(px) - xstart) of the DRIFTER_ACTIVE particles inside the T internal region of `grid`
+    -- the box drifter_step uses -- with every other particle behind them in its old order.  Returns (perm, nlive), nlive a
+    one-element int32 CUDA tensor: the number of particles in front.  Asynchronous, no synchronisation; the scratch is a
+    tensor of the caching allocator made on `stream`."""
+    import torch
+    who = "particle_order"
+    n = _drifter_arrays(who, px, py, status)
+    it = field_bounds(grid, GO_T_POINTS)[0]
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_particle_order_scratch(n, C.byref(need)))
+    with _on(stream):
+        if perm is None:
+            perm = torch.empty(n, dtype=torch.int32, device=px.device)
+        nlive = torch.empty(1, dtype=torch.int32, device=px.device)
+        scratch = torch.empty(max(need.value, 16), dtype=torch.uint8, device=px.device)
+        if not (perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32 and perm.numel() == n):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: perm is a contiguous int32 CUDA tensor of n elements" % who)
+        check(_cabi.lib().dlesm_particle_order_f64(
+            it.xstart, it.xstop, it.ystart, it.ystop, n, C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()),
+            C.c_void_p(status.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_void_p(nlive.data_ptr()),
+            C.c_void_p(scratch.data_ptr()), need.value, _stream_ptr(stream)))
+    return perm, nlive
+
+
+def particle_permute(perm, arrays, out=None, stream=None):
+    """out[a][k] = arrays[a][perm[k]] (dlesm_particle_permute) for any number of contiguous CUDA
+    tensors of n elements of 4 or 8 bytes, eight to a launch; an index outside 0..n-1 leaves its slot as it was.  out: a
+    list of tensors like `arrays`, or None for new ones.  Returns the list.  Asynchronous."""
+    import torch
+    who = "particle_permute"
+    arrays = list(arrays)
+    n = perm.numel()
+    if not (perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: perm is a contiguous int32 CUDA tensor" % who)
+    if any(not (a.is_cuda and a.is_contiguous() and a.numel() == n and a.element_size() in (4, 8)) for a in arrays):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: contiguous CUDA tensors of n elements of 4 or 8 bytes" % who)
+    if out is None:
+        with _on(stream):
+            out = [torch.empty_like(a) for a in arrays]
+    out = list(out)
+    if len(out) != len(arrays) or any(not (o.is_cuda and o.is_contiguous() and o.numel() == n and o.dtype == a.dtype)
+                                      for o, a in zip(out, arrays)):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: out holds one tensor like each of arrays" % who)
+    for first in range(0, len(arrays), 8):
+        src, dst = arrays[first:first + 8], out[first:first + 8]
+        k = len(src)
+        check(_cabi.lib().dlesm_particle_permute(
+            n, C.c_void_p(perm.data_ptr()), k, (C.c_void_p * k)(*[a.data_ptr() for a in src]),
+            (C.c_void_p * k)(*[o.data_ptr() for o in dst]), (C.c_int * k)(*[a.element_size() for a in src]),
+            _stream_ptr(stream)))
+    return out
+
+
+def particle_sort(px, py, status, un, carry=(), stream=None):
+    """bring the particles into cell order in place: particle_order over the T internal region of
+    un.grid, then px, py, status and every tensor of `carry` (contiguous CUDA tensors of one 4- or 8-byte element per
+    particle: ages, identities, samples) gathered through the permutation and copied back.  Returns (perm, nlive); the live
+    particles are the first nlive, so later steps may pass px[:k], py[:k], status[:k] for any k >= nlive.  Asynchronous."""
+    arrays = [px, py, status] + list(carry)
+    perm, nlive = particle_order(px, py, status, un.grid, stream=stream)
+    with _on(stream):
+        for a, b in zip(arrays, particle_permute(perm, arrays, stream=stream)):
+            a.copy_(b)
+    return perm, nlive
+
+
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
 
 

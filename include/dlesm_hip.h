@@ -1253,6 +1253,43 @@ int dlesm_drifters_get(dlesm_drifters *set, double *px, double *py, int *status)
 int dlesm_drifters_arrays(dlesm_drifters *set, long long *n, double **px, double **py, int **status);
 int dlesm_drifters_destroy(dlesm_drifters *set);
 
+/* Particles in cell order: section 6.17's step is a gather, and particles that lie in memory in the
+ * row-major order of their cells step several times faster than particles in random order.  With the box xstart..xstop x
+ * ystart..ystop, nxb = xstop - xstart + 1, nyb = ystop - ystart + 1, ncells = nxb * nyb (an empty box: 0) and section 6.17's
+ * inbox, evaluated in double before any conversion (a NaN or an infinity is never cast):
+ *     live(p) = status[p] == DLESM_DRIFTER_ACTIVE && inbox(px[p], py[p])
+ *     key(p)  = live(p) ? (floor(py[p]) - ystart) * nxb + (floor(px[p]) - xstart) : ncells            (unsigned 32-bit)
+ * dlesm_particle_order_f64 writes perm[0..n), the STABLE ascending order of the keys -- key(perm[k]) does not decrease with k
+ * and equal keys keep ascending p, so perm is unique -- and, where nlive is not NULL, one int on the device: the number of
+ * live particles, which occupy the slots 0..nlive-1.  The dead (LEFT, OPEN, GROUNDED, any other status, outside the box)
+ * follow in their old order, so later steps may pass n = nlive.  No mask and no flow array is read.  ncells == 0 gives the
+ * identity and nlive = 0; n == 0 writes nlive = 0 and nothing else.  A least-significant-digit radix sort on 8-bit digits,
+ * ceil(bit_length(ncells) / 8) passes (a 200 x 200 box: two), hand-written kernels, no global atomics.  scratch: device
+ * memory, 16-byte aligned, of at least the bytes dlesm_particle_order_scratch gives for n (it needs no device); nothing is
+ * written outside perm, nlive and those bytes.  Asynchronous on `stream`, no host synchronisation, no allocation: it may be
+ * captured into a graph.
+ * dlesm_particle_permute: dst[a][k] = src[a][perm[k]] for k < n and each of narrays (1..8) arrays of elem_bytes[a] (4 or 8)
+ * bytes an element, in one launch that reads perm once.  An index outside 0..n-1 leaves that slot of every dst as it was: a
+ * bad perm cannot fault.  src, dst and elem_bytes are HOST arrays, passed to the kernel by value.  Asynchronous, capturable.
+ * DLESM_EINVAL before anything is launched: a null pointer (nlive may be NULL), n < 0 or n > 2^31-1, xstop < xstart - 1,
+ * ystop < ystart - 1, ncells > 2^32-2, scratch_bytes too small, px or py not 8-byte aligned, status, perm or nlive not
+ * 4-byte aligned, scratch not 16-byte aligned, a src or dst not aligned to its element, perm, nlive or scratch overlapping
+ * each other or px, py or status, a dst overlapping perm, a src or another dst, narrays outside 1..8, an elem_bytes other
+ * than 4 or 8.  DLESM_ENODEV without a device.
+ * dlesm_particle_sort_set orders the owner's px, py and status and an int array origin: origin[k] is the index, at the last
+ * dlesm_drifters_put, of the particle now in slot k (put resets it to the identity).  The pointers dlesm_drifters_arrays
+ * gave stay valid and hold the sorted set.  Asynchronous on `stream`, but the first call on a set allocates its second
+ * buffers and scratch (dlesm_drifters_destroy frees them), so capture only later calls.  dlesm_particle_set_origin: device
+ * -> host after waiting for the device; origin (n ints) or nlive may be NULL; before the first sort since a put origin is the
+ * identity and *nlive = -1 (not known). */
+int dlesm_particle_order_scratch(long long n, long long *bytes);
+int dlesm_particle_order_f64(int xstart, int xstop, int ystart, int ystop, long long n, const double *px, const double *py,
+                             const int *status, int *perm, int *nlive, void *scratch, long long scratch_bytes, void *stream);
+int dlesm_particle_permute(long long n, const int *perm, int narrays, const void *const *src, void *const *dst,
+                           const int *elem_bytes, void *stream);
+int dlesm_particle_sort_set(dlesm_drifters *set, int xstart, int xstop, int ystart, int ystop, void *stream);
+int dlesm_particle_set_origin(dlesm_drifters *set, int *origin, long long *nlive);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
