@@ -25,3 +25,4 @@ from .field_mod import (r2d_field, field_checksum, field_stats, field_locate, co
 from . import psy  # noqa: E402,F401
 from .psy import flow_output, drifter_step, drifter_sample  # noqa: E402,F401
 from .psy import particle_order, particle_permute, particle_sort  # noqa: E402,F401
+from .psy import cell_bin  # noqa: E402,F401

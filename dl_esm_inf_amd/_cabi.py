@@ -307,6 +307,10 @@ PROTOTYPES = {
     "dlesm_particle_permute": (_i, [C.c_longlong, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _vp]),
     "dlesm_particle_sort_set": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "dlesm_particle_set_origin": (_i, [_vp, _vp, C.POINTER(C.c_longlong)]),
+    "dlesm_cell_bin_scratch": (_i, [C.c_longlong, _i, C.POINTER(C.c_longlong)]),
+    "dlesm_cell_bin_f64": (_i, [_i, _d, _i, _i, _i, _i, _i, _i, C.c_longlong] + [_vp] * 4 +
+                           [_i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.c_longlong, _vp]),
+    "dlesm_cell_bin_set": (_i, [_vp, _i, _d] + [_i] * 6 + [_vp, _vp]),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

@@ -271,6 +271,7 @@ extern "C" int dlesm_drifters_destroy(dlesm_drifters *set)
     set->magic = 0;
     if (set->px) (void)hipFree(set->px);
     if (set->sort_mem) (void)hipFree(set->sort_mem);
+    if (set->bin_mem) (void)hipFree(set->bin_mem);
     delete set;
     return DLESM_OK;
 }

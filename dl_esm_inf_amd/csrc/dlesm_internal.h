@@ -19,7 +19,8 @@ struct dlesm_obc {
     int *dev;         // one allocation: t[nt] | uf[nu] ui[nu] uo[nu] | vf[nv] vi[nv] vo[nv]; NULL when all lists are empty
 };
 
-// the owner of the particle arrays (dlesm_drifter.hip makes it; dlesm_particle_sort.hip orders it)
+// the owner of the particle arrays (dlesm_drifter.hip makes it; dlesm_particle_sort.hip orders it, DESIGN.md section 6.18;
+// dlesm_cell_bin.hip counts it by cell, section 6.19)
 struct dlesm_drifters {
     uint64_t magic;
     long long n;
@@ -31,6 +32,8 @@ struct dlesm_drifters {
     void *scratch;
     long long scratch_bytes;
     bool sorted;               // origin and nlive are those of a sort since the last put
+    // made by the first dlesm_cell_bin_set: one allocation, perm | the order's scratch | the bin's
+    void *bin_mem;
 };
 static const uint64_t DLESM_DRIFTERS_MAGIC = 0x444c45534d445246ULL; // "DLESMDRF"
 

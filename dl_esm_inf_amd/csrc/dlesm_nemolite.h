@@ -189,6 +189,32 @@ struct DrifterBox {
     double x_lo, x_hi, y_lo, y_hi;            // xstart, xstop + 1, ystart, ystop + 1
     __host__ __device__ bool has(double x, double y) const { return x >= x_lo && x < x_hi && y >= y_lo && y < y_hi; }
 };
+// The key of a particle (dlesm_particle_sort.hip orders by it, dlesm_cell_bin.hip bins by it): the
+// row-major number of its cell in the box while it is live -- ACTIVE and in the box --, ncells when it is not.  cell() is
+// for a live particle alone: the cast stands behind inbox.
+struct CellKey {
+    DrifterBox box;
+    unsigned xstart, ystart, nxb, ncells;
+    __device__ __forceinline__ bool live(double x, double y, int status) const
+    {
+        return status == DLESM_DRIFTER_ACTIVE && box.has(x, y);
+    }
+    __device__ __forceinline__ unsigned cell(double x, double y) const
+    {
+        return ((unsigned)(int)floor(y) - ystart) * nxb + ((unsigned)(int)floor(x) - xstart);
+    }
+    __device__ __forceinline__ unsigned of(double x, double y, int status) const
+    {
+        unsigned key = ncells;
+        if (live(x, y, status)) key = cell(x, y);
+        return key;
+    }
+};
+inline CellKey cell_key(int xstart, int xstop, int ystart, int ystop, long long ncells)
+{
+    return CellKey{DrifterBox{(double)xstart, (double)xstop + 1.0, (double)ystart, (double)ystop + 1.0}, (unsigned)xstart,
+                   (unsigned)ystart, (unsigned)((long long)xstop - xstart + 1), (unsigned)ncells};
+}
 // what one velocity evaluation reads of cell (i, j): the four neighbour masks, the four faces, the two metrics
 struct DrifterCell {
     int t_e, t_w, t_n, t_s;

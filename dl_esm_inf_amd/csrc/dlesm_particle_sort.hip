@@ -79,8 +79,8 @@ struct KeyArgs {
     const int *status;
     unsigned *keys, *table, *live_part;
     long long n;
-    DrifterBox box;
-    unsigned xstart, ystart, nxb, ncells, nblocks;
+    CellKey cell;
+    unsigned nblocks;
 };
 
 SORT_KERNEL sort_key_k(const KeyArgs a)
@@ -95,12 +95,12 @@ SORT_KERNEL sort_key_k(const KeyArgs a)
     for (int c = 0; c < SORT_TILE / SORT_BLOCK && first + c * SORT_BLOCK < a.n; c++) {
         const long long p = first + c * SORT_BLOCK + t;
         const bool valid = p < a.n;
-        unsigned key = a.ncells;
+        unsigned key = a.cell.ncells;
         bool live = false;
         if (valid) {
             const double x = a.px[p], y = a.py[p];
-            live = a.status[p] == DLESM_DRIFTER_ACTIVE && a.box.has(x, y);
-            if (live) key = ((unsigned)(int)floor(y) - a.ystart) * a.nxb + ((unsigned)(int)floor(x) - a.xstart);
+            live = a.cell.live(x, y, a.status[p]);
+            if (live) key = a.cell.cell(x, y);
             a.keys[p] = key;
         }
         live_here += (unsigned)__popcll(__ballot(live));
@@ -375,10 +375,7 @@ int launch_order(int xstart, int xstop, int ystart, int ystop, long long n, long
     const dim3 grid(plan.nblocks);
     const int passes = (bit_length((unsigned long long)ncells) + 7) / 8;       // 1..4: the dead key is ncells itself
 
-    const KeyArgs ka{px, py, status, keys[0], table, live, n,
-                     DrifterBox{(double)xstart, (double)xstop + 1.0, (double)ystart, (double)ystop + 1.0},
-                     (unsigned)xstart, (unsigned)ystart, (unsigned)((long long)xstop - xstart + 1), (unsigned)ncells,
-                     plan.nblocks};
+    const KeyArgs ka{px, py, status, keys[0], table, live, n, cell_key(xstart, xstop, ystart, ystop, ncells), plan.nblocks};
     hipLaunchKernelGGL(sort_key_k, grid, block, 0, s, ka);
     if (nlive) hipLaunchKernelGGL(sort_nlive_k, dim3(1), block, 0, s, (const unsigned *)live, plan.nblocks, nlive);
     for (int pass = 0; pass < passes; pass++) {

@@ -81,7 +81,7 @@ module dlesm_hip_mod
 
   !> A set of drifters on the device (DESIGN.md section 6.17): the number of particles and the dlesm_drifters handle that
   !! owns their positions and statuses (dlesm_psy_mod: drifters_create, drifters_get, drifters_free, drifter_step,
-  !! particle_sort, particle_origin)
+  !! particle_sort, particle_origin, cell_bin)
   type :: drifters_type
      integer(c_long_long) :: n = 0
      type(c_ptr) :: handle = c_null_ptr
@@ -1054,6 +1054,42 @@ module dlesm_hip_mod
        import :: c_int, c_ptr, c_long_long
        type(c_ptr), value :: set, origin
        integer(c_long_long), intent(out) :: nlive
+       integer(c_int) :: rc
+     end function
+     ! ---- particles binned by cell (DESIGN.md section 6.19): per-cell sums of 1..8 per-particle weights (c_null_ptr: the
+     !      count) over a permutation in key order (perm = c_null_ptr: the identity) into T-point arrays, mode 0 stores
+     !      alpha * sum in every cell of the box, mode 1 adds it where a live particle is; unordered: one int on the device
+     !      (c_null_ptr = not wanted); and the count for the owner
+     function dlesm_cell_bin_scratch(n, narrays, bytes) bind(C, name="dlesm_cell_bin_scratch") result(rc)
+       import :: c_int, c_long_long
+       integer(c_long_long), value :: n
+       integer(c_int), value :: narrays
+       integer(c_long_long), intent(out) :: bytes
+       integer(c_int) :: rc
+     end function
+     function dlesm_cell_bin_f64(mode, alpha, ld, ny, xstart, xstop, ystart, ystop, n, px, py, status, perm, narrays, &
+          weights, out, unordered, scratch, scratch_bytes, stream) bind(C, name="dlesm_cell_bin_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       integer(c_int), value :: mode
+       real(c_double), value :: alpha
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: px, py, status, perm
+       integer(c_int), value :: narrays
+       type(c_ptr), intent(in) :: weights(*), out(*)
+       type(c_ptr), value :: unordered, scratch
+       integer(c_long_long), value :: scratch_bytes
+       type(c_ptr), value :: stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_cell_bin_set(set, mode, alpha, ld, ny, xstart, xstop, ystart, ystop, count, &
+          stream) bind(C, name="dlesm_cell_bin_set") result(rc)
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: set
+       integer(c_int), value :: mode
+       real(c_double), value :: alpha
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: count, stream
        integer(c_int) :: rc
      end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)

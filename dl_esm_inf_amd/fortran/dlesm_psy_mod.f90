@@ -63,6 +63,7 @@ module dlesm_psy_mod
   public :: flow_output
   public :: drifters_type, drifters_create, drifters_get, drifters_free, drifter_step
   public :: particle_sort, particle_origin
+  public :: cell_bin
   public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
@@ -1067,6 +1068,30 @@ contains
     origin = int(o) + 1
     nlive = int(live)
   end subroutine particle_origin
+
+  !> The set's particles per cell (dlesm_cell_bin_set, DESIGN.md section 6.19) into the T-point field cnt, over its internal
+  !! region -- the box drifter_step and particle_sort use: the particles that are ACTIVE and inside it are counted, exactly.
+  !! mode 0 (the default) stores alpha * count in every cell of the region, mode 1 adds alpha * count to the cells that hold
+  !! a particle (alpha = dt into a zeroed field: an exposure); alpha defaults to 1.  The particles are not moved.
+  !! Asynchronous on the default stream; the first call on a set allocates its buffers.
+  subroutine cell_bin(set, cnt, mode, alpha)
+    type(drifters_type), intent(inout) :: set
+    type(r2d_field), intent(inout), target :: cnt
+    integer, optional, intent(in) :: mode
+    real(go_wp), optional, intent(in) :: alpha
+    integer(c_int) :: rc, m
+    real(c_double) :: a
+    if (.not. c_associated(set%handle)) call gocean_stop('cell_bin: the set has not been created')
+    if (cnt%defined_on /= GO_T_POINTS) call gocean_stop('cell_bin: cnt is a field at T points')
+    m = 0_c_int;  a = 1.0_c_double
+    if (present(mode)) m = int(mode, c_int)
+    if (present(alpha)) a = real(alpha, c_double)
+    call need_device(cnt)
+    rc = dlesm_cell_bin_set(set%handle, m, a, int(cnt%grid%nx, c_int), int(cnt%grid%ny, c_int), &
+                            int(cnt%internal%xstart, c_int), int(cnt%internal%xstop, c_int), &
+                            int(cnt%internal%ystart, c_int), int(cnt%internal%ystop, c_int), field_device_data(cnt), c_null_ptr)
+    if (rc /= 0) call gocean_stop('cell_bin: ' // dlesm_error_text())
+  end subroutine cell_bin
 
   ! the call the six tracer wrappers make (dm: the distributed entry with `plan`; scheme: 0 the upwind entries, 1 the limited
   ! scheme's, 2 the time-centred limited scheme's)

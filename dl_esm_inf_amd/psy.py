@@ -744,6 +744,50 @@ def particle_sort(px, py, status, un, carry=(), stream=None):
     return perm, nlive
 
 
+def cell_bin(px, py, status, grid, weights=(None,), out=None, perm=None, mode=_cabi.OUT_SET, alpha=1.0, stream=None):
+    """the particles binned by cell (dlesm_cell_bin_f64): one output per entry of `weights`, the
+    per-cell sum of that contiguous float64 CUDA tensor of one weight per particle -- None: 1.0, the cell's count, exact --
+    over the DRIFTER_ACTIVE particles inside the T internal region of `grid`, the box particle_order uses, in the fixed
+    order of section 6.19.  out: a list of contiguous float64 CUDA tensors of grid.ny x grid.nx, or None for new ones filled
+    with zeros.  mode = OUT_SET stores alpha * sum in every cell of the region, OUT_ADD adds alpha * sum to the cells that
+    hold a live particle.  perm: the particles' order by particle_order for the same grid (computed here when None).  Returns
+    (out, unordered), unordered a one-element int32 CUDA tensor: 1 when perm was not in key order and the result is not
+    defined.  Asynchronous, no synchronisation; the scratch is a tensor of the caching allocator made on `stream`."""
+    import torch
+    who = "cell_bin"
+    n = _drifter_arrays(who, px, py, status)
+    weights = list(weights)
+    if not 1 <= len(weights) <= 8:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: 1 to 8 weights" % who)
+    if any(w is not None and not (w.is_cuda and w.is_contiguous() and w.dtype == torch.float64 and w.numel() == n)
+           for w in weights):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: a weight is None or a contiguous float64 CUDA tensor of n elements" % who)
+    k = len(weights)
+    it = field_bounds(grid, GO_T_POINTS)[0]
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_cell_bin_scratch(n, k, C.byref(need)))
+    if perm is None:
+        perm = particle_order(px, py, status, grid, stream=stream)[0]
+    if not (perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32 and perm.numel() == n):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: perm is a contiguous int32 CUDA tensor of n elements" % who)
+    with _on(stream):
+        if out is None:
+            out = [torch.zeros((grid.ny, grid.nx), dtype=torch.float64, device=px.device) for _ in weights]
+        out = list(out)
+        if len(out) != k or any(not (o.is_cuda and o.is_contiguous() and o.dtype == torch.float64 and
+                                     o.numel() == grid.nx * grid.ny) for o in out):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: out holds one contiguous float64 CUDA tensor of ny x nx per weight" % who)
+        unordered = torch.empty(1, dtype=torch.int32, device=px.device)
+        scratch = torch.empty(max(need.value, 16), dtype=torch.uint8, device=px.device)
+        check(_cabi.lib().dlesm_cell_bin_f64(
+            int(mode), float(alpha), grid.nx, grid.ny, it.xstart, it.xstop, it.ystart, it.ystop, n, C.c_void_p(px.data_ptr()),
+            C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(perm.data_ptr()), k,
+            (C.c_void_p * k)(*[w.data_ptr() if w is not None else None for w in weights]),
+            (C.c_void_p * k)(*[o.data_ptr() for o in out]), C.c_void_p(unordered.data_ptr()), C.c_void_p(scratch.data_ptr()),
+            need.value, _stream_ptr(stream)))
+    return out, unordered
+
+
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
 
 

@@ -1290,6 +1290,47 @@ int dlesm_particle_permute(long long n, const int *perm, int narrays, const void
 int dlesm_particle_sort_set(dlesm_drifters *set, int xstart, int xstop, int ystart, int ystop, void *stream);
 int dlesm_particle_set_origin(dlesm_drifters *set, int *origin, long long *nlive);
 
+/* Particles binned by cell: the Eulerian product of a particle set -- particles or mass per cell, a
+ * time-integrated exposure -- as T-point fields, without atomics and with bits that can be pinned.  The box, inbox, live(p)
+ * and key(p) are section 6.18's.  perm is a permutation in key order, as dlesm_particle_order_f64 gives for the same box and
+ * arrays; perm == NULL is the identity, for arrays already sorted in place.  Slot k holds particle p = perm[k].  In key
+ * order the particles of a live cell c are one run of slots.  For each of narrays (1..8) outputs, with w(p) = weights[a][p],
+ * or 1.0 where weights[a] is NULL (the cell's count, exact as a double), the sum S_a(c) over the run has a fixed order:
+ *     the chunks are the aligned groups of 64 consecutive slots, g = k >> 6;
+ *     P_a(c, g) = the run's slots of chunk g added one by one in ascending k, beginning with the first of them (not with 0.0);
+ *     S_a(c)    = the partials P_a(c, g) added one by one in ascending g, beginning with the first;
+ * every addition rounded in double, nothing contracted.  A cell without live particle has S = +0.0.  The bits depend on the
+ * inputs and on perm alone, not on the launch shape, the stream or the run.
+ *     DLESM_OUT_SET: EVERY cell of the box gets out[a](c) = alpha * S_a(c), one rounding.
+ *     DLESM_OUT_ADD: the cells with at least one live particle get out[a](c) = out[a](c) + alpha * S_a(c), two roundings
+ *                    (alpha = dt or 1/nsteps into zeroed fields: an exposure, a time mean); every other cell keeps its bits.
+ * Nothing outside the box is ever written.  The dead (key ncells) lie behind the live and add nothing.  A slot whose index is
+ * outside 0..n-1 counts as dead.  unordered, where not NULL, is one int on the device: it ends as 1 if the key of some slot is
+ * below that of the slot before it or an index was out of range, else as 0; equal keys being contiguous exactly when the keys
+ * do not decrease, 0 means "the result is the one defined here".  With 1 the values inside the box are unspecified, and still
+ * nothing but the box, the flag and the stated scratch bytes is written and no load leaves [0, n): a stale perm cannot
+ * fault.  No mask and no flow array is read.
+ * out[a]: device memory, ny x ld doubles, cell (i, j) at (size_t)(j-1)*ld + (i-1).  weights and out are HOST arrays of narrays
+ * device pointers, passed to the kernels by value; px, py, status, perm and every weights[a] have n elements.  scratch: device
+ * memory, 16-byte aligned, of at least the bytes dlesm_cell_bin_scratch gives for n and narrays (it needs no device).
+ * Asynchronous on `stream`, no host synchronisation, no allocation, no global atomics: it may be captured into a graph.  n == 0
+ * with DLESM_OUT_SET still fills the box; n == 0 or an empty box with DLESM_OUT_ADD touches no out.
+ * DLESM_EINVAL before anything is launched: a null pointer other than perm, unordered and single weights[a], a mode other
+ * than the two, a non-finite alpha, n < 0 or n > 2^31-1, narrays outside 1..8, xstop < xstart - 1, ystop < ystart - 1, a box
+ * that does not fit in ld x ny, ncells > 2^32-2, a double array not 8-byte aligned, an int array not 4-byte aligned, scratch
+ * not 16-byte aligned, scratch_bytes too small, an out[a], unordered or scratch overlapping each other or an input.
+ * DLESM_ENODEV without a device.
+ * dlesm_cell_bin_set, for callers without device arrays: the count of the owner's particles (weights NULL) into `count`.  The
+ * order is computed into buffers of the owner and the particles are not moved.  Asynchronous on `stream`, but the first call
+ * on a set allocates those buffers (dlesm_drifters_destroy frees them), so capture only later calls. */
+int dlesm_cell_bin_scratch(long long n, int narrays, long long *bytes);
+int dlesm_cell_bin_f64(int mode, double alpha, int ld, int ny, int xstart, int xstop, int ystart, int ystop, long long n,
+                       const double *px, const double *py, const int *status, const int *perm, int narrays,
+                       const double *const *weights, double *const *out, int *unordered, void *scratch,
+                       long long scratch_bytes, void *stream);
+int dlesm_cell_bin_set(dlesm_drifters *set, int mode, double alpha, int ld, int ny, int xstart, int xstop, int ystart,
+                       int ystop, double *count, void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this

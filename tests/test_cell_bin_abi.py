@@ -1,0 +1,158 @@
+"""CPU tests of the boundary of the cell bin: the three entries are exported from the product and
+from the lab build and stand in the header, the ctypes table, INTEGRATION.md and dlesm_hip_mod with one argument list each;
+none of their names contains `particle` or `drifter` (tests/test_particle_order_abi.py and tests/test_drifter_abi.py pin those
+sets); dlesm_version() is unchanged; the Python and Fortran names are public; the scratch query is host arithmetic and grows
+with n and narrays; without a GPU the entries fail loudly and write nothing, and with one every refusal is DLESM_EINVAL with
+nothing written."""
+import ctypes as C
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from conftest import ROOT
+
+import dl_esm_inf_amd as D
+from dl_esm_inf_amd import _cabi
+
+L = _cabi.lib()
+_i, _d, _vp, _ll = C.c_int, C.c_double, C.c_void_p, C.c_longlong
+ENTRIES = {
+    "dlesm_cell_bin_scratch": (["long long n", "int narrays", "long long *bytes"], [_ll, _i, C.POINTER(_ll)]),
+    "dlesm_cell_bin_f64": (
+        ["int mode", "double alpha", "int ld", "int ny", "int xstart", "int xstop", "int ystart", "int ystop", "long long n",
+         "const double *px", "const double *py", "const int *status", "const int *perm", "int narrays",
+         "const double *const *weights", "double *const *out", "int *unordered", "void *scratch", "long long scratch_bytes",
+         "void *stream"],
+        [_i, _d] + [_i] * 6 + [_ll] + [_vp] * 4 + [_i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _ll, _vp]),
+    "dlesm_cell_bin_set": (
+        ["dlesm_drifters *set", "int mode", "double alpha", "int ld", "int ny", "int xstart", "int xstop", "int ystart",
+         "int ystop", "double *count", "void *stream"],
+        [_vp, _i, _d] + [_i] * 6 + [_vp, _vp]),
+}
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dlesm_hip.h")).read(), flags=re.S)
+
+
+def _names(args):
+    return [a.split()[-1].lstrip("*") for a in args]
+
+
+def test_header_exports_ctypes_and_documents_agree():
+    txt = _header()
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    fortran = open(os.path.join(ROOT, "dl_esm_inf_amd", "fortran", "dlesm_hip_mod.f90")).read()
+    exported = []
+    for lib in [_cabi.LIB_PATH, os.path.join(os.path.dirname(_cabi.LIB_PATH), "libdlesm_hip_lab.so")]:
+        out = subprocess.check_output(["nm", "-D", "--defined-only", lib], text=True)
+        exported.append({l.split()[-1] for l in out.splitlines() if " T " in l})
+    for entry, (args, ctypes_args) in ENTRIES.items():
+        assert entry in exported[0] and entry in exported[1], entry
+        assert "drifter" not in entry and "particle" not in entry
+        m = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % entry, txt)
+        assert m and [" ".join(a.split()) for a in m.group(1).split(",")] == args, entry
+        res, got = _cabi.PROTOTYPES[entry]
+        assert res is C.c_int and list(got) == ctypes_args, entry
+        m = re.search(r"`%s\(([^)]*)\)`" % entry, doc)
+        assert m and [a.strip() for a in m.group(1).replace("\n", " ").split(",")] == _names(args), entry
+        m = re.search(r"function %s\((.*?)\)\s*bind\(C, name=\"%s\"\)" % (entry, entry), fortran, flags=re.S)
+        assert m and [a.strip() for a in m.group(1).replace("&", " ").split(",")] == _names(args), entry
+    assert {e for e in exported[0] if "cell_bin" in e} == set(ENTRIES)
+    for name in ("psy.cell_bin", "call cell_bin(set, cnt, mode, alpha)"):
+        assert name in doc, name
+    raw = open(os.path.join(ROOT, "include", "dlesm_hip.h")).read()
+    assert "section 6.19" in raw
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "### 6.19 Particles binned by cell (frozen here)" in design and all(e in design for e in ENTRIES)
+    assert L.dlesm_version() == 310
+
+
+def test_the_wrappers_are_public():
+    from dl_esm_inf_amd import psy
+    assert D.cell_bin is psy.cell_bin
+    sig = inspect.signature(psy.cell_bin).parameters
+    assert list(sig) == ["px", "py", "status", "grid", "weights", "out", "perm", "mode", "alpha", "stream"]
+    assert sig["weights"].default == (None,) and sig["out"].default is None and sig["perm"].default is None
+    assert sig["mode"].default == _cabi.OUT_SET and sig["alpha"].default == 1.0 and sig["stream"].default is None
+    psy_f = open(os.path.join(ROOT, "dl_esm_inf_amd", "fortran", "dlesm_psy_mod.f90")).read()
+    assert re.search(r"public ::[^\n]*\bcell_bin\b", psy_f)
+    assert re.search(r"subroutine cell_bin\(set, cnt, mode, alpha\)", psy_f)
+    assert re.search(r"integer, optional, intent\(in\) :: mode", psy_f) and "drifter_sample" not in psy_f
+
+
+def test_the_scratch_query_is_host_arithmetic():
+    """it needs no device; the bytes hold the n keys, one key per chunk of 64 slots and two partials per chunk and output, and
+    grow with n and with narrays"""
+    b = _ll(-3)
+    assert L.dlesm_cell_bin_scratch(-1, 1, C.byref(b)) == _cabi.EINVAL and b.value == -3
+    assert L.dlesm_cell_bin_scratch(2 ** 31, 1, C.byref(b)) == _cabi.EINVAL and b.value == -3
+    assert L.dlesm_cell_bin_scratch(1000, 0, C.byref(b)) == _cabi.EINVAL and L.dlesm_cell_bin_scratch(1000, 9, C.byref(b)) == _cabi.EINVAL
+    assert L.dlesm_cell_bin_scratch(1000, 1, None) == _cabi.EINVAL and b.value == -3
+    last = -1
+    for n in [0, 1, 63, 64, 65, 4097, 70001, 2 ** 22, 2 ** 31 - 1]:
+        per, one = -1, -1
+        for k in range(1, 9):
+            assert L.dlesm_cell_bin_scratch(n, k, C.byref(b)) == 0, (n, k)
+            chunks = -(-n // 64)
+            assert b.value >= 4 * n + chunks * (4 + 16 * k) and b.value <= 4 * n + chunks * (4 + 16 * k) + 64, (n, k)
+            assert b.value % 16 == 0 and b.value >= per                    # (one chunk: two partials pad to 16 bytes)
+            per, one = b.value, b.value if k == 1 else one
+        assert per > one or n == 0
+        assert L.dlesm_cell_bin_scratch(n, 1, C.byref(b)) == 0 and b.value >= last         # (63 and 64 keys pad to the same)
+        if n <= 2 ** 22:
+            more = _ll()
+            assert L.dlesm_cell_bin_scratch(n + 64, 1, C.byref(more)) == 0 and more.value > b.value
+        last = b.value
+    assert L.dlesm_cell_bin_scratch(0, 8, C.byref(b)) == 0 and b.value == 0
+
+
+def test_without_a_gpu_the_entries_fail_loudly_and_write_nothing():
+    """DLESM_ENODEV without a device; with one, host arrays of a valid shape pass every check that needs no device and the
+    bad arguments are refused"""
+    n, ld, ny = 8, 12, 10
+    px, py, st = np.full(n, 3.5), np.full(n, 4.5), np.zeros(n, dtype=np.int32)
+    perm, flag = np.arange(n, dtype=np.int32), np.full(1, -7, dtype=np.int32)
+    w = np.full(n, 2.0)
+    outs = [np.full(ld * ny, -7.0) for _ in range(2)]
+    need = _ll()
+    assert L.dlesm_cell_bin_scratch(n, 2, C.byref(need)) == 0
+    scratch = np.full(need.value // 8 + 2, -7.0)
+    base = scratch.ctypes.data + (-scratch.ctypes.data) % 16
+    have_gpu = L.dlesm_device_count() > 0
+    want = _cabi.EINVAL if have_gpu else _cabi.ENODEV
+
+    def bin_(mode=0, alpha=1.0, ld_=ld, ny_=ny, box=(2, 7, 2, 7), n_=n, x=px.ctypes.data, pm=perm.ctypes.data, k=2,
+             wt=(None, w.ctypes.data), o=(outs[0].ctypes.data, outs[1].ctypes.data), fl=flag.ctypes.data, sc=base, nb=need.value):
+        pw = (_vp * 8)(*wt) if wt is not None else None
+        po = (_vp * 8)(*o) if o is not None else None
+        return L.dlesm_cell_bin_f64(mode, alpha, ld_, ny_, *box, n_, x, py.ctypes.data, st.ctypes.data, pm, k, pw, po, fl, sc,
+                                    nb, None)
+
+    assert bin_(x=None) == want
+    if not have_gpu:
+        assert b"no HIP device" in L.dlesm_last_error()
+        assert bin_() == _cabi.ENODEV                                        # a valid call: nothing to run it on
+    assert bin_(wt=None) == want and bin_(o=None) == want and bin_(sc=None) == want
+    assert bin_(o=(outs[0].ctypes.data, None)) == want
+    assert bin_(mode=2) == want and bin_(mode=-1) == want
+    assert bin_(alpha=float("nan")) == want and bin_(alpha=float("inf")) == want
+    assert bin_(n_=-1) == want and bin_(n_=2 ** 31) == want
+    assert bin_(k=0) == want and bin_(k=9) == want
+    assert bin_(box=(2, 0, 2, 7)) == want and bin_(box=(2, 7, 2, 0)) == want
+    assert bin_(box=(0, 7, 2, 7)) == want and bin_(box=(2, ld + 1, 2, 7)) == want and bin_(box=(2, 7, 2, ny + 1)) == want
+    assert bin_(ld_=65536, ny_=65536, box=(1, 65536, 1, 65536)) == want
+    assert bin_(nb=need.value - 1) == want
+    assert bin_(x=px.ctypes.data + 4) == want and bin_(pm=perm.ctypes.data + 2) == want and bin_(sc=base + 8) == want
+    assert bin_(fl=flag.ctypes.data + 2) == want and bin_(o=(outs[0].ctypes.data + 4, outs[1].ctypes.data)) == want
+    assert bin_(wt=(None, w.ctypes.data + 4)) == want
+    assert bin_(o=(outs[0].ctypes.data, outs[0].ctypes.data)) == want and bin_(o=(outs[0].ctypes.data, px.ctypes.data)) == want
+    assert bin_(o=(outs[0].ctypes.data, w.ctypes.data)) == want and bin_(fl=outs[1].ctypes.data) == want
+    assert bin_(fl=perm.ctypes.data) == want and bin_(sc=outs[0].ctypes.data + (-outs[0].ctypes.data) % 16) == want
+    assert bin_(fl=base) == want
+    assert L.dlesm_cell_bin_set(None, 0, 1.0, ld, ny, 2, 7, 2, 7, outs[0].ctypes.data, None) == want
+    assert (px == 3.5).all() and (py == 4.5).all() and (st == 0).all() and (perm == np.arange(n)).all() and (flag == -7).all()
+    assert (scratch == -7.0).all() and (outs[0] == -7.0).all() and (outs[1] == -7.0).all() and (w == 2.0).all()
