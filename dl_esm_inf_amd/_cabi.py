@@ -359,6 +359,8 @@ LAB_BUILD_PATH = os.path.join(HERE, "lib", "libdlesm_hip_lab.so")
 LAB_PROTOTYPES = {
     "dlesm_lab_last_error": (C.c_char_p, []),
     "dlesm_lab_stream_copy_f64": (_i, [_i, _i, C.POINTER(_vp), C.POINTER(_vp), C.c_size_t, _i, _vp]),
+    "dlesm_lab_load_rmw_f64": (_i, [_vp, C.c_size_t, _i, C.c_size_t, _i, _i, _vp]),
+    "dlesm_lab_load_rmw_occupancy": (_i, [_i, C.POINTER(_i)]),
 }
 _lab = None
 

@@ -70,11 +70,57 @@ void launch_stream(const StreamPtrs &p, size_t n2, int nt, hipStream_t s)
     }
 }
 
+// A COMPETING LOAD for the hand-over tests (tests/handover_load.py): `groups` workgroups, each read-modify-writing its own
+// slice of `slice` doubles `iters` times with plain vector loads and stores.  Fixed trip counts, no flag, no wait, no
+// atomic: it cannot fail to end, and no workgroup reads what another one writes.  CLAIM > 0: the workgroup declares that
+// many doubles of LDS (more than half a CU's 160 KiB), so that at most ONE workgroup is resident per CU and a grid just
+// over the CU count leaves a few CUs with a second workgroup queued.
+template <int CLAIM>
+__global__ __launch_bounds__(256) void load_rmw_k(double *buf, size_t slice, int iters)
+{
+    __shared__ double claim[CLAIM > 0 ? CLAIM : 1];
+    double *p = buf + (size_t)blockIdx.x * slice;
+    if (CLAIM > 0) claim[(threadIdx.x * 79u + (unsigned)iters) % (unsigned)CLAIM] = (double)threadIdx.x;   // (keeps the LDS claimed)
+    for (int it = 0; it < iters; it++)
+        for (size_t i = threadIdx.x; i < slice; i += 256) p[i] = p[i] * 0.5 + 1.0;     // (stays finite: the fixed point is 2)
+    if (CLAIM > 0) {
+        __syncthreads();
+        if (claim[(threadIdx.x * 31u + (unsigned)iters) % (unsigned)CLAIM] == -1.0) p[threadIdx.x % slice] = 0.0;
+    }
+}
+
+constexpr int LOAD_CLAIM = 96 * 1024 / 8;      // 96 KiB: ⌊160 / 96⌋ = one workgroup per CU
+
 } // namespace
 
 } // namespace dlesm
 
 using namespace dlesm;
+
+extern "C" int dlesm_lab_load_rmw_occupancy(int one_per_cu, int *workgroups_per_cu)
+{
+    LAB_REQUIRE(workgroups_per_cu != nullptr, "dlesm_lab_load_rmw_occupancy: null pointer");
+    const hipError_t e = one_per_cu ? hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, load_rmw_k<LOAD_CLAIM>, 256, 0)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, load_rmw_k<0>, 256, 0);
+    if (e != hipSuccess) return lab_fail("dlesm_lab_load_rmw_occupancy: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int dlesm_lab_load_rmw_f64(double *buf, size_t n, int groups, size_t slice, int iters, int one_per_cu, void *stream)
+{
+    LAB_REQUIRE(buf != nullptr, "dlesm_lab_load_rmw_f64: null pointer");
+    LAB_REQUIRE(groups >= 1 && groups <= 65536, "dlesm_lab_load_rmw_f64: %d workgroups (1 .. 65536)", groups);
+    LAB_REQUIRE(slice >= 1 && slice <= ((size_t)1 << 24), "dlesm_lab_load_rmw_f64: slice of %zu doubles (1 .. 2^24)", slice);
+    LAB_REQUIRE((size_t)groups * slice <= n, "dlesm_lab_load_rmw_f64: %d slices of %zu doubles do not fit the buffer of %zu",
+                groups, slice, n);
+    LAB_REQUIRE(iters >= 1 && iters <= (1 << 20), "dlesm_lab_load_rmw_f64: %d iterations (1 .. 2^20)", iters);
+    hipStream_t s = (hipStream_t)stream;
+    if (one_per_cu) hipLaunchKernelGGL((load_rmw_k<LOAD_CLAIM>), dim3((unsigned)groups), dim3(256), 0, s, buf, slice, iters);
+    else hipLaunchKernelGGL((load_rmw_k<0>), dim3((unsigned)groups), dim3(256), 0, s, buf, slice, iters);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lab_fail("dlesm_lab_load_rmw_f64: launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
 
 extern "C" const char *dlesm_lab_last_error(void) { return g_lab_err; }
 

@@ -21,6 +21,15 @@ const char *dlesm_lab_last_error(void);
 int dlesm_lab_stream_copy_f64(int nread, int nwrite, const double *const *src, double *const *dst, size_t n, int nt,
                               void *stream);
 
+/* A competing load for the hand-over tests (tests/handover_load.py): `groups` workgroups of 256 threads, each read-modify-
+ * writes its own slice of `slice` doubles of buf (n doubles; groups * slice <= n) `iters` times (1 .. 2^20) with plain
+ * vector loads and stores.  Fixed trip counts, no flags, no waits between workgroups.  one_per_cu != 0: every workgroup
+ * claims 96 KiB of LDS, so a CU holds one of them at a time. */
+int dlesm_lab_load_rmw_f64(double *buf, size_t n, int groups, size_t slice, int iters, int one_per_cu, void *stream);
+
+/* how many workgroups of that kernel one CU holds at a time (the runtime's occupancy figure): 1 with one_per_cu != 0 */
+int dlesm_lab_load_rmw_occupancy(int one_per_cu, int *workgroups_per_cu);
+
 #ifdef __cplusplus
 }
 #endif
