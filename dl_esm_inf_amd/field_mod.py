@@ -30,6 +30,19 @@ def _stream_ptr(stream):
     return C.c_void_p(stream.cuda_stream)
 
 
+def _fetch_record(stream, device, ndoubles, launch):
+    """the host bytes of a record of `ndoubles` doubles that launch(record pointer, stream pointer) has a sweep write on
+    `stream` (None: the current one).  The record is device memory allocated under torch.cuda.stream(stream), so that the
+    caching allocator ties it to the caller's stream, and it comes back by a copy on that stream -- not torch's pinned host
+    memory, which ROCm allocates non-coherent by default: a device store there may reach the host late."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(s):
+        res = torch.empty(ndoubles, dtype=torch.float64, device=device)
+        launch(C.c_void_p(res.data_ptr()), _stream_ptr(s))
+        return res.cpu().numpy().tobytes()                  # (a copy on `s` that the host waits for)
+
+
 def field_bounds(grid, grid_points):
     """set_field_bounds (field_mod.f90:563-624) -> (internal, whole)"""
     internal, whole = Region(), Region()
@@ -128,13 +141,13 @@ class r2d_field:
 
 def field_checksum(field, stream=None):
     """field_checksum (field_mod.f90:1209-1219, 1289-1307): SUM(ABS(internal)) + global_sum"""
+    from . import parallel_mod
     val = C.c_double()
     it = field.internal
     check(_cabi.lib().dlesm_checksum_f64(field.device_ptr, field.grid.nx, field.grid.ny, it.xstart,
                                          it.xstop, it.ystart, it.ystop, C.byref(val),
                                          _stream_ptr(stream)))
-    check(_cabi.lib().dlesm_global_sum_f64(C.byref(val)))
-    return val.value
+    return parallel_mod.global_sum(val.value)
 
 
 def _mask_list(masks, n):
@@ -179,29 +192,17 @@ def field_stats(fields, masks=None, stream=None):
     boxes = (Region * n)()
     for k, f in enumerate(fields):
         C.memmove(C.byref(boxes[k]), C.byref(f.internal), C.sizeof(Region))
-    L = _cabi.lib()
-    s = stream if stream is not None else torch.cuda.current_stream()
-    # the numbers land in device memory allocated on the caller's stream and come back by a copy on it (see
-    # psy.invoke_jacobi5_residual for why torch's pinned host memory is not used)
-    with torch.cuda.stream(s):
-        res = torch.empty(6 * n, dtype=torch.float64, device=fields[0].data.device)
-        check(L.dlesm_field_stats_async_f64(fp, mp if any(m is not None for m in mlist) else None, boxes, n, g.nx, g.ny,
-                                            C.c_void_p(res.data_ptr()), _stream_ptr(s)))
-        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
-    out = (_cabi.FieldStats * n).from_buffer_copy(host.tobytes())
+    host = _fetch_record(stream, fields[0].data.device, 6 * n, lambda res, s: check(_cabi.lib().dlesm_field_stats_async_f64(
+        fp, mp if any(m is not None for m in mlist) else None, boxes, n, g.nx, g.ny, res, s)))
+    out = (_cabi.FieldStats * n).from_buffer_copy(host)
     out = [out[k] for k in range(n)]
-    if parallel_mod.get_num_ranks() > 1:
-        def glob(fn, v):
-            val = C.c_double(v)
-            check(fn(C.byref(val)))
-            return val.value
-        for st in out:                                      # no NaN enters these collectives: see the definition of min .. sumsq
-            st.min = -glob(L.dlesm_global_max_f64, -st.min)
-            st.max = glob(L.dlesm_global_max_f64, st.max)
-            st.sum = glob(L.dlesm_global_sum_f64, st.sum)
-            st.sumsq = glob(L.dlesm_global_sum_f64, st.sumsq)
-            st.count = int(glob(L.dlesm_global_sum_f64, float(st.count)))          # exact below 2**53
-            st.nonfinite = int(glob(L.dlesm_global_sum_f64, float(st.nonfinite)))
+    for st in out:                                          # no NaN enters these collectives: see the definition of min .. sumsq
+        st.min = -parallel_mod.global_max(-st.min)
+        st.max = parallel_mod.global_max(st.max)
+        st.sum = parallel_mod.global_sum(st.sum)
+        st.sumsq = parallel_mod.global_sum(st.sumsq)
+        st.count = parallel_mod._global_count(st.count)
+        st.nonfinite = parallel_mod._global_count(st.nonfinite)
     return out
 
 

@@ -514,6 +514,7 @@ contains
   !! mask: the grid's device tmask mirror (grid%tmask_device once grid_to_device has run); only cells with
   !! tmask > 0 are then counted.
   subroutine field_stats(fld, stats, mask)
+    use rank_collectives_mod, only: rank_max, rank_sum, rank_total
     type(r2d_field), intent(inout), target :: fld
     type(field_stats_type), intent(out) :: stats
     type(c_ptr), intent(in), optional :: mask
@@ -538,22 +539,13 @@ contains
                                res, c_null_ptr)
     if (rc /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
     stats = res(1)
-    ! no NaN enters these collectives: min .. sumsq are over the finite cells; counts are exact as doubles below 2**53
-    v = -stats%min;  call gmax(v);  stats%min = -v
-    call gmax(stats%max)
-    call gsum(stats%sum)
-    call gsum(stats%sumsq)
-    v = real(stats%count, c_double);  call gsum(v);  stats%count = int(v, c_int64_t)
-    v = real(stats%nonfinite, c_double);  call gsum(v);  stats%nonfinite = int(v, c_int64_t)
-  contains
-    subroutine gsum(x)
-      real(c_double), intent(inout) :: x
-      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
-    end subroutine gsum
-    subroutine gmax(x)
-      real(c_double), intent(inout) :: x
-      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('field_stats: ' // dlesm_error_text())
-    end subroutine gmax
+    ! no NaN enters these collectives: min .. sumsq are over the finite cells
+    v = -stats%min;  call rank_max('field_stats', v);  stats%min = -v
+    call rank_max('field_stats', stats%max)
+    call rank_sum('field_stats', stats%sum)
+    call rank_sum('field_stats', stats%sumsq)
+    call rank_total('field_stats', stats%count)
+    call rank_total('field_stats', stats%nonfinite)
   end subroutine field_stats
 
   !> After a check has tripped: the local (i, j) of the first cell (row by row) of fld%internal ON THIS RANK, counted

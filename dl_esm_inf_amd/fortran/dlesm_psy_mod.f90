@@ -743,7 +743,7 @@ contains
   !! flow fields need valid depth-1 halos; collective there.
   subroutine tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, res, face_limit, outflow_limit, face_rank, &
                             outflow_rank)
-    use parallel_utils_mod, only: DIST_MEM_ENABLED, get_rank
+    use rank_collectives_mod, only: place, rank_total
     real(go_wp), intent(in) :: rdt
     type(r2d_field), intent(inout), target :: un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v
     type(tracer_courant_type), intent(out) :: res
@@ -766,46 +766,12 @@ contains
                                   field_device_data(sshn_t), field_device_data(sshn_u), field_device_data(sshn_v), fl, ol, &
                                   res, c_null_ptr)
     if (rc /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
-    fr = 0;  orank = 0
-    if (res%face_index >= 0) fr = get_rank()
-    if (res%outflow_index >= 0) orank = get_rank()
-    if (DIST_MEM_ENABLED) then
-       call place(res%face_max, res%face_index, fr)
-       call place(res%outflow_max, res%outflow_index, orank)
-       call total(res%face_over);  call total(res%outflow_over);  call total(res%invalid);  call total(res%wet)
-    end if
+    call place('tracer_courant', res%face_max, res%face_index, fr)
+    call place('tracer_courant', res%outflow_max, res%outflow_index, orank)
+    call rank_total('tracer_courant', res%face_over);  call rank_total('tracer_courant', res%outflow_over)
+    call rank_total('tracer_courant', res%invalid);  call rank_total('tracer_courant', res%wet)
     if (present(face_rank)) face_rank = fr
     if (present(outflow_rank)) outflow_rank = orank
-  contains
-    ! the maximum over the ranks, the lowest rank that attains it and that rank's index (no NaN enters these collectives)
-    subroutine place(top, index, owner)
-      real(c_double), intent(inout) :: top
-      integer(c_int64_t), intent(inout) :: index
-      integer, intent(inout) :: owner
-      real(c_double) :: x, mine
-      logical :: have
-      x = top
-      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
-      have = index >= 0 .and. top == x
-      top = x
-      mine = -1.0e9_c_double
-      if (have) mine = -real(get_rank(), c_double)
-      if (dlesm_global_max_f64(mine) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
-      owner = 0
-      if (mine > -1.0e9_c_double) owner = nint(-mine)
-      x = 0.0_c_double
-      if (have .and. owner == get_rank()) x = real(index, c_double)            ! exact below 2**53
-      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
-      index = -1
-      if (owner > 0) index = nint(x, c_int64_t)
-    end subroutine place
-    subroutine total(n)
-      integer(c_int64_t), intent(inout) :: n
-      real(c_double) :: x
-      x = real(n, c_double)                                                    ! exact below 2**53
-      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('tracer_courant: ' // dlesm_error_text())
-      n = nint(x, c_int64_t)
-    end subroutine total
   end subroutine tracer_courant
 
   !> "May the flow step take this rdt" (dlesm_flow_courant_f64, DESIGN.md section 6.15): one read-only sweep over the level-n
@@ -818,7 +784,7 @@ contains
   !! j = index / nx + 1.  Synchronous.  On a decomposed grid the fields need valid depth-1 halos; collective there.
   subroutine flow_courant(rdt, un, vn, ht, sshn_t, res, g, visc, gravity_limit, advective_limit, viscous_limit, depth_limit, &
                           gravity_rank, advective_rank, viscous_rank, depth_rank)
-    use parallel_utils_mod, only: DIST_MEM_ENABLED, get_rank
+    use rank_collectives_mod, only: place, rank_total
     real(go_wp), intent(in) :: rdt
     type(r2d_field), intent(inout), target :: un, vn, ht, sshn_t
     type(flow_courant_type), intent(out) :: res
@@ -844,55 +810,19 @@ contains
                                 field_device_data(un), field_device_data(vn), field_device_data(ht), &
                                 field_device_data(sshn_t), gl, al, vl, dl, res, c_null_ptr)
     if (rc /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
-    gr = 0;  ar = 0;  vr = 0;  dr = 0
-    if (res%gravity_index >= 0) gr = get_rank()
-    if (res%advective_index >= 0) ar = get_rank()
-    if (res%viscous_index >= 0) vr = get_rank()
-    if (res%depth_index >= 0) dr = get_rank()
-    if (DIST_MEM_ENABLED) then
-       call place(res%gravity_max, res%gravity_index, gr)
-       call place(res%advective_max, res%advective_index, ar)
-       call place(res%viscous_max, res%viscous_index, vr)
-       deep = -res%depth_min                                                     ! the minimum as the maximum of -d
-       call place(deep, res%depth_index, dr)
-       res%depth_min = -deep
-       call total(res%gravity_over);  call total(res%advective_over);  call total(res%viscous_over)
-       call total(res%shallow);  call total(res%invalid);  call total(res%wet)
-    end if
+    call place('flow_courant', res%gravity_max, res%gravity_index, gr)
+    call place('flow_courant', res%advective_max, res%advective_index, ar)
+    call place('flow_courant', res%viscous_max, res%viscous_index, vr)
+    deep = -res%depth_min                                                        ! the minimum as the maximum of -d
+    call place('flow_courant', deep, res%depth_index, dr)
+    res%depth_min = -deep
+    call rank_total('flow_courant', res%gravity_over);  call rank_total('flow_courant', res%advective_over)
+    call rank_total('flow_courant', res%viscous_over);  call rank_total('flow_courant', res%shallow)
+    call rank_total('flow_courant', res%invalid);  call rank_total('flow_courant', res%wet)
     if (present(gravity_rank)) gravity_rank = gr
     if (present(advective_rank)) advective_rank = ar
     if (present(viscous_rank)) viscous_rank = vr
     if (present(depth_rank)) depth_rank = dr
-  contains
-    ! the maximum over the ranks, the lowest rank that attains it and that rank's index (no NaN enters these collectives)
-    subroutine place(top, index, owner)
-      real(c_double), intent(inout) :: top
-      integer(c_int64_t), intent(inout) :: index
-      integer, intent(inout) :: owner
-      real(c_double) :: x, mine
-      logical :: have
-      x = top
-      if (dlesm_global_max_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
-      have = index >= 0 .and. top == x
-      top = x
-      mine = -1.0e9_c_double
-      if (have) mine = -real(get_rank(), c_double)
-      if (dlesm_global_max_f64(mine) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
-      owner = 0
-      if (mine > -1.0e9_c_double) owner = nint(-mine)
-      x = 0.0_c_double
-      if (have .and. owner == get_rank()) x = real(index, c_double)            ! exact below 2**53
-      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
-      index = -1
-      if (owner > 0) index = nint(x, c_int64_t)
-    end subroutine place
-    subroutine total(n)
-      integer(c_int64_t), intent(inout) :: n
-      real(c_double) :: x
-      x = real(n, c_double)                                                    ! exact below 2**53
-      if (dlesm_global_sum_f64(x) /= 0) call gocean_stop('flow_courant: ' // dlesm_error_text())
-      n = nint(x, c_int64_t)
-    end subroutine total
   end subroutine flow_courant
 
   !> The model's output fields in one sweep (dlesm_flow_output_f64, DESIGN.md section 6.16): of the level-n flow, into the
@@ -1234,6 +1164,7 @@ contains
   function invoke_jacobi5_residual(out, in, norm) result(r)
     use parallel_comms_mod, only: halo_plan_for
     use parallel_utils_mod, only: DIST_MEM_ENABLED
+    use rank_collectives_mod, only: rank_max, rank_sum
     type(r2d_field), intent(inout), target :: out, in
     character(len=*), intent(in) :: norm
     real(go_wp) :: r
@@ -1266,12 +1197,11 @@ contains
     if (hipMemcpy(c_loc(val), dres, int(c_sizeof(val), c_size_t), 2_c_int) /= 0) &
          call gocean_stop('invoke_jacobi5_residual: copy of the result failed')
     if (code == DLESM_NORM_MAX) then
-       rc = dlesm_global_max_f64(val)
+       call rank_max('invoke_jacobi5_residual', val)
     else
-       rc = dlesm_global_sum_f64(val)
+       call rank_sum('invoke_jacobi5_residual', val)
        val = sqrt(val)
     end if
-    if (rc /= 0) call gocean_stop('invoke_jacobi5_residual: ' // dlesm_error_text())
     r = val
   end function invoke_jacobi5_residual
 

@@ -107,6 +107,50 @@ def on_master():
     return _rank == 1
 
 
+def _collective(entry, v):
+    if _nranks == 1:
+        return v
+    val = C.c_double(v)
+    check(getattr(_cabi.lib(), entry)(C.byref(val)))
+    return val.value
+
+
+def global_sum(v):
+    """global_sum (parallel_utils_mod.f90): the sum of every rank's float `v`; collective"""
+    return _collective("dlesm_global_sum_f64", v)
+
+
+def global_max(v):
+    """the largest of every rank's float `v`; collective.  A minimum goes in and comes out negated."""
+    return _collective("dlesm_global_max_f64", v)
+
+
+def _global_count(n):
+    """the sum of every rank's int `n`, carried as a double: exact below 2**53"""
+    return int(global_sum(float(n)))
+
+
+def _owner(here, i, j):
+    """(owner, i, j): the lowest rank (1-based) that passes here = True, and that rank's i and j; None if no rank does"""
+    owner = int(-global_max(-float(_rank) if here else -1.0e9))
+    i = int(global_sum(float(i) if here and _rank == owner else 0.0))
+    j = int(global_sum(float(j) if here and _rank == owner else 0.0))
+    return (owner, i, j) if owner < 1.0e9 else None
+
+
+def _place(local_top, index, nx):
+    """THE ownership rule of the diagnostics: the global maximum `top` of local_top and
+    (rank, i, j) of the lowest rank that attains it -- one that has a cell (index >= 0, 0-based linear in rows of nx) and
+    whose local_top IS top -- with that rank's local 1-based indices, or None.  No NaN enters these collectives."""
+    top = global_max(local_top)
+    return top, _owner(index >= 0 and local_top == top, index % nx + 1, index // nx + 1)
+
+
+def _where(at):
+    """an (owner, i, j) or None, as the *_check messages word it"""
+    return "at local (i, j) = (%d, %d) on rank %d" % (at[1], at[2], at[0]) if at else "nowhere"
+
+
 def go_decompose(domainx, domainy, ndomains=None, ndomainx=None, ndomainy=None, halo_width=1):
     """go_decompose (parallel_mod.f90:70-332)"""
     if ndomains is None:

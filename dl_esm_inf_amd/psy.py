@@ -6,9 +6,9 @@ import collections
 import ctypes as C
 import math
 
-from . import _cabi, grid_mod
+from . import _cabi, grid_mod, parallel_mod
 from ._cabi import SwParams, check
-from .field_mod import GO_T_POINTS, _stream_ptr, field_bounds
+from .field_mod import GO_T_POINTS, _fetch_record, _stream_ptr, field_bounds
 
 
 def invoke_jacobi5(out_fld, in_fld, stream=None):
@@ -388,42 +388,15 @@ def tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit=0
       rdt_limit     rdt * min(face_limit / face_max, outflow_limit / outflow_max), inf when both maxima are 0 -- an
                     ESTIMATE of the largest rdt that keeps both limits: the numbers are linear in rdt only up to rounding.
     On a decomposed grid the flow fields need valid depth-1 halos; collective there."""
-    import torch
-
-    from . import parallel_mod
     g, it = sshn_t.grid, sshn_t.internal
-    L = _cabi.lib()
-    s = stream if stream is not None else torch.cuda.current_stream()
-    with torch.cuda.stream(s):                              # (device memory on the caller's stream: see field_mod.field_stats)
-        res = torch.empty(8, dtype=torch.float64, device=sshn_t.data.device)
-        check(L.dlesm_tracer_courant_async_f64(
+    r = _cabi.TracerCourant.from_buffer_copy(_fetch_record(               # (see there for where the record lives)
+        stream, sshn_t.data.device, 8, lambda res, s: check(_cabi.lib().dlesm_tracer_courant_async_f64(
             float(rdt), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
             C.c_void_p(g.area_t_device.data_ptr()), *[f.device_ptr for f in (un, vn, hu, hv, ht, sshn_t, sshn_u, sshn_v)],
-            float(face_limit), float(outflow_limit), C.c_void_p(res.data_ptr()), _stream_ptr(s)))
-        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
-    r = _cabi.TracerCourant.from_buffer_copy(host.tobytes())
-    rank, many = parallel_mod.get_rank(), parallel_mod.get_num_ranks() > 1
-
-    def glob(fn, v):
-        if not many:
-            return v
-        val = C.c_double(v)
-        check(fn(C.byref(val)))
-        return val.value
-
-    def place(local_max, index):
-        """the global maximum and (rank, i, j) of the lowest rank that attains it"""
-        top = glob(L.dlesm_global_max_f64, local_max)       # (no NaN, nothing negative: see the record's definition)
-        mine = index >= 0 and local_max == top
-        owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if mine else -1.0e9))
-        i = int(glob(L.dlesm_global_sum_f64, float(index % g.nx + 1) if mine and rank == owner else 0.0))
-        j = int(glob(L.dlesm_global_sum_f64, float(index // g.nx + 1) if mine and rank == owner else 0.0))
-        return top, ((owner, i, j) if owner < 1.0e9 else None)
-
-    face_max, face_at = place(r.face_max, r.face_index)
-    outflow_max, outflow_at = place(r.outflow_max, r.outflow_index)
-    counts = [int(glob(L.dlesm_global_sum_f64, float(c)))   # exact below 2**53
-              for c in (r.face_over, r.outflow_over, r.invalid, r.wet)]
+            float(face_limit), float(outflow_limit), res, s))))
+    face_max, face_at = parallel_mod._place(r.face_max, r.face_index, g.nx)
+    outflow_max, outflow_at = parallel_mod._place(r.outflow_max, r.outflow_index, g.nx)
+    counts = [parallel_mod._global_count(c) for c in (r.face_over, r.outflow_over, r.invalid, r.wet)]
     ratio = min(float(face_limit) / face_max if face_max > 0.0 else math.inf,
                 float(outflow_limit) / outflow_max if outflow_max > 0.0 else math.inf)
     return TracerCourantResult(face_max, outflow_max, face_at, outflow_at, *counts,
@@ -436,17 +409,14 @@ def tracer_courant_check(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_l
     (i, j) of the cell that holds the maximum (an invalid cell enters no maximum: its count is all the record has).  Returns
     the TracerCourantResult otherwise."""
     r = tracer_courant(rdt, un, vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, face_limit, outflow_limit, stream)
-
-    def where(at):
-        return "at local (i, j) = (%d, %d) on rank %d" % (at[1], at[2], at[0]) if at else "nowhere"
     if r.invalid > 0:
         why = "invalid: %d wet cell(s) hold a Courant number that is not finite and >= 0 (rdt = %r)" % (r.invalid, float(rdt))
     elif r.face_over > 0:
         why = "face_over: %d wet cell(s) reach face_limit = %r; face_max = %r %s" % (
-            r.face_over, float(face_limit), r.face_max, where(r.face_at))
+            r.face_over, float(face_limit), r.face_max, parallel_mod._where(r.face_at))
     elif r.outflow_over > 0:
         why = "outflow_over: %d wet cell(s) reach outflow_limit = %r; outflow_max = %r %s" % (
-            r.outflow_over, float(outflow_limit), r.outflow_max, where(r.outflow_at))
+            r.outflow_over, float(outflow_limit), r.outflow_max, parallel_mod._where(r.outflow_at))
     else:
         return r
     raise _cabi.DlesmError(_cabi.EABORT, "tracer_courant_check: %s; rdt_limit = %r" % (why, r.rdt_limit))
@@ -484,48 +454,21 @@ def flow_courant(rdt, un, vn, ht, sshn_t, g=None, visc=None, gravity_limit=1.0, 
       rdt_limit     rdt * min(limit / maximum) over the three maxima that are not 0, inf when all are -- an ESTIMATE of the
                     largest rdt that keeps the three limits: the numbers are linear in rdt only up to rounding.
     On a decomposed grid the fields need valid depth-1 halos; collective there."""
-    import torch
-
-    from . import parallel_mod
     gv, nu = _flow_constants("flow_courant", g, visc, params)
     grid, it = sshn_t.grid, sshn_t.internal
-    L = _cabi.lib()
-    s = stream if stream is not None else torch.cuda.current_stream()
     limits = (float(gravity_limit), float(advective_limit), float(viscous_limit))
-    with torch.cuda.stream(s):                              # (device memory on the caller's stream: see field_mod.field_stats)
-        res = torch.empty(16, dtype=torch.float64, device=sshn_t.data.device)
-        check(L.dlesm_flow_courant_async_f64(
+    r = _cabi.FlowCourant.from_buffer_copy(_fetch_record(                 # (see there for where the record lives)
+        stream, sshn_t.data.device, 16, lambda res, s: check(_cabi.lib().dlesm_flow_courant_async_f64(
             float(rdt), gv, nu, grid.nx, grid.ny, it.xstart, it.xstop, it.ystart, it.ystop, grid.tmask_device_ptr,
             C.c_void_p(grid.dx_t_device.data_ptr()), C.c_void_p(grid.dy_t_device.data_ptr()),
-            *[f.device_ptr for f in (un, vn, ht, sshn_t)], *limits, float(depth_limit), C.c_void_p(res.data_ptr()),
-            _stream_ptr(s)))
-        host = res.cpu().numpy()                            # (a copy on `s` that the host waits for)
-    r = _cabi.FlowCourant.from_buffer_copy(host.tobytes())
-    rank, many = parallel_mod.get_rank(), parallel_mod.get_num_ranks() > 1
-
-    def glob(fn, v):
-        if not many:
-            return v
-        val = C.c_double(v)
-        check(fn(C.byref(val)))
-        return val.value
-
-    def place(local_top, index):
-        """the global maximum and (rank, i, j) of the lowest rank that attains it (tracer_courant's rule)"""
-        top = glob(L.dlesm_global_max_f64, local_top)       # (no NaN enters these collectives)
-        mine = index >= 0 and local_top == top
-        owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if mine else -1.0e9))
-        i = int(glob(L.dlesm_global_sum_f64, float(index % grid.nx + 1) if mine and rank == owner else 0.0))
-        j = int(glob(L.dlesm_global_sum_f64, float(index // grid.nx + 1) if mine and rank == owner else 0.0))
-        return top, ((owner, i, j) if owner < 1.0e9 else None)
-
+            *[f.device_ptr for f in (un, vn, ht, sshn_t)], *limits, float(depth_limit), res, s))))
     tops, ats = [], []
     for top, index in ((r.gravity_max, r.gravity_index), (r.advective_max, r.advective_index),
                        (r.viscous_max, r.viscous_index), (-r.depth_min, r.depth_index)):   # the minimum as a maximum of -d
-        top, at = place(top, index)
+        top, at = parallel_mod._place(top, index, grid.nx)
         tops.append(top), ats.append(at)
     tops[3] = -tops[3]
-    counts = [int(glob(L.dlesm_global_sum_f64, float(c)))   # exact below 2**53
+    counts = [parallel_mod._global_count(c)
               for c in (r.gravity_over, r.advective_over, r.viscous_over, r.shallow, r.invalid, r.wet)]
     ratio = min(lim / top if top > 0.0 else math.inf for lim, top in zip(limits, tops[:3]))
     return FlowCourantResult(*tops, *ats, *counts, float(rdt) * ratio if ratio != math.inf else math.inf)
@@ -539,24 +482,21 @@ def flow_courant_check(rdt, un, vn, ht, sshn_t, g=None, visc=None, gravity_limit
     otherwise."""
     r = flow_courant(rdt, un, vn, ht, sshn_t, g, visc, gravity_limit, advective_limit, viscous_limit, depth_limit, params,
                      stream)
-
-    def where(at):
-        return "at local (i, j) = (%d, %d) on rank %d" % (at[1], at[2], at[0]) if at else "nowhere"
     if r.invalid > 0:
         why = "invalid: %d wet cell(s) hold a water column that is not finite and > 0 or a number that is not finite and " \
               ">= 0 (rdt = %r)" % (r.invalid, float(rdt))
     elif r.gravity_over > 0:
         why = "gravity_over: %d wet cell(s) reach gravity_limit = %r; gravity_max = %r %s" % (
-            r.gravity_over, float(gravity_limit), r.gravity_max, where(r.gravity_at))
+            r.gravity_over, float(gravity_limit), r.gravity_max, parallel_mod._where(r.gravity_at))
     elif r.advective_over > 0:
         why = "advective_over: %d wet cell(s) reach advective_limit = %r; advective_max = %r %s" % (
-            r.advective_over, float(advective_limit), r.advective_max, where(r.advective_at))
+            r.advective_over, float(advective_limit), r.advective_max, parallel_mod._where(r.advective_at))
     elif r.viscous_over > 0:
         why = "viscous_over: %d wet cell(s) reach viscous_limit = %r; viscous_max = %r %s" % (
-            r.viscous_over, float(viscous_limit), r.viscous_max, where(r.viscous_at))
+            r.viscous_over, float(viscous_limit), r.viscous_max, parallel_mod._where(r.viscous_at))
     elif r.shallow > 0:
         why = "shallow: %d wet cell(s) are no deeper than depth_limit = %r; depth_min = %r %s" % (
-            r.shallow, float(depth_limit), r.depth_min, where(r.depth_at))
+            r.shallow, float(depth_limit), r.depth_min, parallel_mod._where(r.depth_at))
     else:
         return r
     raise _cabi.DlesmError(_cabi.EABORT, "flow_courant_check: %s; rdt_limit = %r" % (why, r.rdt_limit))
@@ -905,32 +845,21 @@ def invoke_jacobi5_residual(out_fld, in_fld, norm="max", stream=None):
     out_fld%internal on all ranks: max|out - in| (norm="max") or sqrt(SUM (out - in)**2) (norm="l2").  Synchronous: what a
     solver checks every few steps to know when to stop.  On a decomposed grid it first joins a pipelined step's exchange
     (`in`'s halos) and leaves `out` with its depth-1 halos exchanged, as invoke_jacobi5_dm does."""
-    import torch
-
-    from . import parallel_mod
     codes = {"max": _cabi.NORM_MAX, "l2": _cabi.NORM_SUMSQ}
     if norm not in codes:
         raise ValueError(f"invoke_jacobi5_residual: norm {norm!r} is not 'max' or 'l2'")
     g, it = out_fld.grid, out_fld.internal
-    L = _cabi.lib()
     dm = parallel_mod.get_num_ranks() > 1
     if dm:
         halo_join(g, stream)
-    s = stream if stream is not None else torch.cuda.current_stream()
-    # the value lands in device memory allocated on the step's own stream and comes back by a copy on it -- not in torch's
-    # pinned host memory, which ROCm allocates non-coherent by default: a device store there may reach the host late
-    with torch.cuda.stream(s):
-        res = torch.empty(1, dtype=torch.float64, device=out_fld.data.device)
-        check(L.dlesm_stencil5_resid_f64(in_fld.device_ptr, out_fld.device_ptr, g.nx, g.ny, it.xstart, it.xstop,
-                                         it.ystart, it.ystop, codes[norm], C.c_void_p(res.data_ptr()), _stream_ptr(s)))
+
+    def step(res, s):                                       # the sweep, then the exchange, then _fetch_record's copy
+        check(_cabi.lib().dlesm_stencil5_resid_f64(in_fld.device_ptr, out_fld.device_ptr, g.nx, g.ny, it.xstart, it.xstop,
+                                                   it.ystart, it.ystop, codes[norm], res, s))
         if dm:
-            out_fld.halo_exchange(1, stream=s)
-        val = C.c_double(res.item())                        # (a copy on `s` that the host waits for)
-    if norm == "max":
-        check(L.dlesm_global_max_f64(C.byref(val)))
-        return val.value
-    check(L.dlesm_global_sum_f64(C.byref(val)))
-    return math.sqrt(val.value)
+            out_fld.halo_exchange(1, stream=stream)         # (None: the current stream, which is `stream` in there)
+    val = C.c_double.from_buffer_copy(_fetch_record(stream, out_fld.data.device, 1, step)).value
+    return parallel_mod.global_max(val) if norm == "max" else math.sqrt(parallel_mod.global_sum(val))
 
 
 def run_health(fields, names, masks=None, max_abs=None, stream=None):
@@ -940,7 +869,7 @@ def run_health(fields, names, masks=None, max_abs=None, stream=None):
     max_abs[k] (max_abs: None, one bound for all fields, or one entry per field, None = no bound).  The message names the
     field, the lowest rank (1-based, parallel_mod.get_rank) that holds an offending cell and the local 1-based (i, j) of
     its first such cell."""
-    from . import field_mod, parallel_mod
+    from . import field_mod
     fields, names = list(fields), list(names)
     if len(names) != len(fields):
         raise ValueError(f"run_health: {len(names)} names for {len(fields)} fields")
@@ -959,18 +888,8 @@ def run_health(fields, names, masks=None, max_abs=None, stream=None):
         else:
             continue
         here = field_mod.field_locate(fields[k], what, value, mlist[k], stream)
-        rank, (i, j) = parallel_mod.get_rank(), here or (0, 0)
-        if parallel_mod.get_num_ranks() > 1:
-            L = _cabi.lib()
-
-            def glob(fn, v):
-                val = C.c_double(v)
-                check(fn(C.byref(val)))
-                return val.value
-            owner = int(-glob(L.dlesm_global_max_f64, -float(rank) if here else -1.0e9))
-            i = int(glob(L.dlesm_global_sum_f64, float(i) if rank == owner else 0.0))
-            j = int(glob(L.dlesm_global_sum_f64, float(j) if rank == owner else 0.0))
-            rank = owner
+        i, j = here or (0, 0)
+        rank, i, j = parallel_mod._owner(here is not None, i, j) or (parallel_mod.get_rank(), 0, 0)
         raise _cabi.DlesmError(_cabi.EABORT, f"run_health: field {name}: {why}; first at local (i, j) = ({i}, {j}) on rank {rank}")
     return stats
 

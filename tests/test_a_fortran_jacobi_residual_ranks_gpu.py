@@ -6,7 +6,6 @@ step first and exchanges `out` after, as invoke_jacobi5_dm).  Sorts before the i
 have touched the GPU when it starts children."""
 import os
 import re
-import socket
 import struct
 import subprocess
 import time
@@ -14,6 +13,7 @@ import time
 import pytest
 
 from conftest import ROOT
+from rank_world import run_world
 
 pytestmark = pytest.mark.gpu
 FDIR = os.path.join(ROOT, "dl_esm_inf_amd", "fortran")
@@ -21,34 +21,10 @@ EXE = os.path.join(FDIR, "build", "ftest_jacobi_residual.exe")
 NX, NY = 130, 100
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _run(world):
-    port = _free_port()
-    job = f"pytest-{port}-{os.getpid()}-{time.time_ns()}"
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), DLESM_TRANSPORT="mailbox", DLESM_JOB_ID=job, DLESM_BOARD_TIMEOUT_S="120",
-                   HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1", DL_ESM_ALIGNMENT="64")
-        procs.append(subprocess.Popen([EXE, str(NX), str(NY), "dm", "-"], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    deadline = time.monotonic() + 300
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            for q in procs:
-                q.wait()
-            raise
-        outs.append(out)
+    env = dict(LOCAL_RANK="0", DLESM_TRANSPORT="mailbox", DLESM_JOB_ID=f"pytest-{os.getpid()}-{time.time_ns()}",
+               DLESM_BOARD_TIMEOUT_S="120", DL_ESM_ALIGNMENT="64")
+    procs, outs = run_world([EXE, str(NX), str(NY), "dm", "-"], world, env)
     vals = []
     for r, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, f"rank {r} of {world} failed:\n{out[-3000:]}"

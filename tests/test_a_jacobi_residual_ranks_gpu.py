@@ -5,22 +5,14 @@ bit for bit at every check, the same stopping step, l2 within 1e-12, valid halos
 with a NaN on one rank.  Sorts before the in-process GPU tests: the pytest process must not have touched the GPU when it starts
 children."""
 import os
-import socket
-import subprocess
 import sys
-import time
 
 import pytest
 
 from conftest import ROOT
+from rank_world import run_world
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 @pytest.mark.parametrize("nx,ny,ndx,ndy", [(48, 40, 2, 1),      # x-split
@@ -29,26 +21,8 @@ def test_jacobi_residual_between_processes(nx, ny, ndx, ndy):
     import torch
     assert not torch.cuda.is_initialized(), "run this file before any in-process GPU test"
     world = ndx * ndy
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "jacobi_residual_worker.py"), str(nx),
-                                       str(ny), str(ndx), str(ndy)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    deadline = time.monotonic() + 300                # ONE deadline for the whole world
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            for q in procs:
-                q.wait()
-            raise
-        outs.append(out)
+    procs, outs = run_world([sys.executable, os.path.join(ROOT, "tests", "jacobi_residual_worker.py"), str(nx), str(ny), str(ndx),
+                             str(ndy)], world)
     for r, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, f"rank {r} failed:\n{out[-3000:]}"
         assert "ERROR" not in out, out[-3000:]
