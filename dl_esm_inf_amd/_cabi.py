@@ -311,6 +311,9 @@ PROTOTYPES = {
     "dlesm_cell_bin_f64": (_i, [_i, _d, _i, _i, _i, _i, _i, _i, C.c_longlong] + [_vp] * 4 +
                            [_i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.c_longlong, _vp]),
     "dlesm_cell_bin_set": (_i, [_vp, _i, _d] + [_i] * 6 + [_vp, _vp]),
+    "dlesm_dispersal_step_f64": (_i, [_d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 5 + [C.c_longlong] +
+                                 [_vp] * 5),
+    "dlesm_dispersal_step_set": (_i, [_vp, _d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 6),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

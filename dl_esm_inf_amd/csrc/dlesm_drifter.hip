@@ -56,18 +56,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (!active) return;
 
     double x = a.px[p], y = a.py[p];
-    const int ld = a.ld;
-    // 1-based cell -> offset; every cell asked for is a cell of the box or of its ring
-    const auto at = [ld](int i, int j) { return (size_t)(j - 1) * (size_t)ld + (size_t)(i - 1); };
-    const auto mask = [&](int i, int j) { return a.tmask[at(i, j)]; };
-    const auto cell = [&](int i, int j) {
-        const size_t o = at(i, j);
-        DrifterCell c;
-        c.t_e = a.tmask[o + 1], c.t_w = a.tmask[o - 1], c.t_n = a.tmask[o + ld], c.t_s = a.tmask[o - ld];
-        c.u_e = a.un[o], c.u_w = a.un[o - 1], c.v_n = a.vn[o], c.v_s = a.vn[o - ld];
-        c.dx = a.dx_t[o], c.dy = a.dy_t[o];
-        return c;
-    };
+    const DrifterFlow f{a.tmask, a.dx_t, a.dy_t, a.un, a.vn, a.ld};
+    const auto mask = [&](int i, int j) { return f.mask(i, j); };
+    const auto cell = [&](int i, int j) { return f.cell(i, j); };
 
     int st;
     if (!a.box.has(x, y)) {
@@ -111,18 +102,14 @@ int check_particles(const char *who, int ld, int ny, int xstart, int xstop, int 
 
 } // namespace
 
-} // namespace dlesm
-
-using namespace dlesm;
-
-extern "C" int dlesm_drifter_step_f64(double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                                      const int *tmask, const double *dx_t, const double *dy_t, const double *un,
-                                      const double *vn, long long n, double *px, double *py, int *status, void *stream)
+// the checks every particle step shares (dlesm_dispersal.hip makes them too): what dlesm_drifter_step_f64 refuses.
+// *nothing: n == 0 or an empty box
+int lagrangian_step_checks(const char *who, double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                           const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
+                           long long n, const double *px, const double *py, const int *status, bool *nothing)
 {
-    static const char *const who = "dlesm_drifter_step_f64";
     static const char *const in_name[4] = {"dx_t", "dy_t", "un", "vn"};
     static const char *const p_name[3] = {"px", "py", "status"};
-    if (int rc = ensure_device()) return rc;
     DLESM_REQUIRE(std::isfinite(h), "%s: h = %g (a finite number of seconds)", who, h);
     DLESM_REQUIRE(nsub >= 1 && nsub <= DLESM_DRIFTER_MAX_SUB, "%s: nsub = %d (1..%d)", who, nsub, DLESM_DRIFTER_MAX_SUB);
     const double *const ins[4] = {dx_t, dy_t, un, vn};
@@ -144,7 +131,25 @@ extern "C" int dlesm_drifter_step_f64(double h, int nsub, int ld, int ny, int xs
         for (int m = k + 1; m < 3; m++)
             DLESM_REQUIRE(!overlap(parts[k], pb[k], parts[m], pb[m]), "%s: %s and %s overlap", who, p_name[k], p_name[m]);
     }
-    if (n == 0 || empty) return DLESM_OK;
+    *nothing = n == 0 || empty;
+    return DLESM_OK;
+}
+
+} // namespace dlesm
+
+using namespace dlesm;
+
+extern "C" int dlesm_drifter_step_f64(double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                                      const int *tmask, const double *dx_t, const double *dy_t, const double *un,
+                                      const double *vn, long long n, double *px, double *py, int *status, void *stream)
+{
+    static const char *const who = "dlesm_drifter_step_f64";
+    if (int rc = ensure_device()) return rc;
+    bool nothing;
+    if (int rc = lagrangian_step_checks(who, h, nsub, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, n, px, py,
+                                        status, &nothing))
+        return rc;
+    if (nothing) return DLESM_OK;
 
     const DrifterArgs a{tmask, dx_t, dy_t, un, vn, px, py, status, n,
                         DrifterBox{(double)xstart, (double)xstop + 1.0, (double)ystart, (double)ystop + 1.0}, h, nsub, ld};

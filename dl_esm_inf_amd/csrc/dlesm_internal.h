@@ -337,6 +337,11 @@ int launch_stencil5_multi(const double *in, double *out, int ld, int ny, int nst
                           int ge, int gs, int gn, hipStream_t s);
 
 int check_box(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, int ring);
+// everything dlesm_drifter_step_f64 refuses, for every entry that steps particles (dlesm_drifter.hip; dlesm_dispersal.hip adds
+// its own); *nothing = n == 0 or an empty box: return DLESM_OK without a launch
+int lagrangian_step_checks(const char *who, double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                           const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
+                           long long n, const double *px, const double *py, const int *status, bool *nothing);
 // two shallow-water steps per launch (dlesm_shallow_x2.hip): the overlap check of the twelve arrays, and the distributed form's
 // wave-tile conditions and launch (stage 1 computed on the box grown by gw..gn; see shallow_tile_x2_grown)
 int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny);

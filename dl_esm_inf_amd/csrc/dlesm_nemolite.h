@@ -223,6 +223,25 @@ struct DrifterCell {
 struct DrifterMove {
     double kx, ky;
 };
+// the arrays a particle step gathers from, and the one text of its 64-bit offsets: at(i, j) of a 1-based cell -- every cell
+// asked for is a cell of the box or of its ring --, mask(i, j) = T there, cell(i, j) the DrifterCell, its ten loads
+// unconditional and all issued before any is used
+struct DrifterFlow {
+    const int *tmask;
+    const double *dx_t, *dy_t, *un, *vn;
+    int ld;
+    __device__ __forceinline__ size_t at(int i, int j) const { return (size_t)(j - 1) * (size_t)ld + (size_t)(i - 1); }
+    __device__ __forceinline__ int mask(int i, int j) const { return tmask[at(i, j)]; }
+    __device__ __forceinline__ DrifterCell cell(int i, int j) const
+    {
+        const size_t o = at(i, j);
+        DrifterCell c;
+        c.t_e = tmask[o + 1], c.t_w = tmask[o - 1], c.t_n = tmask[o + ld], c.t_s = tmask[o - ld];
+        c.u_e = un[o], c.u_w = un[o - 1], c.v_n = vn[o], c.v_s = vn[o - ld];
+        c.dx = dx_t[o], c.dy = dy_t[o];
+        return c;
+    }
+};
 // the displacement of one substep of h seconds, in cells, at (x, y) inside cell (i, j): section 6.10's face switches (the
 // ones flow_output_point uses), linear between the faces.  Selects, never blends: a face that touches land carries nothing.
 __device__ __forceinline__ DrifterMove drifter_vel(double h, double x, double y, int i, int j, const DrifterCell &c)
@@ -262,6 +281,80 @@ __device__ __forceinline__ int drifter_substep(double h, const DrifterBox &box, 
     if (tn == 0) return DLESM_DRIFTER_GROUNDED;
     x = xn, y = yn, i = in, j = jn;
     return tn < 0 ? DLESM_DRIFTER_OPEN : DLESM_DRIFTER_ACTIVE;
+}
+
+// Random-walk diffusion (dlesm_dispersal.hip).  Philox4x32-10 as published (Salmon et al., "Parallel
+// random numbers: as easy as 1, 2, 3", SC11): a counter-based generator, integer arithmetic alone, no state anywhere.
+struct Philox4 {
+    unsigned w[4];
+};
+__host__ __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                                          unsigned k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1, c3 = (unsigned)p0, c0 = n0, c2 = n2;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+// a word -> the centre of its bin of (-1, 1): exact, never 0, symmetric (w and ~w give opposite numbers)
+__host__ __device__ __forceinline__ double philox_sym(unsigned w) { return ((double)w + 0.5) * 0x1p-31 - 1.0; }
+// the kick of particle `id` at substep `tau`, before the metrics divide it: amp metres times two numbers of (-1, 1)
+__device__ __forceinline__ DrifterMove dispersal_kick(double amp, unsigned id, unsigned long long tau, unsigned k0, unsigned k1)
+{
+    const Philox4 r = philox4x32_10(id, 0u, (unsigned)tau, (unsigned)(tau >> 32), k0, k1);
+    return DrifterMove{amp * philox_sym(r.w[0]), amp * philox_sym(r.w[1])};
+}
+// pin_here (dlesm_internal.h) for an int: a load behind it cannot be sunk into a lane-varying branch
+__device__ __forceinline__ int pin_here(int x) { return __builtin_amdgcn_mov_dpp(x, 0xE4, 0xf, 0xf, true); }
+// One substep with a kick: k1, the midpoint and k2 as drifter_substep, D = (x, y) + k2, A = D + kick() / the metrics of the
+// substep's own cell (stage 1's, already loaded).  A in the box and not on land is taken; a kick that ends on land is
+// rejected -- the no-flux wall -- and D meets drifter_substep's destination rule.  T(cell(A)) and T(cell(D)) are loaded
+// together and unconditionally, a point outside the box at the particle's own cell and then not used: three dependent round
+// trips as drifter_substep, and whichever destination is taken supplies the next substep's own-cell mask.  kick() is called
+// behind the stage-1 loads and before their first use: its integer work sits under their latency.
+template <class CF, class TF, class KF>
+__device__ __forceinline__ int dispersal_substep(double h, const DrifterBox &box, double &x, double &y, int &i, int &j, CF cell,
+                                                 TF mask, KF kick)
+{
+    const DrifterCell c1 = cell(i, j);
+    const DrifterMove g = kick();
+    __builtin_amdgcn_sched_barrier(0);            // the scheduler would otherwise put the generator behind the loads' first use
+    const DrifterMove k1 = drifter_vel(h, x, y, i, j, c1);
+    const double gx = g.kx / c1.dx, gy = g.ky / c1.dy;
+    const double xm = x + 0.5 * k1.kx, ym = y + 0.5 * k1.ky;
+    const bool in_m = box.has(xm, ym);
+    const double xe = in_m ? xm : x, ye = in_m ? ym : y;
+    const int im = (int)floor(xe), jm = (int)floor(ye);
+    const int tm = mask(im, jm);
+    const DrifterMove km = drifter_vel(h, xe, ye, im, jm, cell(im, jm));
+    const bool mid = in_m && tm > 0;
+    const double k2x = mid ? km.kx : k1.kx, k2y = mid ? km.ky : k1.ky;
+    const double xd = x + k2x, yd = y + k2y;
+    const double xa = xd + gx, ya = yd + gy;
+    const bool in_a = box.has(xa, ya), in_d = box.has(xd, yd);
+    const int ia = (int)floor(in_a ? xa : x), ja = (int)floor(in_a ? ya : y);
+    const int id = (int)floor(in_d ? xd : x), jd = (int)floor(in_d ? yd : y);
+    // pinned: left alone, the compiler sinks each load into the branch that uses it, a fourth round trip for a rejected kick
+    const int ta = pin_here(mask(ia, ja)), td = pin_here(mask(id, jd));
+    if (!in_a) {
+        x = xa, y = ya;
+        return DLESM_DRIFTER_LEFT;
+    }
+    if (ta != 0) {
+        x = xa, y = ya, i = ia, j = ja;
+        return ta < 0 ? DLESM_DRIFTER_OPEN : DLESM_DRIFTER_ACTIVE;
+    }
+    if (!in_d) {
+        x = xd, y = yd;
+        return DLESM_DRIFTER_LEFT;
+    }
+    if (td == 0) return DLESM_DRIFTER_GROUNDED;
+    x = xd, y = yd, i = id, j = jd;
+    return td < 0 ? DLESM_DRIFTER_OPEN : DLESM_DRIFTER_ACTIVE;
 }
 
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,

@@ -1092,6 +1092,37 @@ module dlesm_hip_mod
        type(c_ptr), value :: count, stream
        integer(c_int) :: rc
      end function
+     ! ---- drifters with random-walk diffusion (DESIGN.md section 6.20): section 6.17's step plus a Philox4x32-10 kick of
+     !      variance 2 kh |h| per axis and substep, keyed by seed, counted by (id, tick + substep); id: device ints or
+     !      c_null_ptr (the slot number), tick_dev: one device integer(c_long_long) added to tick and advanced by nsub, or
+     !      c_null_ptr; and the step for the owner, whose origin is the id
+     function dlesm_dispersal_step_f64(h, nsub, kh, seed, tick, tick_dev, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, &
+          dy_t, un, vn, n, id, px, py, status, stream) bind(C, name="dlesm_dispersal_step_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       real(c_double), value :: h
+       integer(c_int), value :: nsub
+       real(c_double), value :: kh
+       integer(c_long_long), value :: seed, tick
+       type(c_ptr), value :: tick_dev
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: id, px, py, status, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_dispersal_step_set(set, h, nsub, kh, seed, tick, tick_dev, ld, ny, xstart, xstop, ystart, ystop, tmask, &
+          dx_t, dy_t, un, vn, stream) bind(C, name="dlesm_dispersal_step_set") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       type(c_ptr), value :: set
+       real(c_double), value :: h
+       integer(c_int), value :: nsub
+       real(c_double), value :: kh
+       integer(c_long_long), value :: seed, tick
+       type(c_ptr), value :: tick_dev
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn, stream
+       integer(c_int) :: rc
+     end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)
      function dlesm_nemolite_coupled_step_dm(plan, wet, scheme, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, &
           vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, c_in, c_out, ntracers, stream) &

@@ -63,6 +63,7 @@ module dlesm_psy_mod
   public :: flow_output
   public :: drifters_type, drifters_create, drifters_get, drifters_free, drifter_step
   public :: particle_sort, particle_origin
+  public :: dispersal_step
   public :: cell_bin
   public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
@@ -957,6 +958,39 @@ contains
     end associate
     if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
   end subroutine drifter_step
+
+  !> drifter_step with random-walk diffusion (dlesm_dispersal_step_set, DESIGN.md section 6.20): every substep adds a kick,
+  !! uniform with variance 2 kh |h| per axis (kh: a constant horizontal diffusivity in m2/s), drawn from Philox4x32-10 with
+  !! the seed as key and (the particle's index at drifters_create, tick + substep) as counter; a kick that would end on land
+  !! is rejected.  seed: any 64 bits; tick: the substeps taken so far (>= 0), which the caller advances by nsub from call to
+  !! call.  A particle keeps its random stream through particle_sort.  The region, the mask, the metrics and the statuses are
+  !! drifter_step's.  Asynchronous on the default stream; nothing is exchanged and the call is not collective.
+  subroutine dispersal_step(set, h, nsub, kh, seed, tick, un, vn)
+    type(drifters_type), intent(inout) :: set
+    real(go_wp), intent(in) :: h
+    integer, intent(in) :: nsub
+    real(go_wp), intent(in) :: kh
+    integer(c_long_long), intent(in) :: seed, tick
+    type(r2d_field), intent(inout), target :: un, vn
+    type(c_region) :: sub, box, whole
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('dispersal_step: the set has not been created')
+    call need_device(un);  call need_device(vn)
+    call grid_to_device(un%grid)
+    associate (g => un%grid)
+      associate (s => g%subdomain%internal)
+        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+      end associate
+      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
+                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
+      if (rc /= 0) call gocean_stop('dispersal_step: ' // dlesm_error_text())
+      rc = dlesm_dispersal_step_set(set%handle, real(h, c_double), int(nsub, c_int), real(kh, c_double), seed, tick, &
+                                    c_null_ptr, int(g%nx, c_int), int(g%ny, c_int), box%xstart, box%xstop, box%ystart, &
+                                    box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, field_device_data(un), &
+                                    field_device_data(vn), c_null_ptr)
+    end associate
+    if (rc /= 0) call gocean_stop('dispersal_step: ' // dlesm_error_text())
+  end subroutine dispersal_step
 
   !> Bring the set into cell order (dlesm_particle_sort_set, DESIGN.md section 6.18): the particles that are ACTIVE and inside
   !! the T internal region of un's grid -- the box drifter_step uses -- come first, in the row-major order of their cells and,

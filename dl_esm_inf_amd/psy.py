@@ -579,6 +579,36 @@ def drifter_step(h, px, py, status, un, vn, nsub=1, stream=None):
         C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
 
 
+def dispersal_step(h, kh, seed, tick, px, py, status, un, vn, nsub=1, ids=None, tick_dev=None, stream=None):
+    """drifter_step with random-walk diffusion (dlesm_dispersal_step_f64): every substep adds a kick,
+    uniform with variance 2 kh |h| per axis (kh: a constant horizontal diffusivity in m2/s), drawn from Philox4x32-10 with
+    the seed as key and (particle id, tick + substep) as counter; a kick that would end on land is rejected.  In place; px, py,
+    status, the grid, the box, the mask and the metrics as drifter_step.  seed: any 64 bits; tick: the substeps taken so far
+    (>= 0) -- the caller advances it by nsub from call to call.  ids: None (the slot number is the identity) or a contiguous
+    int32 CUDA tensor of one identity per particle, to be carried along when the particles are sorted.  tick_dev: None, or a
+    one-element int64 CUDA tensor that the kernel adds to tick and the call advances by nsub on the stream: what a captured
+    time loop needs, for a graph without it replays the same kicks.  Same seed, ids and ticks give the same bytes on any
+    stream and any run.  Asynchronous; nothing is exchanged and the call is not collective."""
+    import torch
+    who = "dispersal_step"
+    n = _drifter_arrays(who, px, py, status)
+    g = un.grid
+    if vn.grid is not g:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
+    if ids is not None and not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and ids.numel() == n):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int32 CUDA tensor of one element per particle" % who)
+    if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
+    seed = int(seed) & 0xffffffffffffffff
+    it = field_bounds(g, GO_T_POINTS)[0]
+    check(_cabi.lib().dlesm_dispersal_step_f64(
+        float(h), int(nsub), float(kh), seed - (1 << 64) if seed >> 63 else seed, int(tick),
+        C.c_void_p(tick_dev.data_ptr()) if tick_dev is not None else None, g.nx, g.ny, it.xstart, it.xstop, it.ystart,
+        it.ystop, g.tmask_device_ptr, C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()),
+        un.device_ptr, vn.device_ptr, n, C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(px.data_ptr()),
+        C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+
+
 def drifter_sample(px, py, status, fields, out=None, stream=None):
     """T-point fields at the particles (dlesm_drifter_sample_f64): for every DRIFTER_ACTIVE particle
     inside the T internal region, out[k][p] = fields[k] in the particle's cell, for 1 to 8 T-point r2d_fields of one grid;

@@ -1331,6 +1331,47 @@ int dlesm_cell_bin_f64(int mode, double alpha, int ld, int ny, int xstart, int x
 int dlesm_cell_bin_set(dlesm_drifters *set, int mode, double alpha, int ld, int ny, int xstart, int xstop, int ystart,
                        int ystop, double *count, void *stream);
 
+/* Drifters with random-walk diffusion: section 6.17's step plus one random kick per substep, for a
+ * constant horizontal diffusivity kh in m2/s -- a cloud released at one place spreads.  The grid, the box, inbox, cell, vel,
+ * the statuses and the arithmetic rules are section 6.17's.  The numbers come from Philox4x32-10 as published (Salmon et al.,
+ * Random123: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds), a counter-based
+ * generator: no state is stored anywhere.  For particle p and substep s = 0..nsub-1 of a call:
+ *     tau = tick + (tick_dev ? *tick_dev : 0) + s                                                   (64-bit)
+ *     w   = philox4x32_10(counter = (id_p, 0, lo32(tau), hi32(tau)), key = (lo32(seed), hi32(seed)))
+ *     rx  = ((double)w[0] + 0.5) * 0x1p-31 - 1.0      ry = ((double)w[1] + 0.5) * 0x1p-31 - 1.0     (exact, in (-1, 1), never 0)
+ *     amp = sqrt((6.0 * kh) * fabs(h))                                          (on the host, once per call; metres)
+ *     gx  = (amp * rx) / dx_t(i,j)                    gy = (amp * ry) / dy_t(i,j)      ((i,j): the cell at the substep's start)
+ * id_p = id[p] taken as 32 bits (any values, duplicates allowed), or (uint32)p when id is NULL.  The kick's variance is
+ * 2 kh |h| per axis.  A substep computes k1, the midpoint and k2 as section 6.17 and, with D = (x + k2x, y + k2y):
+ *     A = (D.x + gx, D.y + gy)
+ *     !inbox(A)        -> (x,y) = A, LEFT, stop
+ *     T(cell(A)) != 0  -> (x,y) = A; OPEN and stop if T < 0
+ *     T(cell(A)) == 0  -> the kick is rejected and D meets section 6.17's rule: !inbox(D) -> (x,y) = D, LEFT, stop;
+ *                         T(cell(D)) == 0 -> GROUNDED, stop (position kept); (x,y) = D; T(cell(D)) < 0 -> OPEN, stop
+ * The entry test and the particles that are not ACTIVE are section 6.17's.  kh == 0 gives dlesm_drifter_step_f64's bits.  One
+ * call with nsub = k at tick t equals k calls with nsub = 1 at ticks t .. t+k-1.  A particle's path depends on its id, not on
+ * its slot: sorting between calls with the ids carried along changes no particle's bits.  In still water nobody is GROUNDED:
+ * a kick onto land is rejected, the no-flux wall.  Same seed, ids and ticks give the same bytes on any stream and any run.
+ * seed: any 64 bits.  tick >= 0 with tick + nsub representable: the caller's count of substeps so far.  tick_dev: NULL, or one
+ * 8-byte-aligned long long on the device whose value the kernel adds to tick; behind the step a one-lane launch on the same
+ * stream does *tick_dev += nsub, so that a captured time loop draws fresh numbers on every replay and equals eager calls with
+ * tick advanced by hand.  A GRAPH CAPTURED WITHOUT tick_dev REPLAYS THE SAME KICKS: tick is baked into it.
+ * Asynchronous on `stream`, no plan, no scratch, no atomics, no allocation, no host synchronisation.  n == 0 or an empty box
+ * launches nothing and returns 0, *tick_dev unchanged.  DLESM_EINVAL before anything is launched: everything
+ * dlesm_drifter_step_f64 refuses, kh negative or not finite, tick < 0 or tick + nsub overflowing, id not 4-byte aligned,
+ * tick_dev not 8-byte aligned, id or tick_dev overlapping px, py or status, tick_dev overlapping an input.
+ * dlesm_dispersal_step_set steps the owner's particles with the set's origin (section 6.18) as id -- before the first sort
+ * since a put that is the identity, NULL --, so a set's particles keep their random streams through
+ * dlesm_particle_sort_set. */
+int dlesm_dispersal_step_f64(double h, int nsub, double kh, long long seed, long long tick, const long long *tick_dev,
+                             int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
+                             const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n,
+                             const int *id, double *px, double *py, int *status, void *stream);
+int dlesm_dispersal_step_set(dlesm_drifters *set, double h, int nsub, double kh, long long seed, long long tick,
+                             const long long *tick_dev, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                             const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
+                             void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
