@@ -26,3 +26,5 @@ from . import psy  # noqa: E402,F401
 from .psy import flow_output, drifter_step, drifter_sample, dispersal_step  # noqa: E402,F401
 from .psy import particle_order, particle_permute, particle_sort  # noqa: E402,F401
 from .psy import cell_bin  # noqa: E402,F401
+from .psy import particle_migrate, particle_pack, particle_unpack, particle_exchange  # noqa: E402,F401
+from .psy import migrate_message, migrate_neighbours, MigrateError  # noqa: E402,F401

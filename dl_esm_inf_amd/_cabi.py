@@ -23,6 +23,10 @@ OUT_SSH, OUT_UT, OUT_VT, OUT_SPEED, OUT_KE, OUT_VORT, OUT_COUNT = range(7)   # D
 OUT_SET, OUT_ADD = 0, 1
 DRIFTER_ACTIVE, DRIFTER_LEFT, DRIFTER_OPEN, DRIFTER_GROUNDED = range(4)      # DLESM_DRIFTER_* (dlesm_drifter_step_f64)
 DRIFTER_MAX_SUB, DRIFTER_MAX_FIELDS = 1024, 8
+DRIFTER_FREE = 4                       # DLESM_DRIFTER_FREE: a slot that holds no particle (dlesm_migrate_f64)
+MIGRATE_MAX_PAYLOAD = 4                # DLESM_MIGRATE_MAX_PAYLOAD
+MIGRATE_W, MIGRATE_E, MIGRATE_S, MIGRATE_N = range(4)   # DLESM_MIGRATE_*: the order of every per-direction array
+MIGRATE_X, MIGRATE_Y = 0, 1
 TRACER_UPWIND, TRACER_MUSCL, TRACER_HANCOCK = 0, 1, 2   # scheme of dlesm_nemolite_coupled_step_dm
 LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
@@ -138,6 +142,19 @@ class FlowCourant(C.Structure):
 
     def __repr__(self):
         return "FlowCourant(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_[:14]) + ")"
+
+
+class MigrateCounts(C.Structure):
+    """dlesm_migrate_counts: what a particle migration did, per direction W, E, S, N"""
+    _fields_ = [("sent", C.c_int * 4), ("held", C.c_int * 4), ("arrived", C.c_int * 4), ("dropped", C.c_int),
+                ("nfree", C.c_int), ("bad_message", C.c_int), ("pad", C.c_int)]
+
+    def as16(self):
+        return tuple(self.sent) + tuple(self.held) + tuple(self.arrived) + (self.dropped, self.nfree, self.bad_message, self.pad)
+
+    def __repr__(self):
+        return "MigrateCounts(sent=%r, held=%r, arrived=%r, dropped=%d, nfree=%d, bad_message=%d)" % (
+            list(self.sent), list(self.held), list(self.arrived), self.dropped, self.nfree, self.bad_message)
 
 
 MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
@@ -311,6 +328,16 @@ PROTOTYPES = {
     "dlesm_cell_bin_f64": (_i, [_i, _d, _i, _i, _i, _i, _i, _i, C.c_longlong] + [_vp] * 4 +
                            [_i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.c_longlong, _vp]),
     "dlesm_cell_bin_set": (_i, [_vp, _i, _d] + [_i] * 6 + [_vp, _vp]),
+    "dlesm_migrate_bytes": (_i, [C.c_longlong, _i, C.POINTER(C.c_longlong)]),
+    "dlesm_migrate_scratch": (_i, [C.c_longlong, C.POINTER(C.c_longlong)]),
+    "dlesm_migrate_work": (_i, [C.c_longlong, C.c_longlong, _i, C.POINTER(C.c_longlong)]),
+    "dlesm_migrate_pack_f64": (_i, [_i] * 5 + [C.c_longlong] + [_vp] * 4 + [C.POINTER(_vp), _i, _pi, _pi, _pi, C.c_longlong,
+                                    C.POINTER(_vp), _vp, _vp, C.c_longlong, _vp]),
+    "dlesm_migrate_unpack_f64": (_i, [_i] * 5 + [C.c_longlong] + [_vp] * 4 + [C.POINTER(_vp), _i, C.c_longlong, C.POINTER(_vp),
+                                      _vp, _vp, C.c_longlong, _vp]),
+    "dlesm_migrate_exchange": (_i, [_pi, C.POINTER(_vp), C.POINTER(_vp), C.c_longlong, _vp]),
+    "dlesm_migrate_f64": (_i, [_i] * 4 + [C.c_longlong] + [_vp] * 4 + [C.POINTER(_vp), _i, _pi, _pi, _pi, C.c_longlong, _vp, _vp,
+                               C.c_longlong, _vp]),
     "dlesm_dispersal_step_f64": (_i, [_d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 5 + [C.c_longlong] +
                                  [_vp] * 5),
     "dlesm_dispersal_step_set": (_i, [_vp, _d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 6),

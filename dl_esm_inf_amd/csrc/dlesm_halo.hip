@@ -2343,6 +2343,63 @@ extern "C" int dlesm_gather_f64(const double *send, double *recv, int n)
     return DLESM_OK;
 }
 
+// The transport of the particle migration: the two messages of one axis to the two neighbours, theirs
+// into recv -- what the low neighbour sent towards its high side lands in recv[0], what the high neighbour sent towards its
+// low side in recv[1].  Mailbox mode: both messages staged through the host and all-gathered over the board, O(ranks x bytes)
+// per rank; RCCL: one grouped send/recv pair per neighbour on the side stream.
+extern "C" int dlesm_migrate_exchange(const int *neighbour, const void *const *send, void *const *recv, long long bytes,
+                                      void *stream)
+{
+    static const char *const who = "dlesm_migrate_exchange";
+    DLESM_REQUIRE(neighbour != nullptr && send != nullptr && recv != nullptr, "%s: null neighbour, send or recv", who);
+    DLESM_REQUIRE(bytes >= 16 && bytes % 8 == 0, "%s: %lld bytes a message (dlesm_migrate_bytes)", who, bytes);
+    const int me = g_size >= 1 ? g_rank : 0, size = g_size >= 1 ? g_size : 1;
+    for (int d = 0; d < 2; d++) {
+        DLESM_REQUIRE(send[d] != nullptr && recv[d] != nullptr, "%s: null send[%d] or recv[%d]", who, d, d);
+        DLESM_REQUIRE((uintptr_t)send[d] % 16 == 0 && (uintptr_t)recv[d] % 16 == 0, "%s: send[%d] or recv[%d] is not 16-byte aligned",
+                      who, d, d);
+        DLESM_REQUIRE(neighbour[d] < size, "%s: neighbour[%d] = %d of %d ranks", who, d, neighbour[d], size);
+        for (int e = 0; e < 2; e++)
+            DLESM_REQUIRE(!nemo::overlap(recv[d], (size_t)bytes, send[e], (size_t)bytes), "%s: recv[%d] overlaps send[%d]", who, d, e);
+    }
+    DLESM_REQUIRE(!nemo::overlap(recv[0], (size_t)bytes, recv[1], (size_t)bytes), "%s: recv[0] and recv[1] overlap", who);
+    DLESM_REQUIRE(neighbour[0] < 0 || neighbour[0] == me || neighbour[0] != neighbour[1],
+                  "%s: rank %d on both sides (periodic boundaries between different ranks are left out)", who, neighbour[0]);
+    if (int rc = ensure_device()) return rc;
+    DLESM_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    hipStream_t s = side_stream();
+    const size_t nb = (size_t)bytes;
+    for (int d = 0; d < 2; d++) {
+        if (neighbour[d] < 0) DLESM_HIP_TRY(hipMemsetAsync(recv[d], 0, 16, s));                        // a count of 0
+        else if (neighbour[d] == me) DLESM_HIP_TRY(hipMemcpyAsync(recv[1 - d], send[d], nb, hipMemcpyDeviceToDevice, s));
+    }
+    if (size > 1 && g_mailbox) {
+        std::vector<char> mine(2 * nb), all((size_t)size * 2 * nb);
+        for (int d = 0; d < 2; d++)
+            if (neighbour[d] >= 0 && neighbour[d] != me)
+                DLESM_HIP_TRY(hipMemcpyAsync(mine.data() + d * nb, send[d], nb, hipMemcpyDeviceToHost, s));
+        DLESM_HIP_TRY(hipStreamSynchronize(s));
+        if (int rc = dlesm_board_allgather(mine.data(), 2 * nb, all.data())) return rc;
+        for (int d = 0; d < 2; d++)
+            if (neighbour[d] >= 0 && neighbour[d] != me)
+                DLESM_HIP_TRY(hipMemcpyAsync(recv[d], all.data() + ((size_t)neighbour[d] * 2 + (1 - d)) * nb, nb,
+                                             hipMemcpyHostToDevice, s));
+        DLESM_HIP_TRY(hipStreamSynchronize(s));          // `all` is pageable: the copies have left it
+    } else if (size > 1) {
+        DLESM_REQUIRE(g_comm != nullptr, "%s before dlesm_comm_init", who);
+        DLESM_NCCL_TRY(ncclGroupStart());
+        ncclResult_t err = ncclSuccess;
+        for (int d = 0; d < 2; d++)
+            if (neighbour[d] >= 0 && neighbour[d] != me) {
+                DLESM_NCCL_IN_GROUP(err, ncclSend(send[d], nb, ncclChar, neighbour[d], g_comm, s));
+                DLESM_NCCL_IN_GROUP(err, ncclRecv(recv[d], nb, ncclChar, neighbour[d], g_comm, s));
+            }
+        if (int rc = group_end(err, "particle exchange (ncclSend/ncclRecv)")) return rc;
+    }
+    DLESM_HIP_TRY(hipStreamSynchronize(s));
+    return DLESM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Device-side gather / scatter of whole fields (field_mod.f90:1313-1390, 378-389)
 

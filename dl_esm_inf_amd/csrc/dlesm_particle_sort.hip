@@ -25,14 +25,11 @@ namespace {
 
 using namespace nemo;
 
-constexpr int SORT_BLOCK = 256;            // four waves
+#include "dlesm_scan.h"                      // SORT_BLOCK, SORT_KERNEL, block_scan and the three scan kernels
+
 constexpr int SORT_TILE = 4096;            // keys of one block, in every kernel of a pass
-constexpr int SCAN_ITEMS = 8;              // table entries of one lane of the scan
-constexpr int SCAN_TILE = SORT_BLOCK * SCAN_ITEMS;
 constexpr long long SORT_MAX_N = 0x7fffffffLL;
 constexpr int PERMUTE_MAX = 8;
-
-#define SORT_KERNEL __global__ __launch_bounds__(SORT_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
 // ---- pieces
 
@@ -48,28 +45,6 @@ __device__ __forceinline__ void hist_add(unsigned *hist, unsigned d, bool valid)
     } else if (valid) {
         atomicAdd(&hist[d], 1u);
     }
-}
-
-// exclusive scan of one value per thread over the block; wtot: four words of LDS, free again on return
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned *wtot, unsigned &total)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o);
-        if (lane >= (unsigned)o) inc += up;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-    for (unsigned w = 0; w < SORT_BLOCK / 64; w++) {
-        const unsigned c = wtot[w];
-        before += w < wave ? c : 0;
-        total += c;
-    }
-    __syncthreads();
-    return before + inc - v;
 }
 
 // ---- keys
@@ -151,61 +126,6 @@ SORT_KERNEL sort_hist_k(const unsigned *keys, unsigned *table, long long n, unsi
     }
     __syncthreads();
     table[(size_t)t * nblocks + blockIdx.x] = hist[t];
-}
-
-// the table has m = 256 * nblocks entries, a multiple of SCAN_ITEMS, and starts 16-byte aligned: a lane's eight entries are
-// all there or none is
-__device__ __forceinline__ bool scan_load(const unsigned *table, unsigned m, unsigned (&v)[SCAN_ITEMS], unsigned &at)
-{
-    at = (blockIdx.x * SORT_BLOCK + threadIdx.x) * SCAN_ITEMS;
-    const bool mine = at < m;
-    for (int k = 0; k < SCAN_ITEMS; k += 4) {
-        const uint4 q = mine ? *(const uint4 *)(table + at + k) : make_uint4(0, 0, 0, 0);
-        v[k] = q.x, v[k + 1] = q.y, v[k + 2] = q.z, v[k + 3] = q.w;
-    }
-    return mine;
-}
-
-SORT_KERNEL scan_reduce_k(const unsigned *table, unsigned m, unsigned *sums)
-{
-    __shared__ unsigned wtot[SORT_BLOCK / 64];
-    unsigned v[SCAN_ITEMS], at, s = 0, total;
-    (void)scan_load(table, m, v, at);
-    for (int k = 0; k < SCAN_ITEMS; k++) s += v[k];
-    (void)block_scan(s, wtot, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one block: the exclusive scan of the scan blocks' sums, in place
-SORT_KERNEL scan_top_k(unsigned *sums, unsigned nscan)
-{
-    __shared__ unsigned wtot[SORT_BLOCK / 64];
-    unsigned carry = 0;
-    for (unsigned b0 = 0; b0 < nscan; b0 += SORT_BLOCK) {
-        const unsigned b = b0 + threadIdx.x;
-        const unsigned v = b < nscan ? sums[b] : 0u;
-        unsigned total;
-        const unsigned ex = block_scan(v, wtot, total);
-        if (b < nscan) sums[b] = carry + ex;
-        carry += total;
-    }
-}
-
-// sums == nullptr: the table is one scan block
-SORT_KERNEL scan_down_k(unsigned *table, unsigned m, const unsigned *sums)
-{
-    __shared__ unsigned wtot[SORT_BLOCK / 64];
-    unsigned v[SCAN_ITEMS], at, s = 0, total;
-    const bool mine = scan_load(table, m, v, at);
-    for (int k = 0; k < SCAN_ITEMS; k++) s += v[k];
-    unsigned run = block_scan(s, wtot, total) + (sums ? sums[blockIdx.x] : 0u);
-    if (!mine) return;
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        const unsigned c = v[k];
-        v[k] = run;
-        run += c;
-    }
-    for (int k = 0; k < SCAN_ITEMS; k += 4) *(uint4 *)(table + at + k) = make_uint4(v[k], v[k + 1], v[k + 2], v[k + 3]);
 }
 
 struct ScatterArgs {
@@ -382,12 +302,7 @@ int launch_order(int xstart, int xstop, int ystart, int ystop, long long n, long
         const bool last = pass == passes - 1;
         const unsigned *const kin = keys[pass & 1];
         if (pass > 0) hipLaunchKernelGGL(sort_hist_k, grid, block, 0, s, kin, table, n, plan.nblocks, 8 * pass);
-        if (plan.nscan > 1) {
-            hipLaunchKernelGGL(scan_reduce_k, dim3(plan.nscan), block, 0, s, (const unsigned *)table, plan.m, sums);
-            hipLaunchKernelGGL(scan_top_k, dim3(1), block, 0, s, sums, plan.nscan);
-        }
-        hipLaunchKernelGGL(scan_down_k, dim3(plan.nscan), block, 0, s, table, plan.m,
-                           plan.nscan > 1 ? (const unsigned *)sums : (const unsigned *)nullptr);
+        launch_scan(table, plan.m, plan.nscan, sums, s);
         // pass k writes perm when an even number of passes follow it, so that the last one does
         const int out = (passes - 1 - pass) & 1;
         const ScatterArgs sa{kin, pass == 0 ? nullptr : vals[out ^ 1], last ? nullptr : keys[(pass & 1) ^ 1], vals[out],

@@ -87,7 +87,7 @@ module dlesm_hip_mod
      type(c_ptr) :: handle = c_null_ptr
   end type drifters_type
   integer(c_int), parameter :: DLESM_DRIFTER_ACTIVE = 0, DLESM_DRIFTER_LEFT = 1, DLESM_DRIFTER_OPEN = 2, &
-                               DLESM_DRIFTER_GROUNDED = 3
+                               DLESM_DRIFTER_GROUNDED = 3, DLESM_DRIFTER_FREE = 4
 
   interface
      ! ---- host-side index maps -------------------------------------------

@@ -65,7 +65,7 @@ module dlesm_psy_mod
   public :: particle_sort, particle_origin
   public :: dispersal_step
   public :: cell_bin
-  public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED
+  public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED, DLESM_DRIFTER_FREE
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
   public :: shallow_params, c_sw_params, device_sync, grid_to_device
   public :: invoke_compute_cu, invoke_compute_cv, invoke_compute_z, invoke_compute_h

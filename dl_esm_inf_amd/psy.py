@@ -758,6 +758,155 @@ def cell_bin(px, py, status, grid, weights=(None,), out=None, perm=None, mode=_c
     return out, unordered
 
 
+def _migrate_arrays(who, px, py, status, ids, payload):
+    import torch
+    n = _drifter_arrays(who, px, py, status)
+    payload = list(payload)
+    if not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.numel() == n):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int64 CUDA tensor of one element per slot" % who)
+    if len(payload) > _cabi.MIGRATE_MAX_PAYLOAD or any(
+            not (a.is_cuda and a.is_contiguous() and a.element_size() == 8 and a.numel() == n) for a in payload):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: at most %d payload arrays, contiguous CUDA tensors of one 8-byte element "
+                               "per slot" % (who, _cabi.MIGRATE_MAX_PAYLOAD))
+    k = len(payload)
+    return n, k, (C.c_void_p * max(k, 1))(*[a.data_ptr() for a in payload])
+
+
+def _box_of(grid_or_field):
+    grid = getattr(grid_or_field, "grid", grid_or_field)
+    it = field_bounds(grid, GO_T_POINTS)[0]
+    return grid, (it.xstart, it.xstop, it.ystart, it.ystop)
+
+
+def migrate_message(cap, npayload=0, device="cuda"):
+    """a message buffer of the particle migration for `cap` records with npayload payload words
+    each: a uint8 CUDA tensor of dlesm_migrate_bytes bytes whose count is 0"""
+    import torch
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_migrate_bytes(int(cap), int(npayload), C.byref(need)))
+    m = torch.empty(need.value, dtype=torch.uint8, device=device)
+    m[:16] = 0
+    return m
+
+
+def _migrate_scratch(n, device, scratch):
+    import torch
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_migrate_scratch(n, C.byref(need)))
+    if scratch is None:
+        scratch = torch.empty(max(need.value, 16), dtype=torch.uint8, device=device)
+    return scratch, scratch.numel()
+
+
+def particle_pack(axis, px, py, status, ids, box, has_neighbour, shift_x, shift_y, cap, send, counts, payload=(), scratch=None,
+                  stream=None):
+    """the departures of one axis compacted into its two messages (dlesm_migrate_pack_f64).  axis:
+    _cabi.MIGRATE_X (W, E) or MIGRATE_Y (S, N); box: (xstart, xstop, ystart, ystop); has_neighbour, shift_x, shift_y: two
+    numbers each, low side first; send: two uint8 CUDA tensors of migrate_message's size; counts: an int32 CUDA tensor of 16
+    elements, the dlesm_migrate_counts record.  status is the only particle array written.  Asynchronous."""
+    who = "particle_pack"
+    n, k, pp = _migrate_arrays(who, px, py, status, ids, payload)
+    with _on(stream):
+        scratch, nb = _migrate_scratch(n, px.device, scratch)
+        check(_cabi.lib().dlesm_migrate_pack_f64(
+            int(axis), *[int(b) for b in box], n, C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()),
+            C.c_void_p(status.data_ptr()), C.c_void_p(ids.data_ptr()), pp, k, (C.c_int * 2)(*[int(bool(h)) for h in has_neighbour]),
+            (C.c_int * 2)(*[int(v) for v in shift_x]), (C.c_int * 2)(*[int(v) for v in shift_y]), int(cap),
+            (C.c_void_p * 2)(*[m.data_ptr() for m in send]), C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr()), nb,
+            _stream_ptr(stream)))
+
+
+def particle_unpack(axis, px, py, status, ids, box, cap, recv, counts, payload=(), scratch=None, stream=None):
+    """the arrivals of one axis filled into the FREE slots (dlesm_migrate_unpack_f64): the records of
+    recv[0] (from the low side), then those of recv[1], into the FREE slots in ascending order; arguments as particle_pack.
+    Asynchronous."""
+    who = "particle_unpack"
+    n, k, pp = _migrate_arrays(who, px, py, status, ids, payload)
+    with _on(stream):
+        scratch, nb = _migrate_scratch(n, px.device, scratch)
+        check(_cabi.lib().dlesm_migrate_unpack_f64(
+            int(axis), *[int(b) for b in box], n, C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()),
+            C.c_void_p(status.data_ptr()), C.c_void_p(ids.data_ptr()), pp, k, int(cap),
+            (C.c_void_p * 2)(*[m.data_ptr() for m in recv]), C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr()), nb,
+            _stream_ptr(stream)))
+
+
+def particle_exchange(neighbour, send, recv, stream=None):
+    """the transport of one axis (dlesm_migrate_exchange): send[d] to the 0-based rank neighbour[d],
+    recv[d] from it; a negative neighbour gives an empty recv[d], the caller's own rank a device copy of send[d] into
+    recv[1 - d].  Collective and synchronous, after waiting for the stream."""
+    nb = send[0].numel()
+    if any(m.numel() != nb or not m.is_cuda or not m.is_contiguous() for m in list(send) + list(recv)):
+        raise _cabi.DlesmError(_cabi.EINVAL, "particle_exchange: four contiguous CUDA message buffers of one size")
+    check(_cabi.lib().dlesm_migrate_exchange(
+        (C.c_int * 2)(*[int(r) for r in neighbour]), (C.c_void_p * 2)(*[m.data_ptr() for m in send]),
+        (C.c_void_p * 2)(*[m.data_ptr() for m in recv]), nb, _stream_ptr(stream)))
+
+
+def migrate_neighbours(grid):
+    """(neighbour, shift_x, shift_y) of this rank's tile for particle_migrate, each in the order W, E, S, N: the 0-based rank
+    on that side from map_comms' send tables (-1: the edge of the global domain), and the integer a local coordinate gains
+    on its way there: (my glob.xstart - my internal.xstart) - (the neighbour's), likewise in y."""
+    # the edge strips' direction codes DLESM_IPLUS, _IMINUS, _JPLUS, _JMINUS: sent to the W, E, S and N neighbour
+    side = {1: _cabi.MIGRATE_W, 2: _cabi.MIGRATE_E, 3: _cabi.MIGRATE_S, 4: _cabi.MIGRATE_N}
+    neighbour, shift_x, shift_y = [-1] * 4, [0] * 4, [0] * 4
+    tables = getattr(grid, "comm_tables", None)
+    if grid.decomp is None or tables is None:
+        return neighbour, shift_x, shift_y
+    subs = grid.decomp.subdomains
+    me = subs[parallel_mod.get_rank() - 1]
+    for s in tables.sends():
+        d = side.get(s["dir"])
+        if d is None:
+            continue
+        o = subs[s["dest"]]
+        neighbour[d] = s["dest"]
+        shift_x[d] = (me.glob.xstart - me.internal.xstart) - (o.glob.xstart - o.internal.xstart)
+        shift_y[d] = (me.glob.ystart - me.internal.ystart) - (o.glob.ystart - o.internal.ystart)
+    return neighbour, shift_x, shift_y
+
+
+class MigrateError(_cabi.DlesmError):
+    """particle_migrate lost particles (dropped) or met a bad message; .counts holds the record"""
+
+
+def particle_migrate(px, py, status, ids, grid_or_field, payload=(), cap=None, work=None, stream=None):
+    """hand the particles that have left this rank's tile to the neighbouring ranks and take theirs (dlesm_migrate_f64,
+    DESIGN.md section 6.21): phase X (W, E), then phase Y (S, N), so a corner crossing arrives within the call.  px, py,
+    status as drifter_step, of the set's capacity n, slots without a particle DRIFTER_FREE; ids: a contiguous int64 CUDA tensor,
+    the identity that travels with a particle (dispersal_step takes its low 32 bits); payload: up to 4 contiguous CUDA tensors
+    of one 8-byte element per slot that travel too.  The box is the T internal region of the grid, the neighbours and shifts
+    are migrate_neighbours(grid).  cap: the records one message holds (the same on every rank; default min(n, 65536), at
+    least 1); departures beyond it stay LEFT and go with a later call.  work: a uint8 CUDA tensor of dlesm_migrate_work bytes
+    to reuse, or None.  Returns the _cabi.MigrateCounts record after the call; raises MigrateError if particles were dropped
+    for want of FREE slots or a message was bad.  A particle that crosses loses the rest of the substeps of the step that
+    made it LEFT: step with nsub = 1 between migrations for no lag.  Collective and synchronous."""
+    import torch
+    who = "particle_migrate"
+    n, k, pp = _migrate_arrays(who, px, py, status, ids, payload)
+    grid, box = _box_of(grid_or_field)
+    cap = max(1, min(n, 65536)) if cap is None else int(cap)
+    neighbour, shift_x, shift_y = migrate_neighbours(grid)
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_migrate_work(n, cap, k, C.byref(need)))
+    with _on(stream):
+        if work is None:
+            work = torch.empty(need.value, dtype=torch.uint8, device=px.device)
+        counts = torch.empty(16, dtype=torch.int32, device=px.device)
+        check(_cabi.lib().dlesm_migrate_f64(
+            *box, n, C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(ids.data_ptr()), pp, k, (C.c_int * 4)(*neighbour), (C.c_int * 4)(*shift_x), (C.c_int * 4)(*shift_y), cap,
+            C.c_void_p(counts.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(), _stream_ptr(stream)))
+        host = counts.cpu().numpy()
+    rec = _cabi.MigrateCounts.from_buffer_copy(host.tobytes())
+    if rec.dropped or rec.bad_message:
+        e = MigrateError(_cabi.EINVAL, "%s: %d arrivals dropped for want of FREE slots, bad_message = %d" %
+                         (who, rec.dropped, rec.bad_message))
+        e.counts = rec
+        raise e
+    return rec
+
+
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
 
 

@@ -1372,6 +1372,81 @@ int dlesm_dispersal_step_set(dlesm_drifters *set, double h, int nsub, double kh,
                              const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
                              void *stream);
 
+/* Particles that cross rank boundaries: on a decomposed grid a particle that leaves its tile is handed
+ * to the neighbouring rank on the device, without a host copy of px, py or status.  A particle set is arrays of a fixed length n,
+ * the capacity; a slot whose status is DLESM_DRIFTER_FREE holds no particle (every entry of sections 6.17-6.20 treats it as
+ * dead, like any status other than ACTIVE).  A departure frees its slot, an arrival takes a FREE one.  With a particle travel
+ * `long long id[n]` -- so that section 6.20's random streams follow it -- and npayload (0..DLESM_MIGRATE_MAX_PAYLOAD) further
+ * arrays of one 8-byte word per slot, moved as raw bits.  The box and inbox are section 6.17's, evaluated in double before any
+ * conversion.  Directions: W, E, S, N = 0..3; axis DLESM_MIGRATE_X serves W and E (d = 0, 1), DLESM_MIGRATE_Y S and N.
+ * A MESSAGE of capacity cap is one contiguous device buffer, 16-byte aligned: `long long count`, 8 bytes of padding, then
+ * x[cap] | y[cap] | id[cap] | payload_0[cap] | ...; dlesm_migrate_bytes gives its size, 16 + (3 + npayload) * 8 * cap.  Words past
+ * count, and the padding, are never written by pack.
+ * dlesm_migrate_pack_f64, axis X: slot p is a W departure if status[p] == LEFT, px[p] and py[p] are finite, px[p] < xstart and
+ * has_neighbour[0] != 0; an E departure if instead px[p] >= xstop + 1 and has_neighbour[1] != 0.  Axis Y: xstart <= px[p] <
+ * xstop + 1 is required too, then S if py[p] < ystart and has_neighbour[0], N if py[p] >= ystop + 1 and has_neighbour[1].  The
+ * k-th departure of direction d in ascending slot order, k < cap: send[d] gets x = px[p] + (double)shift_x[d], y = py[p] +
+ * (double)shift_y[d] (one rounded add each), id[p] and the payload words at index k, and status[p] becomes FREE.  k >= cap: the
+ * particle is HELD, nothing changes, a later call retries it.  count = min(departures, cap).  Everything else stays as it is: a
+ * LEFT particle at the edge of the global domain (no neighbour), one with a NaN or an infinite position, one outside in x on
+ * a side without neighbour while outside in y.  px, py, id and the payload are only read.
+ * dlesm_migrate_unpack_f64: the arrivals are the records 0..count-1 of recv[0] (from the low side: W or S), then those of
+ * recv[1]; arrival j goes into the j-th FREE slot in ascending slot order: px, py, id and the payload are stored and status
+ * becomes inbox(x, y) ? ACTIVE : LEFT (so phase Y forwards a corner crossing, a later call a jump longer than a tile; an
+ * arrival on land or an open cell is classified by the next step's entry test).  Arrivals beyond the FREE slots are DROPPED
+ * and counted.  A header count outside 0..cap counts as 0 and sets bit (1 << direction) of bad_message: a bad message cannot
+ * fault.  Unpack after pack of the same axis reuses the slots that pack has freed.
+ * The record, on the device: pack stores sent[] and held[] of its two directions; unpack stores arrived[] of its two (by the
+ * side they came from), nfree (the FREE slots after it) and -- axis X: sets, axis Y: adds to / ors into -- dropped and
+ * bad_message.  After pack X, unpack X, pack Y, unpack Y every word is defined.
+ * scratch: device memory, 16-byte aligned, of at least the bytes dlesm_migrate_scratch gives for n (it needs no device, nor do
+ * dlesm_migrate_bytes and dlesm_migrate_work).  payload, send, recv, has_neighbour, shift_x and shift_y are HOST arrays, passed
+ * to the kernels by value.  Both calls are asynchronous on `stream`, allocate nothing, do not synchronise, use no global
+ * atomics and may be captured into a graph: count, scan, scatter over 4096-slot tiles, hand-written kernels.
+ * dlesm_migrate_exchange, the transport: send[d] travels to rank neighbour[d] (0-based), recv[d] receives what that rank sent
+ * towards this one.  neighbour[d] < 0: recv[d]'s count becomes 0.  neighbour[d] == the caller's rank (0 without a
+ * communicator): send[d] is copied into recv[1 - d] on the device -- one rank whose W and E neighbour is itself, with shifts
+ * +nxb and -nxb, is a periodic channel.  Collective and synchronous, after waiting for `stream`; every rank passes the same
+ * bytes.  Mailbox mode stages both messages through the host and the board, O(ranks x bytes) per rank; RCCL sends and receives
+ * one grouped pair per neighbour.  The same other rank on both sides is refused.
+ * dlesm_migrate_f64: pack X, exchange, unpack X, pack Y, exchange, unpack Y -- a particle that leaves through a corner makes
+ * both hops in one call.  neighbour[4] (< 0: none), shift_x[4], shift_y[4] in the order W, E, S, N; work: device memory, 16-byte
+ * aligned, of dlesm_migrate_work(n, cap, npayload) bytes, holding the eight messages and the scratch.  Collective, synchronous.
+ * A particle that crosses loses the rest of the substeps of the step that made it LEFT: step with nsub = 1 for no lag.
+ * DLESM_EINVAL before anything is launched: a null pointer, px, py, id or a payload not 8-byte aligned, status or counts not
+ * 4-byte aligned, a message, scratch or work not 16-byte aligned, n outside 0..2^31-1, cap outside 1..2^31-1, npayload outside
+ * 0..4, an axis other than 0 or 1, xstop < xstart - 1, ystop < ystart - 1, scratch_bytes or work_bytes too small, an array that
+ * is written overlapping any other array.  DLESM_ENODEV without a device. */
+enum { DLESM_DRIFTER_FREE = 4 };        /* follows DLESM_DRIFTER_GROUNDED */
+enum { DLESM_MIGRATE_MAX_PAYLOAD = 4 };
+enum { DLESM_MIGRATE_W = 0, DLESM_MIGRATE_E, DLESM_MIGRATE_S, DLESM_MIGRATE_N };
+enum { DLESM_MIGRATE_X = 0, DLESM_MIGRATE_Y = 1 };
+typedef struct dlesm_migrate_counts {
+    int sent[4];
+    int held[4];
+    int arrived[4];
+    int dropped;
+    int nfree;
+    int bad_message;
+    int pad;
+} dlesm_migrate_counts;                 /* 64 bytes, no holes */
+int dlesm_migrate_bytes(long long cap, int npayload, long long *bytes);
+int dlesm_migrate_scratch(long long n, long long *bytes);
+int dlesm_migrate_work(long long n, long long cap, int npayload, long long *bytes);
+int dlesm_migrate_pack_f64(int axis, int xstart, int xstop, int ystart, int ystop, long long n, const double *px,
+                           const double *py, int *status, const long long *id, const void *const *payload, int npayload,
+                           const int *has_neighbour, const int *shift_x, const int *shift_y, long long cap, void *const *send,
+                           dlesm_migrate_counts *counts, void *scratch, long long scratch_bytes, void *stream);
+int dlesm_migrate_unpack_f64(int axis, int xstart, int xstop, int ystart, int ystop, long long n, double *px, double *py,
+                             int *status, long long *id, void *const *payload, int npayload, long long cap,
+                             const void *const *recv, dlesm_migrate_counts *counts, void *scratch, long long scratch_bytes,
+                             void *stream);
+int dlesm_migrate_exchange(const int *neighbour, const void *const *send, void *const *recv, long long bytes, void *stream);
+int dlesm_migrate_f64(int xstart, int xstop, int ystart, int ystop, long long n, double *px, double *py, int *status,
+                      long long *id, void *const *payload, int npayload, const int *neighbour, const int *shift_x,
+                      const int *shift_y, long long cap, dlesm_migrate_counts *counts, void *work, long long work_bytes,
+                      void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
