@@ -23,7 +23,7 @@ from .grid_mod import (grid_type, grid_init, GO_ARAKAWA_C, GO_ARAKAWA_B, GO_OFFS
 from .field_mod import (r2d_field, field_checksum, field_stats, field_locate, copy_field, set_field, free_field,  # noqa: E402,F401
                         GO_U_POINTS, GO_V_POINTS, GO_T_POINTS, GO_F_POINTS, GO_ALL_POINTS)
 from . import psy  # noqa: E402,F401
-from .psy import flow_output, drifter_step, drifter_sample, dispersal_step  # noqa: E402,F401
+from .psy import flow_output, drifter_step, drifter_sample, dispersal_step, random_walk  # noqa: E402,F401
 from .psy import particle_order, particle_permute, particle_sort  # noqa: E402,F401
 from .psy import cell_bin  # noqa: E402,F401
 from .psy import particle_migrate, particle_pack, particle_unpack, particle_exchange  # noqa: E402,F401

@@ -341,6 +341,9 @@ PROTOTYPES = {
     "dlesm_dispersal_step_f64": (_i, [_d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 5 + [C.c_longlong] +
                                  [_vp] * 5),
     "dlesm_dispersal_step_set": (_i, [_vp, _d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 6),
+    "dlesm_random_walk_f64": (_i, [_d, _i, _vp, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 5 + [C.c_longlong] +
+                              [_vp] * 5),
+    "dlesm_random_walk_set": (_i, [_vp, _d, _i, _vp, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 6),
     "dlesm_nemolite_coupled_step_dm": (_i, [_vp, _vp, _i, C.POINTER(MomentumParams), C.POINTER(MomentumGrid), _vp, _i, _i,
                                             C.POINTER(Region), C.POINTER(Region), C.POINTER(Region), _vp, _d] + [_vp] * 13 +
                                        [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),

@@ -74,24 +74,14 @@ __global__ __launch_bounds__(64) void tick_bump_k(long long *tick_dev, int nsub)
 
 } // namespace
 
-} // namespace dlesm
-
-using namespace dlesm;
-
-extern "C" int dlesm_dispersal_step_f64(double h, int nsub, double kh, long long seed, long long tick, const long long *tick_dev,
-                                        int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
-                                        const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n,
-                                        const int *id, double *px, double *py, int *status, void *stream)
+// what a step that draws random numbers refuses beyond lagrangian_step_checks (dlesm_random_walk.hip makes these checks too):
+// the rules of tick, id and tick_dev
+int random_stream_checks(const char *who, int nsub, long long tick, const long long *tick_dev, int ld, int ny, const int *tmask,
+                         const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n, const int *id,
+                         const double *px, const double *py, const int *status)
 {
-    static const char *const who = "dlesm_dispersal_step_f64";
     static const char *const p_name[3] = {"px", "py", "status"};
     static const char *const in_name[5] = {"tmask", "dx_t", "dy_t", "un", "vn"};
-    if (int rc = ensure_device()) return rc;
-    bool nothing;
-    if (int rc = lagrangian_step_checks(who, h, nsub, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, n, px, py,
-                                        status, &nothing))
-        return rc;
-    DLESM_REQUIRE(std::isfinite(kh) && kh >= 0.0, "%s: kh = %g (a finite diffusivity >= 0 in m2/s)", who, kh);
     DLESM_REQUIRE(tick >= 0 && tick <= LLONG_MAX - nsub, "%s: tick = %lld (>= 0, tick + nsub representable)", who, tick);
     DLESM_REQUIRE((uintptr_t)id % 4 == 0, "%s: id is not 4-byte aligned", who);
     DLESM_REQUIRE((uintptr_t)tick_dev % 8 == 0, "%s: tick_dev is not 8-byte aligned", who);
@@ -109,6 +99,34 @@ extern "C" int dlesm_dispersal_step_f64(double h, int nsub, double kh, long long
                           in_name[m]);
         DLESM_REQUIRE(!id || !overlap(tick_dev, 8, id, (size_t)n * 4), "%s: tick_dev overlaps the input id", who);
     }
+    return DLESM_OK;
+}
+
+// *tick_dev += nsub behind whatever stands on the stream
+int launch_tick_bump(const long long *tick_dev, int nsub, hipStream_t stream)
+{
+    hipLaunchKernelGGL(tick_bump_k, dim3(1), dim3(64), 0, stream, const_cast<long long *>(tick_dev), nsub);
+    DLESM_HIP_TRY(hipGetLastError());
+    return DLESM_OK;
+}
+
+} // namespace dlesm
+
+using namespace dlesm;
+
+extern "C" int dlesm_dispersal_step_f64(double h, int nsub, double kh, long long seed, long long tick, const long long *tick_dev,
+                                        int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
+                                        const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n,
+                                        const int *id, double *px, double *py, int *status, void *stream)
+{
+    static const char *const who = "dlesm_dispersal_step_f64";
+    if (int rc = ensure_device()) return rc;
+    bool nothing;
+    if (int rc = lagrangian_step_checks(who, h, nsub, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, dy_t, un, vn, n, px, py,
+                                        status, &nothing))
+        return rc;
+    DLESM_REQUIRE(std::isfinite(kh) && kh >= 0.0, "%s: kh = %g (a finite diffusivity >= 0 in m2/s)", who, kh);
+    if (int rc = random_stream_checks(who, nsub, tick, tick_dev, ld, ny, tmask, dx_t, dy_t, un, vn, n, id, px, py, status)) return rc;
     if (nothing) return DLESM_OK;
 
     const DispersalArgs a{DrifterFlow{tmask, dx_t, dy_t, un, vn, ld}, id, tick_dev, px, py, status, n,
@@ -117,11 +135,7 @@ extern "C" int dlesm_dispersal_step_f64(double h, int nsub, double kh, long long
                           (unsigned)((unsigned long long)seed >> 32), nsub};
     hipLaunchKernelGGL(dispersal_step_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     DLESM_HIP_TRY(hipGetLastError());
-    if (tick_dev) {
-        hipLaunchKernelGGL(tick_bump_k, dim3(1), dim3(64), 0, (hipStream_t)stream, const_cast<long long *>(tick_dev), nsub);
-        DLESM_HIP_TRY(hipGetLastError());
-    }
-    return DLESM_OK;
+    return tick_dev ? launch_tick_bump(tick_dev, nsub, (hipStream_t)stream) : DLESM_OK;
 }
 
 extern "C" int dlesm_dispersal_step_set(dlesm_drifters *set, double h, int nsub, double kh, long long seed, long long tick,

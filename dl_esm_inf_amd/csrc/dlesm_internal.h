@@ -342,6 +342,12 @@ int check_box(const char *who, int ld, int ny, int xstart, int xstop, int ystart
 int lagrangian_step_checks(const char *who, double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
                            const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
                            long long n, const double *px, const double *py, const int *status, bool *nothing);
+// the rules of tick, id and tick_dev for a step that draws random numbers, and *tick_dev += nsub on the stream
+// (dlesm_dispersal.hip; dlesm_random_walk.hip uses both)
+int random_stream_checks(const char *who, int nsub, long long tick, const long long *tick_dev, int ld, int ny, const int *tmask,
+                         const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n, const int *id,
+                         const double *px, const double *py, const int *status);
+int launch_tick_bump(const long long *tick_dev, int nsub, hipStream_t stream);
 // two shallow-water steps per launch (dlesm_shallow_x2.hip): the overlap check of the twelve arrays, and the distributed form's
 // wave-tile conditions and launch (stage 1 computed on the box grown by gw..gn; see shallow_tile_x2_grown)
 int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny);

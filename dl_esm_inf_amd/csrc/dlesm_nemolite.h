@@ -310,21 +310,16 @@ __device__ __forceinline__ DrifterMove dispersal_kick(double amp, unsigned id, u
 }
 // pin_here (dlesm_internal.h) for an int: a load behind it cannot be sunk into a lane-varying branch
 __device__ __forceinline__ int pin_here(int x) { return __builtin_amdgcn_mov_dpp(x, 0xE4, 0xf, 0xf, true); }
-// One substep with a kick: k1, the midpoint and k2 as drifter_substep, D = (x, y) + k2, A = D + kick() / the metrics of the
-// substep's own cell (stage 1's, already loaded).  A in the box and not on land is taken; a kick that ends on land is
-// rejected -- the no-flux wall -- and D meets drifter_substep's destination rule.  T(cell(A)) and T(cell(D)) are loaded
-// together and unconditionally, a point outside the box at the particle's own cell and then not used: three dependent round
-// trips as drifter_substep, and whichever destination is taken supplies the next substep's own-cell mask.  kick() is called
-// behind the stage-1 loads and before their first use: its integer work sits under their latency.
-template <class CF, class TF, class KF>
-__device__ __forceinline__ int dispersal_substep(double h, const DrifterBox &box, double &x, double &y, int &i, int &j, CF cell,
-                                                 TF mask, KF kick)
+// The move of a substep with a kick, stage 1 done: k1 of the substep's own cell and the kick (gx, gy) in cells are given.
+// The midpoint and k2 as drifter_substep, D = (x, y) + k2, A = D + (gx, gy).  A in the box and not on land is taken; a kick
+// that ends on land is rejected -- the no-flux wall -- and D meets drifter_substep's destination rule.  T(cell(A)) and
+// T(cell(D)) are loaded together and unconditionally, a point outside the box at the particle's own cell and then not used:
+// three dependent round trips as drifter_substep, and whichever destination is taken supplies the next substep's own-cell
+// mask.
+template <class CF, class TF>
+__device__ __forceinline__ int kicked_move(double h, const DrifterBox &box, double &x, double &y, int &i, int &j,
+                                           const DrifterMove k1, double gx, double gy, CF cell, TF mask)
 {
-    const DrifterCell c1 = cell(i, j);
-    const DrifterMove g = kick();
-    __builtin_amdgcn_sched_barrier(0);            // the scheduler would otherwise put the generator behind the loads' first use
-    const DrifterMove k1 = drifter_vel(h, x, y, i, j, c1);
-    const double gx = g.kx / c1.dx, gy = g.ky / c1.dy;
     const double xm = x + 0.5 * k1.kx, ym = y + 0.5 * k1.ky;
     const bool in_m = box.has(xm, ym);
     const double xe = in_m ? xm : x, ye = in_m ? ym : y;
@@ -339,7 +334,9 @@ __device__ __forceinline__ int dispersal_substep(double h, const DrifterBox &box
     const int ia = (int)floor(in_a ? xa : x), ja = (int)floor(in_a ? ya : y);
     const int id = (int)floor(in_d ? xd : x), jd = (int)floor(in_d ? yd : y);
     // pinned: left alone, the compiler sinks each load into the branch that uses it, a fourth round trip for a rejected kick
-    const int ta = pin_here(mask(ia, ja)), td = pin_here(mask(id, jd));
+    const int la = mask(ia, ja), ld = mask(id, jd);
+    __builtin_amdgcn_sched_barrier(0);            // both issued before either is waited for, whatever the register budget
+    const int ta = pin_here(la), td = pin_here(ld);
     if (!in_a) {
         x = xa, y = ya;
         return DLESM_DRIFTER_LEFT;
@@ -355,6 +352,56 @@ __device__ __forceinline__ int dispersal_substep(double h, const DrifterBox &box
     if (td == 0) return DLESM_DRIFTER_GROUNDED;
     x = xd, y = yd, i = id, j = jd;
     return td < 0 ? DLESM_DRIFTER_OPEN : DLESM_DRIFTER_ACTIVE;
+}
+
+// One substep with a kick of a constant amplitude: kick() / the metrics of the substep's own cell (stage 1's, already
+// loaded), then kicked_move.  kick() is called behind the stage-1 loads and before their first use: its integer work sits
+// under their latency.
+template <class CF, class TF, class KF>
+__device__ __forceinline__ int dispersal_substep(double h, const DrifterBox &box, double &x, double &y, int &i, int &j, CF cell,
+                                                 TF mask, KF kick)
+{
+    const DrifterCell c1 = cell(i, j);
+    const DrifterMove g = kick();
+    __builtin_amdgcn_sched_barrier(0);            // the scheduler would otherwise put the generator behind the loads' first use
+    const DrifterMove k1 = drifter_vel(h, x, y, i, j, c1);
+    return kicked_move(h, box, x, y, i, j, k1, g.kx / c1.dx, g.ky / c1.dy, cell, mask);
+}
+
+// A random walk in a varying diffusivity (dlesm_random_walk.hip).  WalkCell: what one substep reads of
+// kh_t, the cell's own value and its four neighbours'.  A face between two cells that are not land carries the mean of the
+// two, a coast face the cell's own value: K along x is linear between the cell's u-faces, along y between its v-faces.
+struct WalkCell {
+    double c, e, w, n, s;
+};
+// the kick along one axis, in cells: the drift ah * dK/dx (Visser 1997) plus r in (-1, 1) times the amplitude of K half a drift
+// ahead of the particle; t_hi, k_hi: the east (north) neighbour's mask and value, frac: the particle's place in its cell
+__device__ __forceinline__ double random_walk_kick(double ah, double d, double frac, int t_hi, int t_lo, double kc, double k_hi,
+                                                   double k_lo, double r)
+{
+    const double f_hi = t_hi != 0 ? 0.5 * (kc + k_hi) : kc, f_lo = t_lo != 0 ? 0.5 * (kc + k_lo) : kc;
+    const double dk = f_hi - f_lo;
+    const double c = (ah * dk) / (d * d);
+    double k = f_lo + dk * (frac + 0.5 * c);
+    k = k > 0.0 ? k : 0.0;
+    return c + (sqrt((6.0 * k) * ah) * r) / d;
+}
+// One substep of it: dispersal_substep with the kick made from kh_t.  kcell(i, j) loads the WalkCell, five unconditional
+// loads issued with cell(i, j)'s ten before any is used; rng() gives the two numbers of (-1, 1) and stands, like kick()
+// above, behind the loads and before their first use.
+template <class CF, class WF, class TF, class RF>
+__device__ __forceinline__ int random_walk_substep(double h, const DrifterBox &box, double &x, double &y, int &i, int &j, CF cell,
+                                                   WF kcell, TF mask, RF rng)
+{
+    const DrifterCell c1 = cell(i, j);
+    const WalkCell k = kcell(i, j);
+    const DrifterMove r = rng();
+    __builtin_amdgcn_sched_barrier(0);
+    const DrifterMove k1 = drifter_vel(h, x, y, i, j, c1);
+    const double ah = fabs(h);
+    const double gx = random_walk_kick(ah, c1.dx, x - (double)i, c1.t_e, c1.t_w, k.c, k.e, k.w, r.kx);
+    const double gy = random_walk_kick(ah, c1.dy, y - (double)j, c1.t_n, c1.t_s, k.c, k.n, k.s, r.ky);
+    return kicked_move(h, box, x, y, i, j, k1, gx, gy, cell, mask);
 }
 
 // next_sshu / next_sshv at a face whose mask sum t0 + t1 is > 0: 0 = the face's own T cell,

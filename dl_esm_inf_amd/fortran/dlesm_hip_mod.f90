@@ -1123,6 +1123,35 @@ module dlesm_hip_mod
        type(c_ptr), value :: tmask, dx_t, dy_t, un, vn, stream
        integer(c_int) :: rc
      end function
+     ! ---- drifters in a varying diffusivity (DESIGN.md section 6.22): section 6.20's step with the kick made from the T-point
+     !      field kh_t (device doubles laid out like dx_t) and Visser's drift correction; everything else as above
+     function dlesm_random_walk_f64(h, nsub, kh_t, seed, tick, tick_dev, ld, ny, xstart, xstop, ystart, ystop, tmask, dx_t, &
+          dy_t, un, vn, n, id, px, py, status, stream) bind(C, name="dlesm_random_walk_f64") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       real(c_double), value :: h
+       integer(c_int), value :: nsub
+       type(c_ptr), value :: kh_t
+       integer(c_long_long), value :: seed, tick
+       type(c_ptr), value :: tick_dev
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn
+       integer(c_long_long), value :: n
+       type(c_ptr), value :: id, px, py, status, stream
+       integer(c_int) :: rc
+     end function
+     function dlesm_random_walk_set(set, h, nsub, kh_t, seed, tick, tick_dev, ld, ny, xstart, xstop, ystart, ystop, tmask, &
+          dx_t, dy_t, un, vn, stream) bind(C, name="dlesm_random_walk_set") result(rc)
+       import :: c_int, c_ptr, c_double, c_long_long
+       type(c_ptr), value :: set
+       real(c_double), value :: h
+       integer(c_int), value :: nsub
+       type(c_ptr), value :: kh_t
+       integer(c_long_long), value :: seed, tick
+       type(c_ptr), value :: tick_dev
+       integer(c_int), value :: ld, ny, xstart, xstop, ystart, ystop
+       type(c_ptr), value :: tmask, dx_t, dy_t, un, vn, stream
+       integer(c_int) :: rc
+     end function
      ! ---- the coupled step on a decomposed grid and the int halo exchange (DESIGN.md section 6.13)
      function dlesm_nemolite_coupled_step_dm(plan, wet, scheme, params, grid, area_t, ld, ny, tbox, ubox, vbox, obc, ssh_bc, un, &
           vn, ht, hu, hv, sshn_t, sshn_u, sshn_v, ssha, ssha_u, ssha_v, ua, va, c_in, c_out, ntracers, stream) &

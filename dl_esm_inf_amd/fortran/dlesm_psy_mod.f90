@@ -63,7 +63,7 @@ module dlesm_psy_mod
   public :: flow_output
   public :: drifters_type, drifters_create, drifters_get, drifters_free, drifter_step
   public :: particle_sort, particle_origin
-  public :: dispersal_step
+  public :: dispersal_step, random_walk
   public :: cell_bin
   public :: DLESM_DRIFTER_ACTIVE, DLESM_DRIFTER_LEFT, DLESM_DRIFTER_OPEN, DLESM_DRIFTER_GROUNDED, DLESM_DRIFTER_FREE
   public :: invoke_shallow_step_dm, halo_exchange_multi, invoke_jacobi5_multi, plan_jacobi5, plan_shallow_step
@@ -991,6 +991,41 @@ contains
     end associate
     if (rc /= 0) call gocean_stop('dispersal_step: ' // dlesm_error_text())
   end subroutine dispersal_step
+
+  !> dispersal_step in a diffusivity that varies in space (dlesm_random_walk_set, DESIGN.md section 6.22): kh_t is a T-point
+  !! field of un's grid in m2/s, finite and >= 0 wherever the mask is not 0.  Per substep and axis a particle drifts by
+  !! |h| dK/dx (Visser's correction, without which particles collect where mixing is weak) and takes a kick sized by K half a
+  !! drift ahead; a constant field gives dispersal_step's bits.  seed, tick, the region, the mask, the metrics, the statuses
+  !! and the random streams through particle_sort are dispersal_step's.  On a decomposed grid kh_t needs valid depth-1 halos,
+  !! like un, vn and the mask.  Asynchronous on the default stream; nothing is exchanged and the call is not collective.
+  subroutine random_walk(set, h, nsub, kh_t, seed, tick, un, vn)
+    type(drifters_type), intent(inout) :: set
+    real(go_wp), intent(in) :: h
+    integer, intent(in) :: nsub
+    type(r2d_field), intent(inout), target :: kh_t
+    integer(c_long_long), intent(in) :: seed, tick
+    type(r2d_field), intent(inout), target :: un, vn
+    type(c_region) :: sub, box, whole
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop('random_walk: the set has not been created')
+    if (.not. associated(kh_t%grid, un%grid) .or. kh_t%defined_on /= GO_T_POINTS) &
+         call gocean_stop('random_walk: kh_t is a T-point field of the grid of un')
+    call need_device(un);  call need_device(vn);  call need_device(kh_t)
+    call grid_to_device(un%grid)
+    associate (g => un%grid)
+      associate (s => g%subdomain%internal)
+        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+      end associate
+      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
+                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
+      if (rc /= 0) call gocean_stop('random_walk: ' // dlesm_error_text())
+      rc = dlesm_random_walk_set(set%handle, real(h, c_double), int(nsub, c_int), field_device_data(kh_t), seed, tick, &
+                                 c_null_ptr, int(g%nx, c_int), int(g%ny, c_int), box%xstart, box%xstop, box%ystart, &
+                                 box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, field_device_data(un), &
+                                 field_device_data(vn), c_null_ptr)
+    end associate
+    if (rc /= 0) call gocean_stop('random_walk: ' // dlesm_error_text())
+  end subroutine random_walk
 
   !> Bring the set into cell order (dlesm_particle_sort_set, DESIGN.md section 6.18): the particles that are ACTIVE and inside
   !! the T internal region of un's grid -- the box drifter_step uses -- come first, in the row-major order of their cells and,

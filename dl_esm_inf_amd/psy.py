@@ -609,6 +609,43 @@ def dispersal_step(h, kh, seed, tick, px, py, status, un, vn, nsub=1, ids=None, 
         C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
 
 
+def random_walk(h, kh_t, seed, tick, px, py, status, un, vn, nsub=1, ids=None, tick_dev=None, stream=None):
+    """dispersal_step in a diffusivity that varies in space (dlesm_random_walk_f64).  kh_t: an
+    r2d_field at T points of un's grid, or a contiguous float64 CUDA tensor of ny x nx laid out like the grid's dx_t, in
+    m2/s; it must be finite and >= 0 wherever the mask is not 0 (what it holds on land changes no bit).  Per substep and axis
+    a particle drifts by |h| dK/dx -- Visser's correction, without which particles collect where mixing is weak -- and takes
+    a kick sized by K half a drift ahead, K linear between the cell's faces; a constant kh_t gives dispersal_step's bits.
+    Everything else -- seed, tick, ids, tick_dev, the rejection at the coast, the statuses, the region -- is dispersal_step's.
+    Keep |h| |dK| / dx^2 + sqrt(6 K |h|) / dx below one cell.  Asynchronous.  On a decomposed grid kh_t needs valid depth-1
+    halos, like un, vn and the mask; nothing is exchanged and the call is not collective."""
+    import torch
+    who = "random_walk"
+    n = _drifter_arrays(who, px, py, status)
+    g = un.grid
+    if vn.grid is not g:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
+    if isinstance(kh_t, torch.Tensor):
+        if not (kh_t.is_cuda and kh_t.is_contiguous() and kh_t.dtype == torch.float64 and tuple(kh_t.shape) == (g.ny, g.nx)):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: kh_t is a contiguous float64 CUDA tensor of %d x %d" % (who, g.ny, g.nx))
+        pk = C.c_void_p(kh_t.data_ptr())
+    else:
+        if kh_t.grid is not g or kh_t.defined_on != GO_T_POINTS:
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: kh_t is a T-point field of the grid of un" % who)
+        pk = kh_t.device_ptr
+    if ids is not None and not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and ids.numel() == n):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int32 CUDA tensor of one element per particle" % who)
+    if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
+    seed = int(seed) & 0xffffffffffffffff
+    it = field_bounds(g, GO_T_POINTS)[0]
+    check(_cabi.lib().dlesm_random_walk_f64(
+        float(h), int(nsub), pk, seed - (1 << 64) if seed >> 63 else seed, int(tick),
+        C.c_void_p(tick_dev.data_ptr()) if tick_dev is not None else None, g.nx, g.ny, it.xstart, it.xstop, it.ystart,
+        it.ystop, g.tmask_device_ptr, C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()),
+        un.device_ptr, vn.device_ptr, n, C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(px.data_ptr()),
+        C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+
+
 def drifter_sample(px, py, status, fields, out=None, stream=None):
     """T-point fields at the particles (dlesm_drifter_sample_f64): for every DRIFTER_ACTIVE particle
     inside the T internal region, out[k][p] = fields[k] in the particle's cell, for 1 to 8 T-point r2d_fields of one grid;

@@ -1372,6 +1372,41 @@ int dlesm_dispersal_step_set(dlesm_drifters *set, double h, int nsub, double kh,
                              const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
                              void *stream);
 
+/* Drifters in a varying diffusivity: section 6.20's step with the kick made from a T-point field
+ * kh_t (m2/s; ld x ny doubles laid out like dx_t) instead of one number, with the drift correction of Visser (1997), so that
+ * a well-mixed cloud stays well mixed where kh_t varies -- a walk without the drift collects particles where mixing is weak.
+ * Everything of section 6.20 holds -- the generator, its counter and key, rx, ry, tau, k1, the midpoint and k2, D, A = D +
+ * (gx, gy), the destination rule on A then D, the entry test, the statuses, tick, tick_dev and the ids -- except how the kick
+ * is made.  With (i,j) the particle's cell at the substep's start, a = x - i, b = y - j there, t_e..t_s the four neighbours'
+ * masks, dx = dx_t(i,j), dy = dy_t(i,j), every operation rounded in double in the order written:
+ *     Kc  = kh_t(i,j)
+ *     ke  = t_e != 0 ? 0.5*(Kc + kh_t(i+1,j)) : Kc      kw, kn, ks likewise        (face values; a coast face takes the cell's own)
+ *     ah  = fabs(h)
+ *     dkx = ke - kw                         dky = kn - ks
+ *     cx  = (ah * dkx) / (dx * dx)          cy  = (ah * dky) / (dy * dy)           (the drift, in cells)
+ *     kx  = kw + dkx * (a + 0.5*cx)         ky  = ks + dky * (b + 0.5*cy)          (K half a drift ahead, linear in the cell)
+ *     kx  = kx > 0.0 ? kx : 0.0             ky likewise
+ *     gx  = cx + (sqrt((6.0*kx) * ah) * rx) / dx
+ *     gy  = cy + (sqrt((6.0*ky) * ah) * ry) / dy
+ * The five values of kh_t are read whatever the masks say; a neighbour that is wet or open (T != 0) is used, ring cells outside
+ * the box included, and what a land cell of kh_t holds changes no bit.  kh_t must be finite and >= 0 on the cells with T != 0:
+ * the caller's responsibility, the host cannot see the field; any other value is carried through the arithmetic above and
+ * cannot fault.  kh_t == kh on every cell with T != 0 gives dlesm_dispersal_step_f64(kh)'s bits, kh_t == 0 there
+ * dlesm_drifter_step_f64's.  Keep |cx| + sqrt(6 K |h|) / dx below one cell, and h short where the gradients of neighbouring
+ * faces differ strongly.  Asynchronous on `stream`, no plan, no scratch, no atomics, no allocation, no host synchronisation.
+ * n == 0 or an empty box launches nothing and returns 0, *tick_dev unchanged.  DLESM_EINVAL before anything is launched:
+ * everything dlesm_dispersal_step_f64 refuses of the arguments they share, kh_t NULL or not 8-byte aligned, kh_t overlapping
+ * px, py, status or tick_dev.  dlesm_random_walk_set steps the owner's particles with the set's origin as id, like
+ * dlesm_dispersal_step_set. */
+int dlesm_random_walk_f64(double h, int nsub, const double *kh_t, long long seed, long long tick, const long long *tick_dev,
+                          int ld, int ny, int xstart, int xstop, int ystart, int ystop, const int *tmask,
+                          const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n,
+                          const int *id, double *px, double *py, int *status, void *stream);
+int dlesm_random_walk_set(dlesm_drifters *set, double h, int nsub, const double *kh_t, long long seed, long long tick,
+                          const long long *tick_dev, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
+                          const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
+                          void *stream);
+
 /* Particles that cross rank boundaries: on a decomposed grid a particle that leaves its tile is handed
  * to the neighbouring rank on the device, without a host copy of px, py or status.  A particle set is arrays of a fixed length n,
  * the capacity; a slot whose status is DLESM_DRIFTER_FREE holds no particle (every entry of sections 6.17-6.20 treats it as
