@@ -1,7 +1,7 @@
 // Particles binned by cell: per-cell sums of up to eight per-particle weights -- a null weight
 // array counts -- over the slots of a permutation in key order, stored (DLESM_OUT_SET) or added with a factor
 // (DLESM_OUT_ADD) into T-point fields, and the count for the owner of dlesm_drifter.hip.  The key rule is section 6.18's
-// (CellKey, dlesm_nemolite.h).  In key order a cell's particles are one run of slots, so no cell is added to from two places.
+// (CellKey, dlesm_particles.h).  In key order a cell's particles are one run of slots, so no cell is added to from two places.
 //
 // The sum of a run has a fixed order: the aligned groups of 64 slots are chunks; inside a chunk the run's slots are added one
 // by one in slot order, beginning with the first; the chunks' partials are added one by one in chunk order, beginning with the
@@ -23,7 +23,7 @@
 // atomics, no LDS, no scratch memory; latency bound and small, so held at eight waves per SIMD.
 #include <cmath>
 
-#include "dlesm_nemolite.h"
+#include "dlesm_particles.h"
 
 namespace dlesm {
 
@@ -348,7 +348,7 @@ extern "C" int dlesm_cell_bin_set(dlesm_drifters *set, int mode, double alpha, i
 {
     static const char *const who = "dlesm_cell_bin_set";
     if (int rc = ensure_device()) return rc;
-    DLESM_REQUIRE(set != nullptr && set->magic == DLESM_DRIFTERS_MAGIC, "%s: not a drifter set", who);
+    if (int rc = drifters_ok(who, set)) return rc;
     const long long n = set->n;
     DLESM_REQUIRE(n <= BIN_MAX_N, "%s: %lld particles (0..2^31-1)", who, n);
     long long ncells;

@@ -1973,7 +1973,7 @@ static int nemolite_dm_step(const NemoDmStep &d, dlesm_halo_plan *p, int ld, int
         const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
         for (int k = 0; k < t.ntracers; k++)
             for (int m = 0; m < 14; m++)
-                DLESM_REQUIRE(!nemo::overlap(t.c_out[k], nb, more[m], nb), "%s: c_out[%d] overlaps %s", who, k, more_name[m]);
+                DLESM_REQUIRE(!overlap(t.c_out[k], nb, more[m], nb), "%s: c_out[%d] overlaps %s", who, k, more_name[m]);
     }
     if (p->sends.empty() && p->recvs.empty())        // no neighbour: the single-domain entries, bit for bit
         return nemolite_single_domain(fl, t, ld, ny, stream);
@@ -2360,9 +2360,9 @@ extern "C" int dlesm_migrate_exchange(const int *neighbour, const void *const *s
                       who, d, d);
         DLESM_REQUIRE(neighbour[d] < size, "%s: neighbour[%d] = %d of %d ranks", who, d, neighbour[d], size);
         for (int e = 0; e < 2; e++)
-            DLESM_REQUIRE(!nemo::overlap(recv[d], (size_t)bytes, send[e], (size_t)bytes), "%s: recv[%d] overlaps send[%d]", who, d, e);
+            DLESM_REQUIRE(!overlap(recv[d], (size_t)bytes, send[e], (size_t)bytes), "%s: recv[%d] overlaps send[%d]", who, d, e);
     }
-    DLESM_REQUIRE(!nemo::overlap(recv[0], (size_t)bytes, recv[1], (size_t)bytes), "%s: recv[0] and recv[1] overlap", who);
+    DLESM_REQUIRE(!overlap(recv[0], (size_t)bytes, recv[1], (size_t)bytes), "%s: recv[0] and recv[1] overlap", who);
     DLESM_REQUIRE(neighbour[0] < 0 || neighbour[0] == me || neighbour[0] != neighbour[1],
                   "%s: rank %d on both sides (periodic boundaries between different ranks are left out)", who, neighbour[0]);
     if (int rc = ensure_device()) return rc;

@@ -337,17 +337,18 @@ int launch_stencil5_multi(const double *in, double *out, int ld, int ny, int nst
                           int ge, int gs, int gn, hipStream_t s);
 
 int check_box(const char *who, int ld, int ny, int xstart, int xstop, int ystart, int ystop, int ring);
-// everything dlesm_drifter_step_f64 refuses, for every entry that steps particles (dlesm_drifter.hip; dlesm_dispersal.hip adds
-// its own); *nothing = n == 0 or an empty box: return DLESM_OK without a launch
-int lagrangian_step_checks(const char *who, double h, int nsub, int ld, int ny, int xstart, int xstop, int ystart, int ystop,
-                           const int *tmask, const double *dx_t, const double *dy_t, const double *un, const double *vn,
-                           long long n, const double *px, const double *py, const int *status, bool *nothing);
-// the rules of tick, id and tick_dev for a step that draws random numbers, and *tick_dev += nsub on the stream
-// (dlesm_dispersal.hip; dlesm_random_walk.hip uses both)
-int random_stream_checks(const char *who, int nsub, long long tick, const long long *tick_dev, int ld, int ny, const int *tmask,
-                         const double *dx_t, const double *dy_t, const double *un, const double *vn, long long n, const int *id,
-                         const double *px, const double *py, const int *status);
-int launch_tick_bump(const long long *tick_dev, int nsub, hipStream_t stream);
+// true if [a, a+na) and [b, b+nb) share a byte
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// the guard of every entry that takes a drifter set
+inline int drifters_ok(const char *who, const dlesm_drifters *set)
+{
+    DLESM_REQUIRE(set != nullptr && set->magic == DLESM_DRIFTERS_MAGIC, "%s: not a drifter set", who);
+    return DLESM_OK;
+}
 // two shallow-water steps per launch (dlesm_shallow_x2.hip): the overlap check of the twelve arrays, and the distributed form's
 // wave-tile conditions and launch (stage 1 computed on the box grown by gw..gn; see shallow_tile_x2_grown)
 int x2_disjoint(const char *who, const double *const (&all)[12], int ld, int ny);

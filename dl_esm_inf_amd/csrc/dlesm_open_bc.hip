@@ -51,12 +51,6 @@ __global__ __launch_bounds__(256) void obc_apply(ObcArgs a)
     if (k < a.nv) flather(a.va, a.hv, a.sshn_v, a.sshn_t, a.g, a.vf[k], a.vi[k], a.vo[k]);
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 // the open faces of one box: (di, dj) = (1, 0) for u faces, (0, 1) for v faces; indices 0-based linear
 int scan_faces(const char *who, const char *kind, const int *tm, int ld, int ny, const dlesm_region *box, int di, int dj,
                std::vector<int> &f, std::vector<int> &in, std::vector<int> &o)

@@ -18,7 +18,7 @@
 // at eight waves per SIMD, as the sort's.
 #include <cmath>
 
-#include "dlesm_nemolite.h"
+#include "dlesm_particles.h"
 
 namespace dlesm {
 
@@ -354,11 +354,6 @@ int check_phase(const char *who, int axis, const void *const *msg, bool msg_out,
     return disjoint(who, s, ns);
 }
 
-DrifterBox box_of(int xstart, int xstop, int ystart, int ystop)
-{
-    return DrifterBox{(double)xstart, (double)xstop + 1.0, (double)ystart, (double)ystop + 1.0};
-}
-
 int launch_pack(int axis, int xstart, int xstop, int ystart, int ystop, long long n, const double *px, const double *py,
                 int *status, const long long *id, const void *const *payload, int npayload, const int *has_neighbour,
                 const int *shift_x, const int *shift_y, long long cap, void *const *send, dlesm_migrate_counts *counts,
@@ -369,7 +364,7 @@ int launch_pack(int axis, int xstart, int xstop, int ystart, int ystop, long lon
     PackArgs a{};
     a.px = px, a.py = py, a.status = status, a.id = (const uint64_t *)id, a.npayload = npayload, a.n = n;
     for (int q = 0; q < npayload; q++) a.payload[q] = (const uint64_t *)payload[q];
-    a.box = box_of(xstart, xstop, ystart, ystop), a.axis = axis, a.cap = cap;
+    a.box = drifter_box(xstart, xstop, ystart, ystop), a.axis = axis, a.cap = cap;
     for (int d = 0; d < 2; d++) {
         a.has[d] = has_neighbour[d] != 0, a.sx[d] = (double)shift_x[d], a.sy[d] = (double)shift_y[d];
         a.msg[d] = (uint64_t *)send[d];
@@ -393,7 +388,7 @@ int launch_unpack(int axis, int xstart, int xstop, int ystart, int ystop, long l
     UnpackArgs a{};
     a.px = px, a.py = py, a.status = status, a.id = (uint64_t *)id, a.npayload = npayload, a.n = n;
     for (int q = 0; q < npayload; q++) a.payload[q] = (uint64_t *)payload[q];
-    a.box = box_of(xstart, xstop, ystart, ystop), a.axis = axis, a.cap = cap;
+    a.box = drifter_box(xstart, xstop, ystart, ystop), a.axis = axis, a.cap = cap;
     for (int d = 0; d < 2; d++) a.msg[d] = (const uint64_t *)recv[d];
     a.table = (unsigned *)(base + plan.table), a.wave_part = (unsigned *)(base + plan.wave_part);
     a.nblocks = plan.nblocks, a.m = plan.m[1], a.counts = counts;

@@ -17,7 +17,7 @@
 // permute_k: one slot per lane, perm read once, a loop over the arrays; an index outside 0..n-1 stores nothing.
 #include <cmath>
 
-#include "dlesm_nemolite.h"
+#include "dlesm_particles.h"
 
 namespace dlesm {
 
@@ -351,12 +351,6 @@ int launch_permute(long long n, const int *perm, int narrays, const void *const 
     return DLESM_OK;
 }
 
-int set_ok(const char *who, const dlesm_drifters *set)
-{
-    DLESM_REQUIRE(set != nullptr && set->magic == DLESM_DRIFTERS_MAGIC, "%s: not a drifter set", who);
-    return DLESM_OK;
-}
-
 } // namespace
 
 } // namespace dlesm
@@ -397,7 +391,7 @@ extern "C" int dlesm_particle_sort_set(dlesm_drifters *set, int xstart, int xsto
 {
     static const char *const who = "dlesm_particle_sort_set";
     if (int rc = ensure_device()) return rc;
-    if (int rc = set_ok(who, set)) return rc;
+    if (int rc = drifters_ok(who, set)) return rc;
     const long long n = set->n;
     DLESM_REQUIRE(n <= SORT_MAX_N, "%s: %lld particles (0..2^31-1)", who, n);
     DLESM_REQUIRE((long long)xstop >= (long long)xstart - 1 && (long long)ystop >= (long long)ystart - 1,
@@ -440,7 +434,7 @@ extern "C" int dlesm_particle_set_origin(dlesm_drifters *set, int *origin, long 
 {
     static const char *const who = "dlesm_particle_set_origin";
     if (int rc = ensure_device()) return rc;
-    if (int rc = set_ok(who, set)) return rc;
+    if (int rc = drifters_ok(who, set)) return rc;
     if (nlive) *nlive = set->n == 0 ? 0 : -1;
     if (!set->sorted) {                                  // no sort since the last put: the identity, nlive not known
         for (long long k = 0; origin && k < set->n; k++) origin[k] = (int)k;

@@ -128,9 +128,9 @@ inline int check_result_apart(const char *who, const void *result_dev, size_t by
 {
     if (!result_dev) return DLESM_OK;
     const size_t nb = (size_t)ld * (size_t)ny * sizeof(double);
-    DLESM_REQUIRE(!nemo::overlap(result_dev, bytes, tmask, nb / 2), "%s: result_dev lies inside tmask", who);
+    DLESM_REQUIRE(!overlap(result_dev, bytes, tmask, nb / 2), "%s: result_dev lies inside tmask", who);
     for (int k = 0; k < n; k++)
-        DLESM_REQUIRE(!nemo::overlap(result_dev, bytes, ins[k], nb), "%s: result_dev lies inside %s", who, name[k]);
+        DLESM_REQUIRE(!overlap(result_dev, bytes, ins[k], nb), "%s: result_dev lies inside %s", who, name[k]);
     return DLESM_OK;
 }
 

@@ -926,6 +926,33 @@ contains
     set%n = 0
   end subroutine drifters_free
 
+  !> What drifter_step, dispersal_step and random_walk do before their call, stopping under the caller's name `who`: the set
+  !! has been created, kh_t (where given) is a T-point field of un's grid, the fields and the grid are on the device; box
+  !! becomes the T internal region of un's grid.
+  subroutine particle_step_box(who, set, un, vn, box, kh_t)
+    character(len=*), intent(in) :: who
+    type(drifters_type), intent(in) :: set
+    type(r2d_field), intent(inout), target :: un, vn
+    type(c_region), intent(out) :: box
+    type(r2d_field), intent(inout), target, optional :: kh_t
+    type(c_region) :: sub, whole
+    integer(c_int) :: rc
+    if (.not. c_associated(set%handle)) call gocean_stop(who // ': the set has not been created')
+    if (present(kh_t)) then
+       if (.not. associated(kh_t%grid, un%grid) .or. kh_t%defined_on /= GO_T_POINTS) &
+            call gocean_stop(who // ': kh_t is a T-point field of the grid of un')
+    end if
+    call need_device(un);  call need_device(vn)
+    if (present(kh_t)) call need_device(kh_t)
+    call grid_to_device(un%grid)
+    associate (g => un%grid, s => un%grid%subdomain%internal)
+      sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
+      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
+                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
+    end associate
+    if (rc /= 0) call gocean_stop(who // ': ' // dlesm_error_text())
+  end subroutine particle_step_box
+
   !> Carry the set through the level-n flow (dlesm_drifter_step_f64, DESIGN.md section 6.17): nsub substeps of h seconds by
   !! the midpoint rule, in place, over the T internal region of un's grid with the grid's mask, dx_t and dy_t.  A particle
   !! that leaves the region becomes LEFT and one that reaches an open cell OPEN, both at their new position; one whose move
@@ -936,22 +963,14 @@ contains
     real(go_wp), intent(in) :: h
     integer, intent(in) :: nsub
     type(r2d_field), intent(inout), target :: un, vn
-    type(c_region) :: sub, box, whole
+    type(c_region) :: box
     type(c_ptr) :: px, py, status
     integer(c_long_long) :: n
     integer(c_int) :: rc
-    if (.not. c_associated(set%handle)) call gocean_stop('drifter_step: the set has not been created')
-    call need_device(un);  call need_device(vn)
-    call grid_to_device(un%grid)
+    call particle_step_box('drifter_step', set, un, vn, box)
+    rc = dlesm_drifters_arrays(set%handle, n, px, py, status)
+    if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
     associate (g => un%grid)
-      associate (s => g%subdomain%internal)
-        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
-      end associate
-      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
-                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
-      if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
-      rc = dlesm_drifters_arrays(set%handle, n, px, py, status)
-      if (rc /= 0) call gocean_stop('drifter_step: ' // dlesm_error_text())
       rc = dlesm_drifter_step_f64(real(h, c_double), int(nsub, c_int), int(g%nx, c_int), int(g%ny, c_int), box%xstart, &
                                   box%xstop, box%ystart, box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, &
                                   field_device_data(un), field_device_data(vn), n, px, py, status, c_null_ptr)
@@ -972,18 +991,10 @@ contains
     real(go_wp), intent(in) :: kh
     integer(c_long_long), intent(in) :: seed, tick
     type(r2d_field), intent(inout), target :: un, vn
-    type(c_region) :: sub, box, whole
+    type(c_region) :: box
     integer(c_int) :: rc
-    if (.not. c_associated(set%handle)) call gocean_stop('dispersal_step: the set has not been created')
-    call need_device(un);  call need_device(vn)
-    call grid_to_device(un%grid)
+    call particle_step_box('dispersal_step', set, un, vn, box)
     associate (g => un%grid)
-      associate (s => g%subdomain%internal)
-        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
-      end associate
-      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
-                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
-      if (rc /= 0) call gocean_stop('dispersal_step: ' // dlesm_error_text())
       rc = dlesm_dispersal_step_set(set%handle, real(h, c_double), int(nsub, c_int), real(kh, c_double), seed, tick, &
                                     c_null_ptr, int(g%nx, c_int), int(g%ny, c_int), box%xstart, box%xstop, box%ystart, &
                                     box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, field_device_data(un), &
@@ -1005,20 +1016,10 @@ contains
     type(r2d_field), intent(inout), target :: kh_t
     integer(c_long_long), intent(in) :: seed, tick
     type(r2d_field), intent(inout), target :: un, vn
-    type(c_region) :: sub, box, whole
+    type(c_region) :: box
     integer(c_int) :: rc
-    if (.not. c_associated(set%handle)) call gocean_stop('random_walk: the set has not been created')
-    if (.not. associated(kh_t%grid, un%grid) .or. kh_t%defined_on /= GO_T_POINTS) &
-         call gocean_stop('random_walk: kh_t is a T-point field of the grid of un')
-    call need_device(un);  call need_device(vn);  call need_device(kh_t)
-    call grid_to_device(un%grid)
+    call particle_step_box('random_walk', set, un, vn, box, kh_t)
     associate (g => un%grid)
-      associate (s => g%subdomain%internal)
-        sub = c_region(s%nx, s%ny, s%xstart, s%xstop, s%ystart, s%ystop)
-      end associate
-      rc = dlesm_field_bounds(int(GO_T_POINTS, c_int), int(g%offset, c_int), int(g%boundary_conditions(1), c_int), &
-                              int(g%boundary_conditions(2), c_int), sub, int(g%nx, c_int), int(g%ny, c_int), box, whole)
-      if (rc /= 0) call gocean_stop('random_walk: ' // dlesm_error_text())
       rc = dlesm_random_walk_set(set%handle, real(h, c_double), int(nsub, c_int), field_device_data(kh_t), seed, tick, &
                                  c_null_ptr, int(g%nx, c_int), int(g%ny, c_int), box%xstart, box%xstop, box%ystart, &
                                  box%ystop, g%tmask_device, g%dx_t_device, g%dy_t_device, field_device_data(un), &

@@ -558,6 +558,34 @@ def _drifter_arrays(who, px, py, status):
     return n
 
 
+def _particle_step(who, entry, h, nsub, px, py, status, un, vn, own=None, rng=None, stream=None):
+    """what drifter_step, dispersal_step and random_walk share: the checks of the arrays and of the one grid, the T internal
+    box and the call of `entry`.  own(g): the entry's own argument behind nsub (kh, or kh_t's address), made where the entry
+    looks at it; rng = (seed, tick, ids, tick_dev) for the two entries that draw numbers."""
+    import torch
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    n = _drifter_arrays(who, px, py, status)
+    g = un.grid
+    if vn.grid is not g:
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
+    head, id_arg = [float(h), int(nsub)] + ([own(g)] if own is not None else []), []
+    if rng is not None:
+        seed, tick, ids, tick_dev = rng
+        if ids is not None and not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and ids.numel() == n):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int32 CUDA tensor of one element per particle" % who)
+        if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
+            raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
+        seed = int(seed) & 0xffffffffffffffff
+        head += [seed - (1 << 64) if seed >> 63 else seed, int(tick), ptr(tick_dev)]
+        id_arg = [ptr(ids)]
+    it = field_bounds(g, GO_T_POINTS)[0]
+    check(entry(*head, g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr, ptr(g.dx_t_device),
+                ptr(g.dy_t_device), un.device_ptr, vn.device_ptr, n, *id_arg, ptr(px), ptr(py), ptr(status), _stream_ptr(stream)))
+
+
 def drifter_step(h, px, py, status, un, vn, nsub=1, stream=None):
     """carry particles through the level-n C-grid flow (dlesm_drifter_step_f64): nsub substeps of h
     seconds by the midpoint rule, in place.  px, py: contiguous float64 CUDA tensors, positions in local index coordinates (T
@@ -567,16 +595,7 @@ def drifter_step(h, px, py, status, un, vn, nsub=1, stream=None):
     DRIFTER_GROUNDED at its last wet position.  Over the T internal region of un.grid with the grid's tmask, dx_t and dy_t.
     Asynchronous.  On a decomposed grid un, vn and the mask need valid depth-1 halos; nothing is exchanged and the call is
     not collective."""
-    who = "drifter_step"
-    n = _drifter_arrays(who, px, py, status)
-    g = un.grid
-    if vn.grid is not g:
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
-    it = field_bounds(g, GO_T_POINTS)[0]
-    check(_cabi.lib().dlesm_drifter_step_f64(
-        float(h), int(nsub), g.nx, g.ny, it.xstart, it.xstop, it.ystart, it.ystop, g.tmask_device_ptr,
-        C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()), un.device_ptr, vn.device_ptr, n,
-        C.c_void_p(px.data_ptr()), C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+    _particle_step("drifter_step", _cabi.lib().dlesm_drifter_step_f64, h, nsub, px, py, status, un, vn, stream=stream)
 
 
 def dispersal_step(h, kh, seed, tick, px, py, status, un, vn, nsub=1, ids=None, tick_dev=None, stream=None):
@@ -589,24 +608,8 @@ def dispersal_step(h, kh, seed, tick, px, py, status, un, vn, nsub=1, ids=None, 
     one-element int64 CUDA tensor that the kernel adds to tick and the call advances by nsub on the stream: what a captured
     time loop needs, for a graph without it replays the same kicks.  Same seed, ids and ticks give the same bytes on any
     stream and any run.  Asynchronous; nothing is exchanged and the call is not collective."""
-    import torch
-    who = "dispersal_step"
-    n = _drifter_arrays(who, px, py, status)
-    g = un.grid
-    if vn.grid is not g:
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
-    if ids is not None and not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and ids.numel() == n):
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int32 CUDA tensor of one element per particle" % who)
-    if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
-    seed = int(seed) & 0xffffffffffffffff
-    it = field_bounds(g, GO_T_POINTS)[0]
-    check(_cabi.lib().dlesm_dispersal_step_f64(
-        float(h), int(nsub), float(kh), seed - (1 << 64) if seed >> 63 else seed, int(tick),
-        C.c_void_p(tick_dev.data_ptr()) if tick_dev is not None else None, g.nx, g.ny, it.xstart, it.xstop, it.ystart,
-        it.ystop, g.tmask_device_ptr, C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()),
-        un.device_ptr, vn.device_ptr, n, C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(px.data_ptr()),
-        C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+    _particle_step("dispersal_step", _cabi.lib().dlesm_dispersal_step_f64, h, nsub, px, py, status, un, vn, lambda g: float(kh),
+                   (seed, tick, ids, tick_dev), stream)
 
 
 def random_walk(h, kh_t, seed, tick, px, py, status, un, vn, nsub=1, ids=None, tick_dev=None, stream=None):
@@ -620,30 +623,17 @@ def random_walk(h, kh_t, seed, tick, px, py, status, un, vn, nsub=1, ids=None, t
     halos, like un, vn and the mask; nothing is exchanged and the call is not collective."""
     import torch
     who = "random_walk"
-    n = _drifter_arrays(who, px, py, status)
-    g = un.grid
-    if vn.grid is not g:
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: un and vn are fields of one grid" % who)
-    if isinstance(kh_t, torch.Tensor):
-        if not (kh_t.is_cuda and kh_t.is_contiguous() and kh_t.dtype == torch.float64 and tuple(kh_t.shape) == (g.ny, g.nx)):
-            raise _cabi.DlesmError(_cabi.EINVAL, "%s: kh_t is a contiguous float64 CUDA tensor of %d x %d" % (who, g.ny, g.nx))
-        pk = C.c_void_p(kh_t.data_ptr())
-    else:
+
+    def own(g):
+        if isinstance(kh_t, torch.Tensor):
+            if not (kh_t.is_cuda and kh_t.is_contiguous() and kh_t.dtype == torch.float64 and tuple(kh_t.shape) == (g.ny, g.nx)):
+                raise _cabi.DlesmError(_cabi.EINVAL, "%s: kh_t is a contiguous float64 CUDA tensor of %d x %d" % (who, g.ny, g.nx))
+            return C.c_void_p(kh_t.data_ptr())
         if kh_t.grid is not g or kh_t.defined_on != GO_T_POINTS:
             raise _cabi.DlesmError(_cabi.EINVAL, "%s: kh_t is a T-point field of the grid of un" % who)
-        pk = kh_t.device_ptr
-    if ids is not None and not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and ids.numel() == n):
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids is a contiguous int32 CUDA tensor of one element per particle" % who)
-    if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
-        raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
-    seed = int(seed) & 0xffffffffffffffff
-    it = field_bounds(g, GO_T_POINTS)[0]
-    check(_cabi.lib().dlesm_random_walk_f64(
-        float(h), int(nsub), pk, seed - (1 << 64) if seed >> 63 else seed, int(tick),
-        C.c_void_p(tick_dev.data_ptr()) if tick_dev is not None else None, g.nx, g.ny, it.xstart, it.xstop, it.ystart,
-        it.ystop, g.tmask_device_ptr, C.c_void_p(g.dx_t_device.data_ptr()), C.c_void_p(g.dy_t_device.data_ptr()),
-        un.device_ptr, vn.device_ptr, n, C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(px.data_ptr()),
-        C.c_void_p(py.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+        return kh_t.device_ptr
+
+    _particle_step(who, _cabi.lib().dlesm_random_walk_f64, h, nsub, px, py, status, un, vn, own, (seed, tick, ids, tick_dev), stream)
 
 
 def drifter_sample(px, py, status, fields, out=None, stream=None):

@@ -1,6 +1,6 @@
 """CPU tests of the boundary of the cell bin: the three entries are exported from the product and
 from the lab build and stand in the header, the ctypes table, INTEGRATION.md and dlesm_hip_mod with one argument list each;
-none of their names contains `particle` or `drifter` (tests/test_particle_order_abi.py and tests/test_drifter_abi.py pin those
+none of their names contains `particle` or `drifter` (tests/test_particle_order_abi.py and tests/test_particle_steps_abi.py pin those
 sets); dlesm_version() is unchanged; the Python and Fortran names are public; the scratch query is host arithmetic and grows
 with n and narrays; without a GPU the entries fail loudly and write nothing, and with one every refusal is DLESM_EINVAL with
 nothing written."""

@@ -13,71 +13,14 @@ import pytest
 
 import drifter_cases as DC
 import drifter_numpy as DN
+from particle_gpu import NS, SENT, SLACK, T, _check, _equal, _flow, _particles, _ptr, _up, shared_refusals  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-SENT = DC.SENTINEL
-SLACK = 64
-NS = [1, 63, 64, 65, 257, 1000, 70001]
-_DEV = {}
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU")
-    import dl_esm_inf_amd as d
-    torch.cuda.set_device(0)
-    d.parallel_init(0, 1)
-    yield torch, d, d._cabi.lib()
-    _DEV.clear()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _up(torch, a, off=0):
-    """a host array on the device, its base `off` elements behind an allocation's"""
-    flat = torch.empty(a.size + off, dtype=torch.from_numpy(a).dtype, device="cuda")
-    t = flat[off:].view(a.shape)
-    t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-    return t
-
-
-def _flow(torch, ld, off):
-    """(tm, dx_t, dy_t, un, vn) on the device with leading dimension ld, bases offset by `off` elements; made once"""
-    key = (ld, off)
-    if key not in _DEV:
-        tm, dx_t, dy_t, un, vn = DC.flow()
-        _DEV[key] = [_up(torch, DC.embed(tm, ld, 0), off)] + [_up(torch, DC.embed(a, ld, np.nan), off)
-                                                              for a in (dx_t, dy_t, un, vn)]
-    return _DEV[key]
-
-
-def _particles(torch, n, off=0):
-    """the first n of the pool, in arrays with SLACK sentinel elements behind them"""
-    px, py, st = DC.particles()
-    out = []
-    for a, fill in ((px, SENT), (py, SENT), (st, -9)):
-        h = np.full(n + SLACK, fill, dtype=a.dtype)
-        h[:n] = a[:n]
-        out.append(_up(torch, h, off))
-    return out
 
 
 def _step(L, nsub, ld, box, F, n, P, stream=None, h=DC.H, ny=DC.NY):
     return L.dlesm_drifter_step_f64(h, nsub, ld, ny, *box, *[_ptr(t) for t in F], n, *[_ptr(t) for t in P],
                                     C.c_void_p(stream.cuda_stream) if stream is not None else None)
-
-
-def _check(P, n, want, what):
-    got = [t.cpu().numpy() for t in P]
-    assert DN.same(got[0][:n], want[0][:n]), (what, "px")
-    assert DN.same(got[1][:n], want[1][:n]), (what, "py")
-    assert (got[2][:n] == want[2][:n]).all(), (what, "status")
-    assert (got[0][n:] == SENT).all() and (got[1][n:] == SENT).all() and (got[2][n:] == -9).all(), (what, "slack")
-    return got
 
 
 @pytest.mark.parametrize("n", NS)
@@ -145,7 +88,7 @@ def test_twelve_successive_calls_and_the_nsub_identity(T):
         for _ in range(3):
             assert _step(L, 1, 27, box, F, DC.POOL, B) == 0
         torch.cuda.synchronize()
-        assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(A, B))
+        assert _equal(torch, A, B)
 
 
 def test_repeats_a_second_stream_and_a_graph_give_identical_bytes(T):
@@ -163,7 +106,7 @@ def test_repeats_a_second_stream_and_a_graph_give_identical_bytes(T):
         torch.cuda.synchronize()
         assert _step(L, 3, ld, box, F, n, P, stream) == 0
         torch.cuda.synchronize()
-        assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(P, first))
+        assert _equal(torch, P, first)
     # one capture of two calls (nsub = 1 and 2) on one stream, no branches; replayed once it equals the eager nsub = 3, and
     # replayed again six substeps
     P = _particles(torch, n)
@@ -176,10 +119,10 @@ def test_repeats_a_second_stream_and_a_graph_give_identical_bytes(T):
         rc2 = _step(L, 2, ld, box, F, n, P, s)
     assert rc1 == 0 and rc2 == 0, L.dlesm_last_error()
     torch.cuda.synchronize()
-    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(P, start))       # captured, not run
+    assert _equal(torch, P, start)                                                 # captured, not run
     graph.replay()
     torch.cuda.synchronize()
-    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(P, first))
+    assert _equal(torch, P, first)
     graph.replay()
     torch.cuda.synchronize()
     _check(P, n, DC.reference(box, 3, calls=2), "graph twice")
@@ -207,7 +150,7 @@ def test_sampling_equals_numpy(T, nfields):
             for k in range(nfields):
                 assert DN.same(out[k].cpu().numpy(), want[k]), (box, ld, k)
             assert (want[0][:n] != SENT).sum() > 300 and (want[0][:n] == SENT).sum() > 100
-            assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(P, before))
+            assert _equal(torch, P, before)
 
 
 def test_the_python_wrappers(T):
@@ -263,38 +206,13 @@ def test_every_refusal_returns_einval_and_changes_nothing(T):
     fb = [t.clone() for t in F]
     assert _step(L, 1, ld, box, F, 0, P) == 0                                      # n == 0: nothing launched
     assert _step(L, 1, ld, (5, 4, 2, 21), F, n, P) == 0 and _step(L, 1, ld, (2, 25, 9, 8), F, n, P) == 0   # an empty box
-    for k in range(5):                                                              # a null input
-        G = list(F)
-        G[k] = None
-        args = [_ptr(t) if t is not None else None for t in G]
-        assert L.dlesm_drifter_step_f64(DC.H, 1, ld, DC.NY, *box, *args, n, *[_ptr(t) for t in P], None) == EINVAL, k
-    for k in range(3):                                                              # a null particle array
-        Q = [_ptr(t) for t in P]
-        Q[k] = None
-        assert L.dlesm_drifter_step_f64(DC.H, 1, ld, DC.NY, *box, *[_ptr(t) for t in F], n, *Q, None) == EINVAL, k
 
     def raw(Fp, Pp, n_=n, nsub=1, h=DC.H, b=box, ny=DC.NY, ld_=ld):
-        return L.dlesm_drifter_step_f64(h, nsub, ld_, ny, *b, *[C.c_void_p(p) for p in Fp], n_, *[C.c_void_p(p) for p in Pp], None)
+        return L.dlesm_drifter_step_f64(h, nsub, ld_, ny, *b, *[C.c_void_p(p) if p else None for p in Fp], n_,
+                                        *[C.c_void_p(p) if p else None for p in Pp], None)
 
     Fp, Pp = [t.data_ptr() for t in F], [t.data_ptr() for t in P]
-    for k in range(1, 5):                                                           # a double array not 8-byte aligned
-        G = list(Fp)
-        G[k] += 4
-        assert raw(G, Pp) == EINVAL, k
-    assert raw([Fp[0] + 2] + Fp[1:], Pp) == EINVAL                                  # the mask not 4-byte aligned
-    assert raw(Fp, [Pp[0] + 4, Pp[1], Pp[2]]) == EINVAL and raw(Fp, [Pp[0], Pp[1] + 4, Pp[2]]) == EINVAL
-    assert raw(Fp, [Pp[0], Pp[1], Pp[2] + 2]) == EINVAL
-    assert raw(Fp, Pp, n_=-1) == EINVAL
-    assert raw(Fp, Pp, nsub=0) == EINVAL and raw(Fp, Pp, nsub=D._cabi.DRIFTER_MAX_SUB + 1) == EINVAL
-    for h in (float("nan"), float("inf"), float("-inf")):
-        assert raw(Fp, Pp, h=h) == EINVAL
-    for b in ((1, 25, 2, 21), (2, 26, 2, 21), (2, 25, 1, 21), (2, 25, 2, 22)):      # no room for the ring
-        assert raw(Fp, Pp, b=b) == EINVAL, b
-    assert raw(Fp, Pp, ld_=0) == EINVAL and raw(Fp, Pp, ny=0) == EINVAL
-    assert raw(Fp, [Pp[0], Pp[0], Pp[2]]) == EINVAL and raw(Fp, [Pp[0], Pp[1], Pp[0]]) == EINVAL       # particle arrays overlap
-    assert raw(Fp, [Pp[0], Pp[0] + 8 * (n - 1), Pp[2]]) == EINVAL
-    for k in range(5):                                                              # ... or lie in an input
-        assert raw(Fp, [Fp[k], Pp[1], Pp[2]]) == EINVAL and raw(Fp, [Pp[0], Pp[1], Fp[k]]) == EINVAL, k
+    shared_refusals(raw, EINVAL, D._cabi.DRIFTER_MAX_SUB, Fp, Pp, n)
     assert b"overlaps" in L.dlesm_last_error()
 
     # sampling
