@@ -577,6 +577,16 @@ static int capture_ok(const dlesm_halo_plan *p, hipStream_t s, bool over_mailbox
     return DLESM_OK;
 }
 
+// Will this call go over the plan's mailboxes, `nfields` fields per mailbox operation?  Always in mailbox mode (there is no
+// other transport), else unless dm_peer = 0 -- or, for an entry that is its sweep followed by an EXCHANGE (exchange_peer: the
+// 9-point and NEMOLite2D-class steps, exchange_on itself), dm_peer_exchange = 0.  Evaluated ONCE per call, for capture_ok and for
+// the branch.  nfields = 0: the Jacobi and 9-point steps, which never looked at the room (any mailbox holds one field).
+static bool steps_over_mailboxes(const dlesm_halo_plan *p, int nfields, bool as_exchange = false)
+{
+    return p->peer_on && p->peer_fcap >= nfields &&
+           (g_mailbox || (tuning("dm_peer", 1) && (!as_exchange || tuning("dm_peer_exchange", 1))));
+}
+
 // A pipelined step leaves its exchange in flight: whoever touches the plan or the halos next on
 // stream `s` is ordered behind it first.
 static int join_pending(dlesm_halo_plan *p, hipStream_t s)
@@ -706,9 +716,7 @@ static int exchange_on(dlesm_halo_plan *p, double *const *fields, int nf, unsign
     for (const Msg &m : p->recvs)
         if (dir_enabled(mask, m.dir)) { any = true; any_rpack |= m.off >= 0; }
     if (!any) return DLESM_OK; // serial run, or no direction enabled: nothing to do (pcomms:1546,1557-1571)
-    if (p->peer_on && nf <= p->peer_fcap && !prepacked && !skip_unpack &&
-        (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1))))      // (mailbox mode has no other transport)
-        return exchange_peer(p, fields, nf, mask, s);
+    if (!prepacked && !skip_unpack && steps_over_mailboxes(p, nf, true)) return exchange_peer(p, fields, nf, mask, s);
     // (a single field on its own goes the same way: rows staged through the buffer travel faster than rows
     //  sent in place from their 8-byte-aligned position in the field -- 42 against 52 us at 8192^2)
     if ((nf > 1 || (!prepacked && !skip_unpack && tuning("dm_aggregate_single", 1))) && tuning("dm_aggregate", 1))
@@ -750,6 +758,151 @@ static int exchange_on(dlesm_halo_plan *p, double *f, unsigned mask, hipStream_t
 {
     double *one[1] = {f};
     return exchange_on(p, one, 1, mask, s, prepacked, skip_unpack);
+}
+
+// ---- what the distributed steps below share: the refusal, the ring tests, and the two hand-overs
+// between the caller's stream and the side stream, each of which stands here ONCE; the rest of a step is its own
+// a wait that gave up leaves halos nobody filled
+static int no_earlier_timeout(const dlesm_halo_plan *p, const char *waits = "frame or halo wait timed out")
+{
+    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
+                  "an earlier distributed step gave up waiting for a flag (%s)", waits);
+    return DLESM_OK;
+}
+
+// the cells of a step's 1-based box, 0-based inclusive as the messages are; is a strip a piece of its one-cell ring?
+struct Box0 {
+    int x0, x1, y0, y1;
+    Box0(int xstart, int xstop, int ystart, int ystop) : x0(xstart - 1), x1(xstop - 1), y0(ystart - 1), y1(ystop - 1) {}
+    bool empty() const { return x1 < x0 || y1 < y0; }
+};
+static bool ring_column(const Msg &m, const Box0 &b)
+{
+    return m.nx == 1 && (m.i0 == b.x0 || m.i0 == b.x1) && m.j0 >= b.y0 && m.j0 + m.ny - 1 <= b.y1;
+}
+// ... or a south/north row (a corner is both).  Of a box that is empty in ONE direction a strip can still be a "column" or a
+// "row": the Jacobi step over the mailboxes takes such a box (its frame launch then only raises the flags), the shallow-water
+// steps ask for !empty() as well
+static bool on_ring(const Msg &m, const Box0 &b)
+{
+    return ring_column(m, b) || (m.ny == 1 && (m.j0 == b.y0 || m.j0 == b.y1) && m.i0 >= b.x0 && m.i0 + m.nx - 1 <= b.x1);
+}
+
+// The strided (west/east) send columns of a one-field exchange, for a frame kernel that drops their cells straight into the
+// send buffer (no pack launch).  prepacked: in, the caller's wish; out, false when a column is off the ring (fp then empty).
+static int frame_columns(dlesm_halo_plan *p, unsigned mask, const Box0 &b, hipStream_t s, FramePack &fp, bool &prepacked)
+{
+    for (const Msg &m : p->sends) {
+        if (m.off < 0 || !dir_enabled(mask, m.dir)) continue;
+        if (!ring_column(m, b) || fp.n == FramePack::MAXS) { prepacked = false; break; }
+        fp.s[fp.n++] = FramePack::Col{m.i0, m.j0, m.ny, m.off};
+    }
+    if (prepacked && fp.n) {
+        if (int rc = ensure_buffers(p, 1, s)) return rc;
+        fp.buf = p->sendbuf;
+    } else {
+        fp.n = 0;
+    }
+    return DLESM_OK;
+}
+
+// THE FUSED HAND-OVER (one launch on the caller's stream, the frame as its first workgroups).  What those need: the counter
+// and the flag they publish frame_seq + 1 through and, chained on a pending step, the flag and number of that step's
+// exchange (halo_seq = 0: no wait; dm_acquire belongs to that wait alone).
+template <class Job>
+static void frame_job_head(Job &job, const dlesm_halo_plan *p, unsigned long long halo_seq)
+{
+    job.counter = p->frame_counter;
+    job.flag = p->frame_flag;
+    job.seq = p->frame_seq + 1;
+    job.halo_flag = p->halo_flag;
+    job.halo_seq = halo_seq;
+    job.timed_out = p->frame_timed_out;
+    job.halo_wait_ticks = remote_wait_ticks();
+    job.acquire = halo_seq ? tuning("dm_acquire", 1) : 0;
+}
+
+// ... the side stream: parked on the frame flag (no event record on the caller's stream), the exchange, then `seq` into the
+// halo flag for whoever waits on the device and ev_comm for whoever waits on a stream
+static int exchange_behind_frame_flag(dlesm_halo_plan *p, double *const *fields, int nf, unsigned mask, unsigned long long seq,
+                                      bool prepacked, bool skip_unpack = false)
+{
+    hipStream_t side = side_stream();
+    if (int rc = launch_frame_flag_wait(p->frame_flag, seq, p->frame_timed_out, side)) return rc;
+    if (int rc = exchange_on(p, fields, nf, mask, side, prepacked, skip_unpack)) return rc;
+    if (int rc = launch_flag_set(p->halo_flag, seq, side)) return rc;
+    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
+    return DLESM_OK;
+}
+
+// ... the caller's stream joins: a one-wave kernel that sleeps on the halo flag (a launch costs the stream ~2.5 us, an event
+// wait 7-8, scripts/syncbench.hip; the halos were released at device scope when the exchange's last kernel ended)
+static int join_fused(dlesm_halo_plan *p, unsigned long long seq, hipStream_t s)
+{
+    if (tuning("dm_flag_join", 1)) return launch_frame_flag_wait(p->halo_flag, seq, p->frame_timed_out, s, true);
+    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
+    return DLESM_OK;
+}
+
+// ... or does not (pipelined): the next step's frame workgroups wait for `seq`, anybody else goes through join_pending.
+// field: its west/east strips were left in the receive buffer (exchanged under `mask`); nullptr: everything was unpacked
+static int leave_pending(dlesm_halo_plan *p, unsigned long long seq, hipStream_t s, double *field, unsigned mask)
+{
+    p->pending = true;
+    p->pending_seq = seq;
+    p->pending_stream = s;
+    p->pending_field = field;
+    if (field) p->pending_mask = mask;
+    return DLESM_OK;
+}
+
+// THE EVENT HAND-OVER (any stream, capturable: fork and join are graph edges).  The caller has launched its frame on `s`:
+// ev_frame lets the side stream start exchange(side) behind it, interior() runs on `s` meanwhile, `s` waits for ev_comm.
+template <class Exchange, class Interior>
+static int overlap_by_events(dlesm_halo_plan *p, hipStream_t s, Exchange &&exchange, Interior &&interior)
+{
+    hipStream_t side = side_stream();
+    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
+    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
+    if (int rc = exchange(side)) return rc;
+    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
+    if (int rc = interior()) return rc;
+    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
+    return DLESM_OK;
+}
+
+// The steps of `depth` time levels per exchange: which sides have a neighbour (a receive filed under Iminus comes from the
+// west, ...) and the depth of the first edge message that is not `depth` deep (0: none) -- refused by each entry in its own words
+struct PlanSides { int w, e, s, n, other; };
+static PlanSides plan_sides(const dlesm_halo_plan *p, int depth)
+{
+    PlanSides sd{0, 0, 0, 0, 0};
+    for (const Msg &m : p->recvs) {
+        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
+        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
+        if (!xdir && !ydir) continue;
+        if ((xdir ? m.nx : m.ny) != depth) { sd.other = xdir ? m.nx : m.ny; break; }
+        (m.dir == DLESM_IMINUS ? sd.w : m.dir == DLESM_IPLUS ? sd.e : m.dir == DLESM_JMINUS ? sd.s : sd.n) = 1;
+    }
+    return sd;
+}
+
+// ... what is left of their box behind a depth-deep frame along those sides (none(): nothing to hide an exchange behind),
+// and the frame itself: thin boxes, south and north over the whole width first
+struct InnerBox {
+    int x0, x1, y0, y1;
+    InnerBox(const PlanSides &sd, int depth, int xstart, int xstop, int ystart, int ystop)
+        : x0(xstart + sd.w * depth), x1(xstop - sd.e * depth), y0(ystart + sd.s * depth), y1(ystop - sd.n * depth) {}
+    bool none() const { return x1 < x0 || y1 < y0; }
+};
+template <class Launch>
+static int frame_strips(const PlanSides &sd, const InnerBox &in, int xstart, int xstop, int ystart, int ystop, Launch &&box)
+{
+    auto strip = [&](int on, int xs, int xe, int ys, int ye) { return on ? box(xs, xe, ys, ye) : DLESM_OK; };
+    if (int rc = strip(sd.s, xstart, xstop, ystart, in.y0 - 1)) return rc;
+    if (int rc = strip(sd.n, xstart, xstop, in.y1 + 1, ystop)) return rc;
+    if (int rc = strip(sd.w, xstart, in.x0 - 1, in.y0, in.y1)) return rc;
+    return strip(sd.e, in.x1 + 1, xstop, in.y0, in.y1);
 }
 
 extern "C" int dlesm_halo_exchange_multi_f64(dlesm_halo_plan *p, double *const *fields, int nfields,
@@ -1110,8 +1263,7 @@ static int peer_join(dlesm_halo_plan *p, hipStream_t s)
 static int jacobi5_step_peer(dlesm_halo_plan *p, const double *in, double *out, int ld, int ny, int xstart, int xstop,
                              int ystart, int ystop, hipStream_t s, bool pipelined)
 {
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
+    if (int rc = no_earlier_timeout(p)) return rc;
     const unsigned mask = tuning("j5_dm_corners", 0) ? DLESM_DIRS_ALL : (DLESM_DIRS_ALL | DLESM_DIRS_NO_DIAGONALS);
     const bool chain = pipelined && p->peer_pending && p->pending_stream == s && p->pending_field == in &&
                        p->pending_mask == mask && tuning("j5_dm_chain", 1);
@@ -1120,7 +1272,7 @@ static int jacobi5_step_peer(dlesm_halo_plan *p, const double *in, double *out, 
     if (int rc = peer_order(p, s)) return rc;
     PeerJob job{};
     const unsigned long long seq = p->peer_seq + 1;
-    const int fx0 = xstart - 1, fx1 = xstop - 1, fy0 = ystart - 1, fy1 = ystop - 1;
+    const Box0 box(xstart, xstop, ystart, ystop);
     for (size_t m = 0; m < p->sends.size(); m++) {
         const Msg &sm = p->sends[m];
         DLESM_REQUIRE(job.nout < PeerJob::MAXM, "more than %d send messages in one peer step", PeerJob::MAXM);
@@ -1128,9 +1280,7 @@ static int jacobi5_step_peer(dlesm_halo_plan *p, const double *in, double *out, 
             job.out[job.nout++] = PeerJob::Out{0, 0, 0, 0, p->peer_tx[m], p->peer_txflag[m]};
             continue;
         }
-        const bool col = sm.nx == 1 && (sm.i0 == fx0 || sm.i0 == fx1) && sm.j0 >= fy0 && sm.j0 + sm.ny - 1 <= fy1;
-        const bool row = sm.ny == 1 && (sm.j0 == fy0 || sm.j0 == fy1) && sm.i0 >= fx0 && sm.i0 + sm.nx - 1 <= fx1;
-        DLESM_REQUIRE(col || row, "peer transport: send strip (%d:%d,%d:%d) is not part of the one-cell frame of the box "
+        DLESM_REQUIRE(on_ring(sm, box), "peer transport: send strip (%d:%d,%d:%d) is not part of the one-cell frame of the box "
                       "(plans of halo depth 1 stepped over their internal region only)", sm.i0 + 1, sm.i0 + sm.nx, sm.j0 + 1, sm.j0 + sm.ny);
         job.out[job.nout++] = PeerJob::Out{sm.i0, sm.j0, sm.nx, sm.ny,
                                            p->peer_tx[m] + (seq & 1) * p->peer_tx_par[m] + p->peer_tx_off[m], p->peer_txflag[m]};
@@ -1174,12 +1324,12 @@ static int jacobi5_step_dm_impl(dlesm_halo_plan *p, const double *in, double *ou
     DLESM_REQUIRE(p != nullptr && in != nullptr && out != nullptr, "null pointer");
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
     if (int rc = ensure_device()) return rc;
-    hipStream_t side = side_stream();
-    if (int rc = capture_ok(p, s, p->peer_on && (g_mailbox || tuning("dm_peer", 1)))) return rc;
+    const bool mailbox = steps_over_mailboxes(p, 0);
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
     const bool comms = !p->sends.empty() || !p->recvs.empty();
     if (!comms) // single tile: one launch over the whole box
         return launch_stencil5(in, out, ld, ny, xstart, xstop, ystart, ystop, s);
-    if (p->peer_on && (g_mailbox || tuning("dm_peer", 1)))      // connected mailboxes: the frame workgroups are the exchange
+    if (mailbox)      // connected mailboxes: the frame workgroups are the exchange
         return jacobi5_step_peer(p, in, out, ld, ny, xstart, xstop, ystart, ystop, s, pipelined);
     // The previous step of a pipelined sequence left its exchange in flight.  If this step can take
     // the one-launch form on the same stream, its frame workgroups wait for that exchange on the
@@ -1194,41 +1344,16 @@ static int jacobi5_step_dm_impl(dlesm_halo_plan *p, const double *in, double *ou
     // (what passing just the needed comm directions does in the reference, pcomms:1557-1571).
     // j5_dm_corners=1 keeps the diagonal messages (halos then equal a full halo_exchange).
     const unsigned mask = tuning("j5_dm_corners", 0) ? DLESM_DIRS_ALL : (DLESM_DIRS_ALL | DLESM_DIRS_NO_DIAGONALS);
-    // 1. the frame of `out`: the only cells a neighbour will ask for.  The west/east columns are
-    //    strided in memory; the frame kernel drops each of their cells straight into its slot of
-    //    the send buffer as well, so no pack launch sits between the frame and the exchange.
+    // 1. the frame of `out`: the only cells a neighbour will ask for, its west/east columns written into the send buffer too
     FramePack fp{};
     bool prepacked = tuning("j5_dm_frame_pack", 1) != 0;
-    for (const Msg &m : p->sends) {
-        if (m.off < 0 || !dir_enabled(mask, m.dir)) continue;
-        const bool on_frame = m.nx == 1 && (m.i0 == xstart - 1 || m.i0 == xstop - 1) && m.j0 >= ystart - 1 &&
-                              m.j0 + m.ny - 1 <= ystop - 1;
-        if (!on_frame || fp.n == FramePack::MAXS) { prepacked = false; break; }
-        fp.s[fp.n++] = FramePack::Col{m.i0, m.j0, m.ny, m.off};
-    }
-    if (prepacked && fp.n) {
-        if (int rc = ensure_buffers(p, 1, s)) return rc;
-        fp.buf = p->sendbuf;
-    } else {
-        fp.n = 0;
-    }
-    // One launch: the frame as the first workgroups of the interior sweep, its completion published
-    // through a flag the side stream is parked on -- no frame launch and no event record on the
-    // caller's stream (each costs it microseconds of a ~180 us step, scripts/syncbench.hip).
-    bool fused = false;
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
+    if (int rc = frame_columns(p, mask, Box0(xstart, xstop, ystart, ystop), s, fp, prepacked)) return rc;
+    if (int rc = no_earlier_timeout(p)) return rc;
+    // the fused hand-over: no frame launch, no event record on the caller's stream (each costs it us of a ~180 us step)
     if (!graph && p->frame_flag && tuning("j5_dm_fused", 1) && streams_run_concurrently(s)) {
         FrameJob job{};
         job.pk = fp;
-        job.counter = p->frame_counter;
-        job.flag = p->frame_flag;
-        job.seq = p->frame_seq + 1;
-        job.halo_flag = p->halo_flag;
-        job.halo_seq = can_chain ? p->pending_seq : 0;
-        job.timed_out = p->frame_timed_out;
-        job.halo_wait_ticks = remote_wait_ticks();
-        job.acquire = tuning("dm_acquire", 1);
+        frame_job_head(job, p, can_chain ? p->pending_seq : 0);
         // chained step: the previous exchange was not unpacked -- `in`'s west/east halo columns are the
         // received strips themselves, read from the receive buffer (the same mask was exchanged)
         const bool virt = can_chain && p->pending_field == in && tuning("j5_dm_lazy_unpack", 1);
@@ -1246,6 +1371,7 @@ static int jacobi5_step_dm_impl(dlesm_halo_plan *p, const double *in, double *ou
             if (int rc = join_pending(p, s)) return rc;
             job.halo_seq = 0;
         }
+        bool fused = false;
         if (int rc = launch_stencil5_framed(in, out, ld, ny, xstart, xstop, ystart, ystop, job, s, &fused)) return rc;
         if (fused) {
             p->frame_seq = job.seq;
@@ -1255,40 +1381,20 @@ static int jacobi5_step_dm_impl(dlesm_halo_plan *p, const double *in, double *ou
             // beside the sweep -- measured: two column-copy kernels cost the sweep 3 us, RCCL itself nothing);
             // the next step reads them there, a join unpacks them
             const bool lazy = pipelined && tuning("j5_dm_lazy_unpack", 1);
-            if (int rc = launch_frame_flag_wait(p->frame_flag, job.seq, p->frame_timed_out, side)) return rc;
-            if (int rc = exchange_on(p, out, mask, side, prepacked, lazy)) return rc;
-            if (int rc = launch_flag_set(p->halo_flag, job.seq, side)) return rc;
-            if (lazy) { p->pending_field = out; p->pending_mask = mask; }
-            DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-        } else if (can_chain) {                          // the arrays do not qualify: fall back to the event join
-            if (int rc = join_pending(p, s)) return rc;
+            double *one[1] = {out};
+            if (int rc = exchange_behind_frame_flag(p, one, 1, mask, job.seq, prepacked, lazy)) return rc;
+            if (pipelined) return leave_pending(p, job.seq, s, lazy ? out : nullptr, mask);
+            return join_fused(p, job.seq, s);
         }
+        if (can_chain)                                   // the arrays do not qualify: fall back to the event join
+            if (int rc = join_pending(p, s)) return rc;
     }
-    if (!fused) {
-        if (int rc = launch_stencil5_frame(in, out, ld, ny, xstart, xstop, ystart, ystop, s, prepacked ? &fp : nullptr))
-            return rc;
-        DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
-        // 2. exchange out's frame on the side stream ...
-        DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
-        if (int rc = exchange_on(p, out, mask, side, prepacked)) return rc;
-        DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-        // 3. ... while the interior streams through HBM on the caller's stream
-        if (int rc = launch_stencil5(in, out, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, s)) return rc;
-    }
-    // 4. join: the next step reads out's halos.  Pipelined one-launch form: left to the next step's
-    //    frame workgroups (device flag) or to dlesm_halo_plan_join, whichever comes first.
-    if (pipelined && fused) {
-        p->pending = true;
-        p->pending_seq = p->frame_seq;
-        p->pending_stream = s;
-        return DLESM_OK;
-    }
-    // joined form of the one-launch step: a one-wave kernel on the caller's stream that sleeps on the
-    // exchange's completion flag -- a kernel launch costs the stream ~2.5 us, an event wait 7-8
-    // (scripts/syncbench.hip); the halos were released at device scope when the exchange's last kernel ended
-    if (fused && tuning("dm_flag_join", 1)) return launch_frame_flag_wait(p->halo_flag, p->frame_seq, p->frame_timed_out, s, true);
-    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-    return DLESM_OK;
+    // the event hand-over: 2. out's frame is exchanged on the side stream 3. while the interior streams through HBM
+    if (int rc = launch_stencil5_frame(in, out, ld, ny, xstart, xstop, ystart, ystop, s, prepacked ? &fp : nullptr))
+        return rc;
+    return overlap_by_events(
+        p, s, [&](hipStream_t side) { return exchange_on(p, out, mask, side, prepacked); },
+        [&] { return launch_stencil5(in, out, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, s); });
 }
 
 extern "C" int dlesm_jacobi5_step_dm(dlesm_halo_plan *p, const double *in, double *out, int ld, int ny,
@@ -1313,65 +1419,42 @@ extern "C" int dlesm_stencil9_step_dm(dlesm_halo_plan *p, const double *in, doub
     DLESM_REQUIRE(p != nullptr && in != nullptr && out != nullptr && coef != nullptr, "null pointer");
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
     if (int rc = ensure_device()) return rc;
-    hipStream_t s = (hipStream_t)stream, side = side_stream();
-    if (int rc = capture_ok(p, s, p->peer_on && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1))))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool mailbox = steps_over_mailboxes(p, 0, true);
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
     if (int rc = join_pending(p, s)) return rc;
     if (p->sends.empty() && p->recvs.empty()) return launch_stencil9(in, out, coef, ld, ny, xstart, xstop, ystart, ystop, s);
     const bool corners = coef[0] != 0.0 || coef[2] != 0.0 || coef[6] != 0.0 || coef[8] != 0.0;
     const unsigned mask = corners ? DLESM_DIRS_ALL : (DLESM_DIRS_ALL | DLESM_DIRS_NO_DIAGONALS);
-    if (p->peer_on && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)))) {
+    if (mailbox) {
         // mailboxes: the whole box, then the two-launch exchange behind it on the same stream (7 us against an RCCL group's 42)
         if (int rc = launch_stencil9(in, out, coef, ld, ny, xstart, xstop, ystart, ystop, s)) return rc;
         return exchange_on(p, out, mask, s);
     }
     FramePack fp{};
     bool prepacked = true;
-    for (const Msg &m : p->sends) {
-        if (m.off < 0 || !dir_enabled(mask, m.dir)) continue;
-        const bool on_frame = m.nx == 1 && (m.i0 == xstart - 1 || m.i0 == xstop - 1) && m.j0 >= ystart - 1 &&
-                              m.j0 + m.ny - 1 <= ystop - 1;
-        if (!on_frame || fp.n == FramePack::MAXS) { prepacked = false; break; }
-        fp.s[fp.n++] = FramePack::Col{m.i0, m.j0, m.ny, m.off};
-    }
-    if (prepacked && fp.n) {
-        if (int rc = ensure_buffers(p, 1, s)) return rc;
-        fp.buf = p->sendbuf;
-    } else {
-        fp.n = 0;
-    }
-    // one launch (frame workgroups inside the interior sweep, device flag to the side stream), as the Jacobi step
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
+    if (int rc = frame_columns(p, mask, Box0(xstart, xstop, ystart, ystop), s, fp, prepacked)) return rc;
+    if (int rc = no_earlier_timeout(p)) return rc;
+    // the fused hand-over, as the Jacobi step (joined form only)
     if (!capturing(s) && p->frame_flag && tuning("s9_dm_fused", 1) && streams_run_concurrently(s)) {
         FrameJob job{};
         job.pk = fp;
-        job.counter = p->frame_counter;
-        job.flag = p->frame_flag;
-        job.seq = p->frame_seq + 1;
-        job.timed_out = p->frame_timed_out;
-        job.halo_wait_ticks = remote_wait_ticks();
+        frame_job_head(job, p, 0);
         bool fused = false;
         if (int rc = launch_stencil9_framed(in, out, coef, ld, ny, xstart, xstop, ystart, ystop, job, s, &fused)) return rc;
         if (fused) {
             p->frame_seq = job.seq;
-            if (int rc = launch_frame_flag_wait(p->frame_flag, job.seq, p->frame_timed_out, side)) return rc;
-            if (int rc = exchange_on(p, out, mask, side, prepacked)) return rc;
-            if (int rc = launch_flag_set(p->halo_flag, job.seq, side)) return rc;
-            DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-            if (tuning("dm_flag_join", 1)) return launch_frame_flag_wait(p->halo_flag, job.seq, p->frame_timed_out, s, true);
-            DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-            return DLESM_OK;
+            double *one[1] = {out};
+            if (int rc = exchange_behind_frame_flag(p, one, 1, mask, job.seq, prepacked)) return rc;
+            return join_fused(p, job.seq, s);
         }
     }
+    // the event hand-over
     if (int rc = launch_stencil9_frame(in, out, coef, ld, ny, xstart, xstop, ystart, ystop, s, prepacked ? &fp : nullptr))
         return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
-    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
-    if (int rc = exchange_on(p, out, mask, side, prepacked)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-    if (int rc = launch_stencil9(in, out, coef, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, s)) return rc;
-    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-    return DLESM_OK;
+    return overlap_by_events(
+        p, s, [&](hipStream_t side) { return exchange_on(p, out, mask, side, prepacked); },
+        [&] { return launch_stencil9(in, out, coef, ld, ny, xstart + 1, xstop - 1, ystart + 1, ystop - 1, s); });
 }
 
 // Distributed form of the fused steps (temporal blocking across tiles): `in` holds valid
@@ -1388,55 +1471,32 @@ extern "C" int dlesm_jacobi5_multi_step_dm(dlesm_halo_plan *p, const double *in,
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
     DLESM_REQUIRE(nsteps >= 2 && nsteps <= 8, "fused distributed step: nsteps = %d (2..8 supported)", nsteps);
     if (int rc = ensure_device()) return rc;
-    hipStream_t s = (hipStream_t)stream, side = side_stream();
+    hipStream_t s = (hipStream_t)stream;
     if (int rc = capture_ok(p, s)) return rc;
     if (int rc = join_pending(p, s)) return rc;
     const int T = nsteps;
-    int hasW = 0, hasE = 0, hasS = 0, hasN = 0;
-    for (const Msg &m : p->recvs) { // a receive filed under Iminus comes from the west neighbour, ...
-        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
-        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
-        if (!xdir && !ydir) continue;
-        DLESM_REQUIRE((xdir ? m.nx : m.ny) == T, "the plan exchanges depth-%d halos, the fused step needs depth %d",
-                      xdir ? m.nx : m.ny, T);
-        if (m.dir == DLESM_IMINUS) hasW = 1;
-        if (m.dir == DLESM_IPLUS) hasE = 1;
-        if (m.dir == DLESM_JMINUS) hasS = 1;
-        if (m.dir == DLESM_JPLUS) hasN = 1;
-    }
-    const int exs = xstart - hasW, exe = xstop + hasE, eys = ystart - hasS, eye = ystop + hasN;
+    const PlanSides sd = plan_sides(p, T);
+    DLESM_REQUIRE(!sd.other, "the plan exchanges depth-%d halos, the fused step needs depth %d", sd.other, T);
+    const int exs = xstart - sd.w, exe = xstop + sd.e, eys = ystart - sd.s, eye = ystop + sd.n;
     auto box = [&](int xs, int xe, int ys, int ye) {
-        return launch_stencil5_multi(in, out, ld, ny, T, xs, xe, ys, ye, exs, exe, eys, eye, hasW, hasE, hasS, hasN, s);
+        return launch_stencil5_multi(in, out, ld, ny, T, xs, xe, ys, ye, exs, exe, eys, eye, sd.w, sd.e, sd.s, sd.n, s);
     };
     const bool comms = !p->sends.empty() || !p->recvs.empty();
     if (!comms) return box(xstart, xstop, ystart, ystop);
-    const int ix0 = xstart + hasW * T, ix1 = xstop - hasE * T, iy0 = ystart + hasS * T, iy1 = ystop - hasN * T;
+    const InnerBox inner(sd, T, xstart, xstop, ystart, ystop);
     // From 7 steps per launch the T-deep frame costs more as four thin launches than the exchange it would hide:
     // measured in loop-back at 8 steps, whole box then exchange 0.3024 / 1.0175 ms (8192^2 / 16384^2) against
     // 0.3116 / 1.0188 overlapped; at 4 steps the overlapped form wins (0.2340 / 0.8013 against 0.2468 / 0.8338).
     const bool serial = T >= 7;
-    if (serial || ix1 < ix0 || iy1 < iy0) { // ... or the tile is all frame: no interior to hide the exchange behind
+    if (serial || inner.none()) { // ... or the tile is all frame: no interior to hide the exchange behind
         if (int rc = box(xstart, xstop, ystart, ystop)) return rc;
         return exchange_on(p, out, DLESM_DIRS_ALL, s);
     }
-    // 1. frame: the T-deep strips along the sides that have a neighbour
-    if (hasS)
-        if (int rc = box(xstart, xstop, ystart, iy0 - 1)) return rc;
-    if (hasN)
-        if (int rc = box(xstart, xstop, iy1 + 1, ystop)) return rc;
-    if (hasW)
-        if (int rc = box(xstart, ix0 - 1, iy0, iy1)) return rc;
-    if (hasE)
-        if (int rc = box(ix1 + 1, xstop, iy0, iy1)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
-    // 2. exchange of out's frame on the side stream ...
-    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
-    if (int rc = exchange_on(p, out, DLESM_DIRS_ALL, side)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-    // 3. ... behind the interior
-    if (int rc = box(ix0, ix1, iy0, iy1)) return rc;
-    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-    return DLESM_OK;
+    // the event hand-over: the T-deep strips along the sides that have a neighbour, out's exchange behind the interior
+    if (int rc = frame_strips(sd, inner, xstart, xstop, ystart, ystop, box)) return rc;
+    return overlap_by_events(
+        p, s, [&](hipStream_t side) { return exchange_on(p, out, DLESM_DIRS_ALL, side); },
+        [&] { return box(inner.x0, inner.x1, inner.y0, inner.y1); });
 }
 
 // The distributed shallow-water step over the mailboxes (a plan connected for >= 3 fields): ONE launch whose ring
@@ -1448,22 +1508,20 @@ extern "C" int dlesm_jacobi5_multi_step_dm(dlesm_halo_plan *p, const double *in,
 static int shallow_step_peer(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
                              int ystop, const SwFields &f, hipStream_t s, const double *smooth_alpha)
 {
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
+    if (int rc = no_earlier_timeout(p)) return rc;
     if (int rc = join_pending(p, s)) return rc;
     if (int rc = peer_order(p, s)) return rc;
     const unsigned long long seq = p->peer_seq + 1;
-    const int fx0 = xstart - 1, fx1 = xstop - 1, fy0 = ystart - 1, fy1 = ystop - 1;
+    const Box0 box(xstart, xstop, ystart, ystop);
     SwFrameJob job{};
     FramePack3 &fp = job.pk;
     DLESM_REQUIRE(p->sends.size() <= (size_t)FramePack3::MAXS && p->recvs.size() <= (size_t)PeerJob::MAXM,
                   "more than %d messages in one peer step", FramePack3::MAXS);
     for (size_t k = 0; k < p->sends.size(); k++) {
         const Msg &m = p->sends[k];
-        const bool in_box = m.i0 >= fx0 && m.i0 + m.nx - 1 <= fx1 && m.j0 >= fy0 && m.j0 + m.ny - 1 <= fy1;
-        const bool on_ring = in_box && ((m.ny == 1 && (m.j0 == fy0 || m.j0 == fy1)) || (m.nx == 1 && (m.i0 == fx0 || m.i0 == fx1)));
-        DLESM_REQUIRE(on_ring, "peer transport: send strip (%d:%d,%d:%d) is not part of the one-cell ring of the box (plans of "
-                      "halo depth 1 stepped over their internal region only)", m.i0 + 1, m.i0 + m.nx, m.j0 + 1, m.j0 + m.ny);
+        DLESM_REQUIRE(!box.empty() && on_ring(m, box), "peer transport: send strip (%d:%d,%d:%d) is not part of the one-cell ring "
+                      "of the box (plans of halo depth 1 stepped over their internal region only)", m.i0 + 1, m.i0 + m.nx, m.j0 + 1,
+                      m.j0 + m.ny);
         fp.s[fp.n] = FramePack3::S{m.i0, m.j0, m.nx, m.ny, 0};
         fp.base[fp.n] = p->peer_tx[k] + (seq & 1) * p->peer_tx_par[k] + 3 * p->peer_tx_off[k];
         job.peer_flag[fp.n] = p->peer_txflag[k];
@@ -1509,8 +1567,8 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
     DLESM_REQUIRE(p != nullptr && q != nullptr, "null pointer");
     DLESM_REQUIRE(p->ld == ld && p->ny == ny, "plan is for %dx%d fields, got %dx%d", p->ld, p->ny, ld, ny);
     if (int rc = ensure_device()) return rc;
-    hipStream_t side = side_stream();
-    if (int rc = capture_ok(p, s, p->peer_on && p->peer_fcap >= 3 && (g_mailbox || tuning("dm_peer", 1)))) return rc;
+    const bool mailbox = steps_over_mailboxes(p, 3);
+    if (int rc = capture_ok(p, s, mailbox)) return rc;
     const bool graph = capturing(s);
     if (graph) pipelined = false;
     // time-loop form: a previous pipelined step on this stream left its exchange in flight; the frame
@@ -1527,7 +1585,7 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
     DLESM_REQUIRE(!g_mailbox || (p->peer_on && p->peer_fcap >= 3),
                   "mailbox mode: the distributed shallow-water step exchanges three fields, this plan's mailboxes have room for %d "
                   "(DLESM_MAILBOX_FIELDS / tuning mailbox_fields, default 3)", p->peer_fcap);
-    if (p->peer_on && p->peer_fcap >= 3 && (g_mailbox || tuning("dm_peer", 1)))      // mailboxes connected for three fields
+    if (mailbox)      // mailboxes connected for three fields
         return shallow_step_peer(p, q, ld, ny, xstart, xstop, ystart, ystop, f, s, smooth_alpha);
     // 1. frame: the one-cell ring of the box, one cell per thread, all four sides, its west/east columns
     //    written straight into the send buffers of the three new fields -- no pack launches.
@@ -1539,13 +1597,10 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
         // every message of a depth-1 exchange is a piece of the frame ring: the frame cells go straight
         // into their slots of the aggregated send buffer (3 strips per message), no pack launch
         prepacked = true;
-        const int fx0 = xstart - 1, fx1 = xstop - 1, fy0 = ystart - 1, fy1 = ystop - 1;
+        const Box0 ring(xstart, xstop, ystart, ystop);
         for (size_t k = 0; k < p->sends.size(); k++) {
             const Msg &m = p->sends[k];
-            const bool in_box = m.i0 >= fx0 && m.i0 + m.nx - 1 <= fx1 && m.j0 >= fy0 && m.j0 + m.ny - 1 <= fy1;
-            const bool on_ring = in_box && ((m.ny == 1 && (m.j0 == fy0 || m.j0 == fy1)) ||
-                                            (m.nx == 1 && (m.i0 == fx0 || m.i0 == fx1)));
-            if (!on_ring || fp.n == FramePack3::MAXS) { prepacked = false; break; }
+            if (ring.empty() || !on_ring(m, ring) || fp.n == FramePack3::MAXS) { prepacked = false; break; }
             fp.s[fp.n++] = FramePack3::S{m.i0, m.j0, m.nx, m.ny, 3 * p->sagg[k]};
         }
         if (prepacked && fp.n) {
@@ -1557,47 +1612,24 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
         }
     }
     double *fields[3] = {f.unew, f.vnew, f.pnew};
-    // One launch (as the Jacobi step): the ring as the first workgroups of the interior sweep, a device flag
-    // hands it to the exchange on the side stream -- no frame launch, no event record on the caller's stream.
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame wait timed out)");
+    // The fused hand-over (as the Jacobi step): the ring as the first workgroups of the interior sweep.
+    if (int rc = no_earlier_timeout(p, "frame wait timed out")) return rc;
     if (one_frame && !graph && p->frame_flag && tuning("sw_dm_fused", 1) && streams_run_concurrently(s)) {
         SwFrameJob job{};
         job.pk = fp;
-        job.counter = p->frame_counter;
-        job.flag = p->frame_flag;
-        job.seq = p->frame_seq + 1;
-        job.halo_flag = p->halo_flag;
-        job.halo_seq = can_chain ? p->pending_seq : 0;
-        job.timed_out = p->frame_timed_out;
-        job.halo_wait_ticks = remote_wait_ticks();
-        job.acquire = tuning("dm_acquire", 1);
+        frame_job_head(job, p, can_chain ? p->pending_seq : 0);
         bool fused = false;
         if (int rc = launch_shallow_framed(*q, ld, ny, xstart, xstop, ystart, ystop, f, job, s, &fused, smooth_alpha)) return rc;
         if (fused) {
             p->frame_seq = job.seq;
             p->pending = false;                          // the chained wait (if any) is inside the launch
-            if (int rc = launch_frame_flag_wait(p->frame_flag, job.seq, p->frame_timed_out, side)) return rc;
-            if (int rc = exchange_on(p, fields, 3, DLESM_DIRS_ALL, side, prepacked)) return rc;
-            if (int rc = launch_flag_set(p->halo_flag, job.seq, side)) return rc;
-            DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-            if (pipelined) {                             // joined by the next step's frame workgroups, or by a join
-                p->pending = true;
-                p->pending_seq = job.seq;
-                p->pending_stream = s;
-                p->pending_field = nullptr;
-                return DLESM_OK;
-            }
-            if (tuning("dm_flag_join", 1))               // as in the Jacobi step: a flag-wait kernel instead of an event wait
-                return launch_frame_flag_wait(p->halo_flag, job.seq, p->frame_timed_out, s, true);
-            DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-            return DLESM_OK;
+            if (int rc = exchange_behind_frame_flag(p, fields, 3, DLESM_DIRS_ALL, job.seq, prepacked)) return rc;
+            if (pipelined) return leave_pending(p, job.seq, s, nullptr, 0);
+            return join_fused(p, job.seq, s);
         }
-        if (can_chain)                                   // the arrays do not qualify: fall back to the event join
-            if (int rc = join_pending(p, s)) return rc;
-    } else if (can_chain) {
-        if (int rc = join_pending(p, s)) return rc;
     }
+    if (can_chain)                                       // not fused after all (arrays that do not qualify): the event join
+        if (int rc = join_pending(p, s)) return rc;
     if (one_frame) {
         if (int rc = launch_shallow_frame(*q, ld, ny, xstart, xstop, ystart, ystop, f, prepacked ? &fp : nullptr, s, smooth_alpha))
             return rc;
@@ -1609,15 +1641,10 @@ static int shallow_step_dm_impl(dlesm_halo_plan *p, const dlesm_sw_params *q, in
         if (xstop > xstart)
             if (int rc = box(xstop, xstop, ystart + 1, ystop - 1)) return rc;
     }
-    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
-    // 2. grouped exchange of the three new fields on the side stream ...
-    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
-    if (int rc = exchange_on(p, fields, 3, DLESM_DIRS_ALL, side, prepacked)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-    // 3. ... behind the interior
-    if (int rc = box(xstart + 1, xstop - 1, ystart + 1, ystop - 1)) return rc;
-    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-    return DLESM_OK;
+    // The event hand-over: 2. grouped exchange of the three new fields on the side stream 3. behind the interior
+    return overlap_by_events(
+        p, s, [&](hipStream_t side) { return exchange_on(p, fields, 3, DLESM_DIRS_ALL, side, prepacked); },
+        [&] { return box(xstart + 1, xstop - 1, ystart + 1, ystop - 1); });
 }
 
 extern "C" int dlesm_shallow_step_dm(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart,
@@ -1687,23 +1714,14 @@ static int shallow_x2_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_s
         return dlesm_shallow_step_x2_f64(q, ld, ny, xstart, xstop, ystart, ystop, all[0], all[1], all[2], all[3], all[4], all[5], w[6],
                                          w[7], w[8], w[9], w[10], w[11], s);
     }
-    DLESM_REQUIRE(!p->frame_timed_out || *(volatile int *)p->frame_timed_out == 0,
-                  "an earlier distributed step gave up waiting for a flag (frame or halo wait timed out)");
-    const bool mailbox = p->peer_on && p->peer_fcap >= 3 && (g_mailbox || tuning("dm_peer", 1));
+    if (int rc = no_earlier_timeout(p)) return rc;
+    const bool mailbox = steps_over_mailboxes(p, 3);
     if (int rc = capture_ok(p, s, mailbox)) return rc;
     if (int rc = join_pending(p, s)) return rc;
-    int gw = 0, ge = 0, gs = 0, gn = 0;
-    for (const Msg &m : p->recvs) {      // as dlesm_jacobi5_multi_step_dm: a receive filed under Iminus comes from the west, ...
-        const bool xdir = m.dir == DLESM_IMINUS || m.dir == DLESM_IPLUS;
-        const bool ydir = m.dir == DLESM_JMINUS || m.dir == DLESM_JPLUS;
-        if (!xdir && !ydir) continue;
-        DLESM_REQUIRE((xdir ? m.nx : m.ny) == 2, "%s: the plan exchanges depth-%d halos, two steps per launch need depth 2 "
-                      "(dlesm_map_comms_depth, depth = 2)", who, xdir ? m.nx : m.ny);
-        if (m.dir == DLESM_IMINUS) gw = 1;
-        if (m.dir == DLESM_IPLUS) ge = 1;
-        if (m.dir == DLESM_JMINUS) gs = 1;
-        if (m.dir == DLESM_JPLUS) gn = 1;
-    }
+    const PlanSides sd = plan_sides(p, 2);
+    DLESM_REQUIRE(!sd.other, "%s: the plan exchanges depth-%d halos, two steps per launch need depth 2 "
+                  "(dlesm_map_comms_depth, depth = 2)", who, sd.other);
+    const int gw = sd.w, ge = sd.e, gs = sd.s, gn = sd.n;        // stage 1 grows by one cell towards every neighbour
     DLESM_REQUIRE(!g_mailbox || mailbox, "mailbox mode: %s exchanges three fields at a time, this plan's mailboxes have room for %d",
                   who, p->peer_fcap);
     if (xstop < xstart || ystop < ystart) return DLESM_OK;
@@ -1747,35 +1765,19 @@ static int shallow_x2_dm_impl(const char *who, dlesm_halo_plan *p, const dlesm_s
         DLESM_HIP_TRY(hipGetLastError());
         return DLESM_OK;
     };
-    const int ix0 = xstart + 2 * gw, ix1 = xstop - 2 * ge, iy0 = ystart + 2 * gs, iy1 = ystop - 2 * gn;
+    const InnerBox inner(sd, 2, xstart, xstop, ystart, ystop);
     // Whole box, then the exchange, by default: the four thin 2-row frame launches cost more than the exchange they hide.
     // Measured in loop-back (scripts/sw_x2_dm_timing.py, profiles/r05_sw_x2_dm_loopback.json), ms per time step, medians of 7
     // interleaved windows, serial / frame-overlapped: plain 8192^2 0.637 / 0.669 (RCCL), 0.620 / 0.659 (mailboxes); 4096^2
     // 0.175 / 0.182, 0.162 / 0.191; filtered 8192^2 0.654 / 0.683, 0.669 / 0.691.  sw_x2_dm_overlap = 1 (HOOK): the overlapped form.
     const bool serial = !tuning("sw_x2_dm_overlap", 0);
-    if (serial || ix1 < ix0 || iy1 < iy0) {      // ... or the tile is all frame: no interior to hide the exchange behind
+    if (serial || inner.none()) {      // ... or the tile is all frame: no interior to hide the exchange behind
         if (int rc = box(xstart, xstop, ystart, ystop)) return rc;
         return exchange(s);
     }
-    hipStream_t side = side_stream();
-    // 1. frame: the 2-deep strips of the new level(s) along the sides that have a neighbour
-    if (gs)
-        if (int rc = box(xstart, xstop, ystart, iy0 - 1)) return rc;
-    if (gn)
-        if (int rc = box(xstart, xstop, iy1 + 1, ystop)) return rc;
-    if (gw)
-        if (int rc = box(xstart, ix0 - 1, iy0, iy1)) return rc;
-    if (ge)
-        if (int rc = box(ix1 + 1, xstop, iy0, iy1)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_frame, s));
-    // 2. exchange of the frame on the side stream ...
-    DLESM_HIP_TRY(hipStreamWaitEvent(side, p->ev_frame, 0));
-    if (int rc = exchange(side)) return rc;
-    DLESM_HIP_TRY(hipEventRecord(p->ev_comm, side));
-    // 3. ... behind the interior
-    if (int rc = box(ix0, ix1, iy0, iy1)) return rc;
-    DLESM_HIP_TRY(hipStreamWaitEvent(s, p->ev_comm, 0));
-    return DLESM_OK;
+    // the event hand-over: the 2-deep strips of the new level(s) along the sides that have a neighbour, then as above
+    if (int rc = frame_strips(sd, inner, xstart, xstop, ystart, ystop, box)) return rc;
+    return overlap_by_events(p, s, exchange, [&] { return box(inner.x0, inner.x1, inner.y0, inner.y1); });
 }
 
 extern "C" int dlesm_shallow_step_x2_dm(dlesm_halo_plan *p, const dlesm_sw_params *q, int ld, int ny, int xstart, int xstop, int ystart,
@@ -1916,12 +1918,6 @@ static int ssha_ring_launch(const RingRects &r, const NemoFlow &fl, int ld, hipS
     return DLESM_OK;
 }
 
-// true: the exchange goes over the plan's connected mailboxes (always in mailbox mode), in turns of at most peer_fcap fields
-static bool exchange_over_mailboxes(const dlesm_halo_plan *p)
-{
-    return p->peer_on && p->peer_fcap > 0 && (g_mailbox || (tuning("dm_peer", 1) && tuning("dm_peer_exchange", 1)));
-}
-
 // ONE exchange of nf fields; over mailboxes ceil(nf / turn) mailbox operations per call on every rank -- nothing rank-local
 // (obc, the wet plan, the path the step takes, the box) changes that number; over RCCL (turn == nf) one aggregated group
 static int exchange_in_turns(dlesm_halo_plan *p, double *const *fields, int nf, int turn, hipStream_t s)
@@ -2017,7 +2013,7 @@ static int nemolite_dm_step(const NemoDmStep &d, dlesm_halo_plan *p, int ld, int
     if (fl)
         for (double *o : {fl->ssha, fl->ssha_u, fl->ssha_v, fl->ua, fl->va}) outs[nf++] = o;
     for (int k = 0; k < t.ntracers; k++) outs[nf++] = t.c_out[k];
-    const bool mailbox = exchange_over_mailboxes(p);
+    const bool mailbox = steps_over_mailboxes(p, 1, true);    // in turns of at most peer_fcap fields
     if (int rc = capture_ok(p, s, mailbox)) return rc;
     if (d.agg_early && !mailbox && tuning("dm_aggregate", 1))
         if (int rc = ensure_agg(p, nf, s)) return rc;

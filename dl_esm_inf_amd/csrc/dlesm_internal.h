@@ -135,7 +135,8 @@ __device__ __forceinline__ double pin_here(double x)
                             __builtin_amdgcn_mov_dpp(__double2loint(x), 0xE4, 0xf, 0xf, true));
 }
 
-// shared by the frame/interior split of the distributed step (dlesm_halo.hip)
+// the launches behind the frame/interior split of the distributed steps (dlesm_halo.hip: their two hand-overs stand there once,
+// exchange_behind_frame_flag and overlap_by_events)
 int launch_stencil5(const double *in, double *out, int ld, int ny, int xstart, int xstop,
                     int ystart, int ystop, hipStream_t s);
 // columns of the frame that are also send strips: the frame kernel writes their cells into
