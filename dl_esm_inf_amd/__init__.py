@@ -28,3 +28,4 @@ from .psy import particle_order, particle_permute, particle_sort  # noqa: E402,F
 from .psy import cell_bin  # noqa: E402,F401
 from .psy import particle_migrate, particle_pack, particle_unpack, particle_exchange  # noqa: E402,F401
 from .psy import migrate_message, migrate_neighbours, MigrateError  # noqa: E402,F401
+from .psy import release_sources, particle_release, ReleaseError  # noqa: E402,F401

@@ -27,6 +27,7 @@ DRIFTER_FREE = 4                       # DLESM_DRIFTER_FREE: a slot that holds n
 MIGRATE_MAX_PAYLOAD = 4                # DLESM_MIGRATE_MAX_PAYLOAD
 MIGRATE_W, MIGRATE_E, MIGRATE_S, MIGRATE_N = range(4)   # DLESM_MIGRATE_*: the order of every per-direction array
 MIGRATE_X, MIGRATE_Y = 0, 1
+RELEASE_MAX_SOURCES = 65536            # DLESM_RELEASE_MAX_SOURCES (dlesm_release_f64)
 TRACER_UPWIND, TRACER_MUSCL, TRACER_HANCOCK = 0, 1, 2   # scheme of dlesm_nemolite_coupled_step_dm
 LOCATE_NONFINITE, LOCATE_EQUAL = 0, 1  # dlesm_field_locate_f64
 DIRS_EDGES_ONLY = DIRS_ALL | DIRS_NO_DIAGONALS
@@ -157,7 +158,23 @@ class MigrateCounts(C.Structure):
             list(self.sent), list(self.held), list(self.arrived), self.dropped, self.nfree, self.bad_message)
 
 
-MOMENTUM_GRID_ARRAYS = ("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
+class ReleaseSource(C.Structure):
+    """dlesm_release_source: one particle source of the device table"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("rx", C.c_double), ("ry", C.c_double), ("next_id", C.c_longlong),
+                ("count", C.c_longlong), ("tag", C.c_longlong), ("pad", C.c_longlong)]
+
+
+class ReleaseCounts(C.Structure):
+    """dlesm_release_counts: what a release did"""
+    _fields_ = [("requested", C.c_longlong), ("released", C.c_int), ("foreign", C.c_int), ("on_land", C.c_int),
+                ("dropped", C.c_int), ("edge", C.c_int), ("nfree", C.c_int), ("clamped", C.c_int), ("bad_source", C.c_int),
+                ("pad", C.c_int * 6)]
+
+    def __repr__(self):
+        return "ReleaseCounts(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_[:9]) + ")"
+
+
+MOMENTUM_GRID_ARRAYS =("tmask", "dx_t", "dy_t", "dx_u", "dy_u", "dx_v", "dy_v", "area_u", "area_v", "fcor_u", "fcor_v")
 
 
 class MomentumGrid(C.Structure):
@@ -338,6 +355,9 @@ PROTOTYPES = {
     "dlesm_migrate_exchange": (_i, [_pi, C.POINTER(_vp), C.POINTER(_vp), C.c_longlong, _vp]),
     "dlesm_migrate_f64": (_i, [_i] * 4 + [C.c_longlong] + [_vp] * 4 + [C.POINTER(_vp), _i, _pi, _pi, _pi, C.c_longlong, _vp, _vp,
                                C.c_longlong, _vp]),
+    "dlesm_release_scratch": (_i, [C.c_longlong, _i, _i, C.POINTER(C.c_longlong)]),
+    "dlesm_release_f64": (_i, [_i] * 8 + [_vp, _vp, _i, _i, C.c_longlong, C.c_longlong, _vp, C.c_longlong] + [_vp] * 8 +
+                          [C.c_longlong, _vp]),
     "dlesm_dispersal_step_f64": (_i, [_d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 5 + [C.c_longlong] +
                                  [_vp] * 5),
     "dlesm_dispersal_step_set": (_i, [_vp, _d, _i, _d, C.c_longlong, C.c_longlong, _vp] + [_i] * 6 + [_vp] * 6),

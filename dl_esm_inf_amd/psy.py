@@ -934,6 +934,92 @@ def particle_migrate(px, py, status, ids, grid_or_field, payload=(), cap=None, w
     return rec
 
 
+class ReleaseError(_cabi.DlesmError):
+    """particle_release dropped particles for want of FREE slots, clamped a source or met a bad one; .counts holds the record"""
+
+
+def release_sources(x, y, rx, ry, first_id, count=0, tag=None, device="cuda"):
+    """the device table of particle sources: an int64 CUDA tensor of nsources x 8 words, one
+    dlesm_release_source a row -- x, y, rx, ry as the bits of doubles, next_id, count, tag, pad.  x, y: the centres in GLOBAL
+    index coordinates; rx, ry: the half-widths in cells (0: a point source); first_id: the id of each source's first
+    particle -- give every source a range of its own; count: the particles wanted at the next call; tag: 8 bytes stored with
+    every particle of the source (default: the source's number).  Every argument is a number or a sequence of nsources; every
+    rank builds the same table.  Column 5 of the tensor may be rewritten between calls to change the rate."""
+    import numpy as np
+    import torch
+    cols = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (x, y, rx, ry)]
+    ns = max([c.size for c in cols] + [np.atleast_1d(np.asarray(v)).size for v in (first_id, count)])
+    if ns > _cabi.RELEASE_MAX_SOURCES:
+        raise _cabi.DlesmError(_cabi.EINVAL, "release_sources: %d sources (at most %d)" % (ns, _cabi.RELEASE_MAX_SOURCES))
+    table = np.zeros((ns, 8), dtype=np.int64)
+    for k, c in enumerate(cols):
+        table[:, k] = np.broadcast_to(c, (ns,)).copy().view(np.int64)
+    table[:, 4] = np.broadcast_to(np.asarray(first_id, dtype=np.int64), (ns,))
+    table[:, 5] = np.broadcast_to(np.asarray(count, dtype=np.int64), (ns,))
+    table[:, 6] = np.arange(ns) if tag is None else np.broadcast_to(np.asarray(tag, dtype=np.int64), (ns,))
+    return torch.from_numpy(table).to(device)
+
+
+def particle_release(sources, px, py, status, ids, grid_or_field, seed, tick=0, tick_dev=None, tag=None, born=None,
+                     max_count=None, scratch=None, stream=None, wait=True):
+    """create this call's particles of every source in the FREE slots of the set (dlesm_release_f64).
+    sources: release_sources' table, the same on every rank; its next_id column advances by what each source gave.  px, py,
+    status, ids as particle_migrate.  The box is the T internal region of the grid, offx = glob.xstart - internal.xstart of this
+    rank's subdomain (0 without a decomposition), the difference migrate_neighbours uses; a candidate outside this rank's tile
+    is another rank's.  seed, tick, tick_dev as dispersal_step; tag, born: None or contiguous int64 CUDA tensors of one element
+    per slot that receive the source's tag and tick + *tick_dev.  max_count: the most one source may give in a call (default:
+    the largest count of the table, read once from the device -- pass it for a captured loop).  scratch: a uint8 CUDA tensor
+    of dlesm_release_scratch bytes to reuse, or None.  wait=True returns the _cabi.ReleaseCounts record after the call and raises
+    ReleaseError if particles were dropped, a source was clamped or a source was bad; wait=False returns the record on the
+    device, an int32 CUDA tensor of 16 elements, without a synchronisation."""
+    import torch
+    who = "particle_release"
+    n = _drifter_arrays(who, px, py, status)
+
+    def slots(t):
+        return t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and t.numel() == n
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    if not slots(ids) or any(t is not None and not slots(t) for t in (tag, born)):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: ids, tag and born are contiguous int64 CUDA tensors of one element per slot" % who)
+    if not (sources.is_cuda and sources.is_contiguous() and sources.dtype == torch.int64 and sources.dim() == 2 and
+            sources.shape[1] == 8):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: sources is release_sources' int64 CUDA tensor of nsources x 8" % who)
+    if tick_dev is not None and not (tick_dev.is_cuda and tick_dev.dtype == torch.int64 and tick_dev.numel() == 1):
+        raise _cabi.DlesmError(_cabi.EINVAL, "%s: tick_dev is a one-element int64 CUDA tensor" % who)
+    ns = sources.shape[0]
+    grid, box = _box_of(grid_or_field)
+    offx = offy = 0
+    if grid.decomp is not None:
+        me = grid.decomp.subdomains[parallel_mod.get_rank() - 1]
+        offx, offy = me.glob.xstart - me.internal.xstart, me.glob.ystart - me.internal.ystart
+    if max_count is None:
+        max_count = max(1, int(sources[:, 5].max().item())) if ns else 1
+    seed = int(seed) & 0xffffffffffffffff
+    need = C.c_longlong()
+    check(_cabi.lib().dlesm_release_scratch(n, ns, int(max_count), C.byref(need)))
+    with _on(stream):
+        if scratch is None:
+            scratch = torch.empty(max(need.value, 16), dtype=torch.uint8, device=px.device)
+        counts = torch.empty(16, dtype=torch.int32, device=px.device)
+        check(_cabi.lib().dlesm_release_f64(
+            grid.nx, grid.ny, *box, offx, offy, grid.tmask_device_ptr, ptr(sources), ns, int(max_count),
+            seed - (1 << 64) if seed >> 63 else seed, int(tick), ptr(tick_dev), n, ptr(px), ptr(py), ptr(status), ptr(ids),
+            ptr(tag), ptr(born), ptr(counts), ptr(scratch), scratch.numel(), _stream_ptr(stream)))
+        if not wait:
+            return counts
+        host = counts.cpu().numpy()
+    rec = _cabi.ReleaseCounts.from_buffer_copy(host.tobytes())
+    if rec.dropped or rec.clamped or rec.bad_source:
+        e = ReleaseError(_cabi.EINVAL, "%s: %d particles dropped for want of FREE slots, %d sources clamped to max_count, %d "
+                         "bad sources" % (who, rec.dropped, rec.clamped, rec.bad_source))
+        e.counts = rec
+        raise e
+    return rec
+
+
 TRACER_SCHEMES = {"upwind": _cabi.TRACER_UPWIND, "muscl": _cabi.TRACER_MUSCL, "hancock": _cabi.TRACER_HANCOCK}
 
 

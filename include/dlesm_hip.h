@@ -1482,6 +1482,62 @@ int dlesm_migrate_f64(int xstart, int xstop, int ystart, int ystop, long long n,
                       const int *shift_y, long long cap, dlesm_migrate_counts *counts, void *work, long long work_bytes,
                       void *stream);
 
+/* Particle sources that fill FREE slots on the device: particles are created during the run, at a rate,
+ * at places -- a spill, a spawning reef, an outfall -- without a copy of the set to the host, and a run on any decomposition
+ * releases the particles of the undivided run.  `sources` is a DEVICE table of nsources records; every rank passes the same
+ * table, seed and max_count and its own box, offx = global minus local x of its tile (0 on an undivided grid), offy likewise.
+ * Every operation is rounded in double in the order written.
+ * Source s is VALID iff x, y, rx, ry are finite, rx >= 0, ry >= 0 and count >= 0.  An invalid source gives c_s = 0, adds 1 to
+ * bad_source and keeps its next_id; a valid one gives c_s = min(count, max_count), and clamped counts those with count >
+ * max_count.  requested = sum of c_s.  Candidate (s, m), 0 <= m < c_s, with 64-bit wrapping id arithmetic:
+ *     id = next_id_s + m
+ *     w  = philox4x32_10(counter = (lo32(id), 1, hi32(id), 0), key = (lo32(seed), hi32(seed)))
+ *     gx = x_s + rx_s * philox_sym(w[0])          gy = y_s + ry_s * philox_sym(w[1])
+ * (section 6.20's generator and its rx expression; its kicks have 0 in the counter's second word, so no release number is a
+ * kick number).  A position depends on the id and the seed alone.  The candidate is OWNED iff gx and gy are finite,
+ * (double)((long long)xstart + offx) <= gx < (double)((long long)xstop + 1 + offx) and the same in y: the tiles of a
+ * decomposition tile the global box, so exactly one rank owns a candidate inside the domain.  One that is not owned adds 1 to
+ * `foreign` and nothing else.  An owned one has lx = gx - (double)offx, ly = gy - (double)offy.  !inbox(lx, ly) (section
+ * 6.17's; only when the subtraction rounds up onto the upper edge): ACCEPTED with status LEFT, counted by `edge`, for section
+ * 6.21 to hand over.  Otherwise T = tmask(cell(lx, ly)): T == 0 adds 1 to on_land and creates nothing, T != 0 is ACCEPTED as
+ * ACTIVE (on an open cell the next step's entry test classifies it).  The accepted, ordered source-major with m ascending:
+ * accepted k takes the k-th FREE slot p in ascending slot order and stores px[p] = lx, py[p] = ly, status[p], id[p] = id,
+ * tag[p] = tag_s if tag is not NULL, born[p] = tick + (tick_dev ? *tick_dev : 0) if born is not NULL; those beyond the FREE
+ * slots add to `dropped` and are lost.  released: the number stored; nfree: the FREE slots afterwards; edge counts every
+ * accepted LEFT candidate, stored or not; requested == released + dropped + foreign + on_land.  No other slot and no other
+ * word is written.  Then next_id_s += c_s for every valid source, on the stream, behind the fill: ids are consumed whether or
+ * not a candidate was owned, wet or placed, so every rank's table advances alike and a captured graph releases fresh ids at
+ * every replay.  tick_dev is only read.
+ * Asynchronous on `stream`; no allocation, no host synchronisation, no global atomics, plain vector stores; capturable.
+ * scratch: device memory, 16-byte aligned, of at least dlesm_release_scratch(n, nsources, max_count) bytes (tables of counts and
+ * a staging area of min(n, nsources * max_count) records of 36 bytes).  n == 0, nsources == 0 or an empty box: counts is filled
+ * as the rule gives, ids advance, 0 is returned.  DLESM_EINVAL before anything is launched: a null tmask, sources, px, py,
+ * status, id, counts or scratch; sources, px, py, id, tag, born, tick_dev or counts not 8-byte aligned, tmask or status not
+ * 4-byte aligned, scratch not 16-byte aligned; n outside 0..2^31-1; nsources outside 0..DLESM_RELEASE_MAX_SOURCES; max_count
+ * < 1, nsources * max_count > 2^31-1 or nsources * ceil(max_count / 256) > 2^22; tick < 0; a box that does not fit ld x ny
+ * with its one-cell ring; scratch_bytes too small; a written array (px, py, status, id, tag, born, sources, counts, scratch)
+ * overlapping any other array.  DLESM_ENODEV without a device. */
+typedef struct dlesm_release_source {   /* 64 bytes, no holes; a DEVICE table of nsources of them */
+    double x, y;          /* centre of the patch, GLOBAL index coordinates (T cell (i,j) covers [i,i+1) x [j,j+1)) */
+    double rx, ry;        /* half-widths in cells, >= 0; 0 = a point source */
+    long long next_id;    /* id of this source's next particle; the call advances it */
+    long long count;      /* particles wanted from this source at the next call; the call leaves it alone */
+    long long tag;        /* any 8 bytes (a source number, a mass as double bits): stored per new particle */
+    long long pad;
+} dlesm_release_source;
+typedef struct dlesm_release_counts {   /* 64 bytes, no holes, on the device */
+    long long requested;
+    int released, foreign, on_land, dropped, edge, nfree, clamped, bad_source;
+    int pad[6];
+} dlesm_release_counts;
+enum { DLESM_RELEASE_MAX_SOURCES = 65536 };
+int dlesm_release_scratch(long long n, int nsources, int max_count, long long *bytes);   /* needs no device */
+int dlesm_release_f64(int ld, int ny, int xstart, int xstop, int ystart, int ystop, int offx, int offy, const int *tmask,
+                      dlesm_release_source *sources, int nsources, int max_count, long long seed, long long tick,
+                      const long long *tick_dev, long long n, double *px, double *py, int *status, long long *id,
+                      long long *tag, long long *born, dlesm_release_counts *counts, void *scratch,
+                      long long scratch_bytes, void *stream);
+
 /* One coupled time step on a decomposed grid: the flow from level n to n+1 and ntracers
  * (0..DLESM_TRACER_MAX) tracers carried by the level-n transports into the new water column, on ONE plan of depth 1 or 2, with
  * ONE exchange of the 5 + ntracers outputs.  Bit for bit, in every cell of every array (halos and padding included), what this
